@@ -12,16 +12,23 @@ columns, 1 MI355X -- per rank (weak scaling: every rank generates its own
 Rank 0 prints ONE JSON line.
 
 Timed region: the K steps are captured in ONE hipGraph; after W untimed warm-up
-steps the graph is replayed REPLAYS times, each replay bracketed by barrier +
-synchronize and timed on its own (wall clock and HIP events on the launch
-stream).  `value` and `ms_per_step` come from the MEDIAN replay (exactly K
-steps); every replay, min and max are in `timing`.
+steps the graph is replayed --replays times (1 by default: exactly K timed
+steps; REPLAYS with --full), each replay bracketed by barrier + synchronize and
+timed on its own (wall clock and HIP events on the launch stream).  `value` and
+`ms_per_step` come from the MEDIAN replay (exactly K steps); every replay, min
+and max are in `timing`.
+
+A plain run does only that and prints the line.  --dump-outputs DIR also writes
+a fixed sample of what the last timed step computed (dump_outputs()).  --full
+adds everything else, as before: the parity gate and device check, the
+secondary measurements (`extra`), the CPU baseline and, with N>1, the gather /
+configs[3] / configs[4] tail.
 
 roofline.achieved = algorithmic bytes per launch (3992 B/block per-block keys,
 3040 B/block shared key: SURVEY.md 8(d)) / mean launch duration of
 the median replay from HIP events; frac_events and frac_wall are both given.
-cpu_baseline = the CPU oracle (a port of the reference's value path, NOT the
-reference: Rust + halo2 cannot be built here) timed on this box's host cores on
+cpu_baseline (--full) = the CPU oracle (a port of the reference's value path, NOT the
+reference: Rust + halo2 cannot be built here) timed on the host's cores on
 a bounded sample of the same workload shape, N=1 only.
 """
 from __future__ import annotations
@@ -57,8 +64,15 @@ def parse():
     ap.add_argument("--workload", choices=["c1", "c2"], default="c2",
                     help="c2 = 2^20 blocks per-block keys + key witness (BASELINE configs[2], the headline); c1 = 2^16 blocks shared key (configs[1])")
     ap.add_argument("--log2-blocks", type=int, default=None, help="override the batch size (per rank)")
-    ap.add_argument("--replays", type=int, default=REPLAYS, help="timed replays of the K-step graph (median reported)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--replays", type=int, default=None,
+                    help="timed replays of the K-step graph (median reported); default 1, so that exactly K steps are timed, "
+                         "and %d with --full" % REPLAYS)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: %d replays, the parity gate, the secondary measurements (extra), "
+                         "the CPU baseline and, with N>1, the gather / configs[3] / configs[4] tail" % REPLAYS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of what the last step wrote as DIR/<column>.npy (float32)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--c3-log2-blocks", type=int, default=None, help="N>1 extra: blocks per GPU of the configs[3] run (default 21)")
     ap.add_argument("--c4-log2-blocks", type=int, default=24, help="N=1 extra: blocks of the configs[4] streaming run")
     ap.add_argument("--c4-rank-log2-blocks", type=int, default=21,
@@ -69,11 +83,14 @@ def parse():
                     help="N>1: what the timed `gather` and `c3` phases use: torch.distributed point-to-point send/recv (RCCL through torch's "
                          "communicator: the default, a path that has run on hardware) or the C ABI's own RCCL gather (aesw_gather_columns_device: "
                          "never run with more than one real rank, DESIGN 7); the C ABI's gather is ALSO run as the last phase (`gather_cabi`)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-graph", action="store_true", help="launch every step from the host instead of a hipGraph")
     ap.add_argument("--option", action="append", default=[], help="name=value passed to aesw_set_option")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo to rehearse on one GPU)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.replays is None:
+        a.replays = REPLAYS if a.full else 1
+    return a
 
 
 class Runner:
@@ -334,6 +351,44 @@ def parity_gate(runner, blocks=4096, seed=SEED + 99):
                 edge - 1, n - edge, n - 1, int(idx.size) - 2 * edge)}
 
 
+DUMP_BLOCKS = 2048
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(runner, out_dir, blocks=DUMP_BLOCKS, seed=SEED + 77):
+    """--dump-outputs: what the LAST timed step wrote, as a caller of aesw_encrypt_witness_device receives it -- the x, y, z
+    advice columns and, with per-block keys, the key-schedule witness (w = words_column, kx, ky, kz) -- for a fixed sample of
+    `blocks` blocks (the first, the last and seeded random ones, ascending), one DIR/<column>.npy each: float32 of shape
+    (blocks, bytes of that column per block).  DIR/blocks.npy (float64) holds the sampled block indices.  Outside every timed
+    region.  Returns {file name: shape}."""
+    import numpy as np
+    torch, pkg, n = runner.torch, runner.pkg, runner.n
+    if n <= blocks:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        inner = 1 + np.random.default_rng(seed).choice(n - 2, blocks - 2, replace=False)
+        idx = np.sort(np.concatenate([[0, n - 1], inner])).astype(np.int64)
+    s = runner.sets[(runner.graph_steps - 1) % runner.nsets]  # launch(i) writes set i % nsets
+    cols = [(c, getattr(s, c), pkg.column_stride(runner.layout, i)) for i, c in enumerate("xyz")]
+    if runner.key_slab:
+        cols += [("w", s.key.w, pkg.WORDS_ROWS)] + [(c, getattr(s.key, c), pkg.key_column_stride(runner.layout, i)) for i, c in enumerate(("kx", "ky", "kz"))]
+    cols = [(c, t, st) for c, t, st in cols if st]  # a column the layout does not hold (values: x) is not written
+    total = idx.size * 8 + sum(idx.size * st * 4 for _, _, st in cols)
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_MAX_BYTES))
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    didx = torch.from_numpy(idx).to(s.x.device)
+    shapes = {}
+    for c, t, st in cols:
+        a = t.view(n, st).index_select(0, didx).cpu().numpy().astype(np.float32)
+        np.save(out / ("%s.npy" % c), a)
+        shapes["%s.npy" % c] = list(a.shape)
+    np.save(out / "blocks.npy", idx.astype(np.float64))
+    shapes["blocks.npy"] = [int(idx.size)]
+    return shapes
+
+
 def usable_cpus():
     """CPUs this process can really run on: the affinity mask, cut down by a cgroup CPU quota if there is one
     (a GPU box hands a 1-GPU job a share of its cores; os.cpu_count() still reports all of them)."""
@@ -549,7 +604,7 @@ def main():
         ctx.set_option(k, int(v))
     layout = {"packed": pkg.LAYOUT_PACKED, "dense": pkg.LAYOUT_DENSE, "values": pkg.LAYOUT_VALUES}[a.layout]
     host_bufs = None
-    if rank == 0 and dist is None and not a.no_extras:
+    if rank == 0 and dist is None and a.full and not a.no_extras:
         # Page-locked buffers of the PCIe-inclusive extras are taken first, as a host would at start-up.
         try:
             nn_host = 1 << 20
@@ -589,16 +644,22 @@ def main():
     achieved = bytes_launch / (ms_launch * 1e-3) / 1e9
     achieved_wall = bytes_launch * a.steps / wall / 1e9
 
-    # parity gate on what the timed replays wrote (outside the timed region; every rank checks its own shard)
-    try:
-        gate = parity_gate(runner)
-    except Exception as e:
-        gate = {"blocks": 0, "mismatches": -1, "error": str(e)}
-    if dist is not None:
-        gt = torch.tensor([float(gate["mismatches"] != 0), float(gate["blocks"])], dtype=torch.float64, device="cuda" if a.backend == "nccl" else "cpu")
-        dist.all_reduce(gt, op=dist.ReduceOp.SUM)
-        gate["ranks_with_mismatches"], gate["blocks_all_ranks"] = int(gt[0]), int(gt[1])
-    gate_failed = gate["mismatches"] != 0 or gate.get("ranks_with_mismatches", 0) != 0
+    dumped = None
+    if a.dump_outputs and rank == 0:  # rank 0's shard: what its last timed step wrote, before anything else runs on the GPU
+        dumped = dump_outputs(runner, a.dump_outputs)
+
+    # --full: parity gate on what the timed replays wrote (outside the timed region; every rank checks its own shard)
+    gate, gate_failed = None, False
+    if a.full:
+        try:
+            gate = parity_gate(runner)
+        except Exception as e:
+            gate = {"blocks": 0, "mismatches": -1, "error": str(e)}
+        if dist is not None:
+            gt = torch.tensor([float(gate["mismatches"] != 0), float(gate["blocks"])], dtype=torch.float64, device="cuda" if a.backend == "nccl" else "cpu")
+            dist.all_reduce(gt, op=dist.ReduceOp.SUM)
+            gate["ranks_with_mismatches"], gate["blocks_all_ranks"] = int(gt[0]), int(gt[1])
+        gate_failed = gate["mismatches"] != 0 or gate.get("ranks_with_mismatches", 0) != 0
 
     traffic = None
     tp = ROOT / "profiles" / "traffic.json"
@@ -622,7 +683,9 @@ def main():
                                         "linear fill timed on each; paid once per allocation, outside the timed region -- "
                                         "extra.headline_plain_tensors is the same graph into columns that were not probed" % runner.nsets)
                                        if use_arena else "torch.empty per column"},
+        "full": a.full,
         "parity_gate": gate,
+        "outputs_dumped": dumped,
         "timing": {"replays": len(replays), "reported": "median replay (exactly %d steps)" % a.steps,
                    "ms_per_step_wall": [w * 1e3 / a.steps for w, _ in replays],
                    "ms_per_step_events": [m for _, m in replays],
@@ -655,7 +718,7 @@ def main():
         sys.exit(5)
 
     extras = {}
-    if rank == 0 and dist is None and not a.no_extras:
+    if rank == 0 and dist is None and a.full and not a.no_extras:
         import numpy as np
         if use_arena:
             # the SAME K-step graph into columns nobody probed (one torch tensor per column), same process, same inputs: what a
@@ -933,7 +996,7 @@ def main():
         except Exception as e:
             extras["key_schedule"] = {"error": str(e)}
         line["extra"] = extras
-    if rank == 0 and dist is None and not a.no_cpu:
+    if rank == 0 and dist is None and a.full and not a.no_cpu:
         try:
             line["cpu_baseline"] = cpu_baseline(pbk)
         except Exception as e:  # the headline must reach the driver whatever happens to a reported baseline
@@ -962,8 +1025,8 @@ def main():
 
         # Order of the tail: configs[4] first (every rank for itself: barriers and two small all-reduces are its only collectives),
         # then the exchange steps whose RCCL leg has never run with real ranks -- if one of those stalls, the watchdog's
-        # line already carries c4.
-        if not a.no_extras:
+        # line already carries c4.  Every phase of the tail runs with --full only.
+        if a.full and not a.no_extras:
             # BASELINE configs[4] at N > 1: every rank streams its own shard to its own host over its own PCIe link (DESIGN 7:
             # the right delivery path -- no gather), kernel + async D2H overlapped with a cheap consumer; ranks timed between
             # barriers, MAX over ranks.  Consumer to match: region.assign_advice, src/aes128.rs:176-192.
@@ -1024,22 +1087,23 @@ def main():
                 failed.append("c4")
                 if rank == 0:
                     line["c4"] = {"error": str(e)}
-        try:
-            dog.arm("gather warm-up (RCCL communicator + peer channel set-up)", 120.0)
-            timed_gather(runner.sets[0], n)
-            dog.arm("gather", 60.0)
-            dt = timed_gather(runner.sets[0], n)
-            dog.disarm()
-            if rank == 0:
-                line["gather"] = {"seconds": dt, "GBps_into_root": (world - 1) * n * sum(strides) / dt / 1e9,
-                                  "path": pkg.sharding.last_gather_path,
-                                  "note": "per-rank column ranges gathered on rank 0, outside `value`"}
-        except Exception as e:
-            dog.disarm()
-            failed.append("gather")
-            if rank == 0:
-                line["gather"] = {"error": str(e)}
-        if not a.no_extras:
+        if a.full:
+            try:
+                dog.arm("gather warm-up (RCCL communicator + peer channel set-up)", 120.0)
+                timed_gather(runner.sets[0], n)
+                dog.arm("gather", 60.0)
+                dt = timed_gather(runner.sets[0], n)
+                dog.disarm()
+                if rank == 0:
+                    line["gather"] = {"seconds": dt, "GBps_into_root": (world - 1) * n * sum(strides) / dt / 1e9,
+                                      "path": pkg.sharding.last_gather_path,
+                                      "note": "per-rank column ranges gathered on rank 0, outside `value`"}
+            except Exception as e:
+                dog.disarm()
+                failed.append("gather")
+                if rank == 0:
+                    line["gather"] = {"error": str(e)}
+        if a.full and not a.no_extras:
             # BASELINE configs[3]: 2^24 blocks over 8 GPUs = 2^21 per GPU, columns gathered on GPU 0 (never `value`)
             try:
                 runner.close()
@@ -1070,7 +1134,7 @@ def main():
                 failed.append("c3")
                 if rank == 0:
                     line["c3"] = {"error": str(e)}
-        if not a.no_extras and a.backend == "nccl" and a.gather_path != "cabi":
+        if a.full and not a.no_extras and a.backend == "nccl" and a.gather_path != "cabi":
             # LAST, because it is the one step that has never run with real ranks: the C ABI's own RCCL gather (what a host without
             # torch calls) over 2^20-block columns.  Everything measured so far is already in the line: a stall
             # here ends the job through the watchdog with that line printed and gather_cabi = {error, fatal: false} (status 0: an

@@ -5,7 +5,11 @@
       /root/reference): the three byte tables of src/constant.rs:1-47, the row
       constants (:113-114), ROUND_CONSTANT (src/utils.rs:28), the EXPANDED
       zero-key round keys of src/key_schedule.rs:337-345 and the xor KAT of
-      src/utils.rs:40-47.  Only values are stored, no source text.
+      src/utils.rs:40-47.  Only values are stored, no source text: of the
+      three tables' declarations only their SHA-256 digests are kept.
+  patch_upstream.json       for rust/halo2-aes-patch/aesw-witness.patch (needs
+      the same upstream checkout): the SHA-256 digest of the upstream lines each hunk
+      replaces and pattern counts of the chip files it edits (tests/patch_hunks.py).
   slab_vectors.npz          inputs and expected witness slabs produced by the
       CPU oracle (oracle/aesw_oracle.c) for a handful of blocks: the reference's
       all-zero vector, FIPS-197 App. B and C.1, a block whose first S-box input
@@ -13,6 +17,7 @@
 
 Run from the repo root:  python tests/golden/make_golden.py
 """
+import hashlib
 import json
 import re
 import sys
@@ -49,6 +54,24 @@ def lift_reference_constants():
         "AES_ROWS": const("AES_ROWS"), "KEY_SCHEDULE_ROWS": const("KEY_SCHEDULE_ROWS"),
         "ROUND_CONSTANT": rc, "EXPANDED_ZERO_KEY": exp,
         "xor_kat": {"x": 5, "y": 12, "z": 9},
+        "TABLE_TEXT_SHA256": {name: hashlib.sha256(re.search(r"pub const %s: \[u8; 256\] = \[.*?\];" % name, src, re.S).group(0).encode())
+                              .hexdigest() for name in ("S_BOX", "MUL_BY_2", "MUL_BY_3")},
+    }
+
+
+def lift_patch_upstream():
+    """For tests/test_rust_shim.py: per hunk of rust/halo2-aes-patch/aesw-witness.patch, the SHA-256 digest of the upstream
+    lines it replaces (old_start .. old_start + old_lines - 1), and the chip files' pattern counts before the patch."""
+    import patch_hunks as ph
+    hunks = []
+    for path, a, b, _c, _d, _body in ph.parse((ROOT / "rust" / "halo2-aes-patch" / "aesw-witness.patch").read_text()):
+        lines = (REF / path).read_text().splitlines()
+        assert a + b - 1 <= len(lines), (path, a, b)
+        hunks.append({"file": path, "old_start": a, "old_lines": b, "sha256": ph.digest(lines[a - 1:a - 1 + b])})
+    return {
+        "source": "tkmct/halo2-aes @ 2024_08_07: the files the patch touches; digests of the lines each hunk replaces, no source text",
+        "hunks": hunks,
+        "chip_counts": {f: ph.counts((REF / f).read_text().splitlines()) for f in ph.CHIP_FILES},
     }
 
 
@@ -84,6 +107,8 @@ def main():
     if REF.exists():
         (HERE / "reference_constants.json").write_text(json.dumps(lift_reference_constants(), indent=0) + "\n")
         print("wrote reference_constants.json")
+        (HERE / "patch_upstream.json").write_text(json.dumps(lift_patch_upstream(), indent=1) + "\n")
+        print("wrote patch_upstream.json")
     else:
         print("no /root/reference here: reference_constants.json left as committed")
     np.savez_compressed(HERE / "slab_vectors.npz", **slab_vectors())

@@ -20,9 +20,54 @@ def test_defaults_and_constants(monkeypatch):
     a = b.parse()
     # the headline is BASELINE configs[2]: 2^20 blocks, per-block keys + key-schedule witness, packed columns
     assert a.gpus == 1 and a.steps > 0 and a.warmup >= 0 and a.workload == "c2" and a.layout == "packed"
-    assert a.replays >= 5 and a.log2_blocks is None
+    # a plain run times exactly --steps steps (one replay) and does nothing else; --full keeps the median of five replays
+    assert a.replays == 1 and not a.full and a.dump_outputs is None and a.log2_blocks is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    f = b.parse()
+    assert f.full and f.replays >= 5 and f.replays == b.REPLAYS
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--replays", "3", "--dump-outputs", "out"])
+    f = b.parse()
+    assert f.replays == 3 and f.dump_outputs == "out"
     assert b.BYTES_SHARED == 3024 + 16 and b.BYTES_PBK == 3024 + 936 + 32
     assert b.HBM_PEAK_GBPS == 8000.0
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_last_step(pkg, tmp_path):
+    """--dump-outputs: the set the LAST timed step wrote (launch i writes set i % nsets), every column a caller receives, the
+    same seeded blocks on every run (first and last included), float32 copies of the bytes, 64 MB at most for the headline
+    batch in every layout."""
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+    b = _bench()
+    n, lay = 5000, pkg.LAYOUT_PACKED
+    g = torch.Generator().manual_seed(3)
+
+    def col(st):
+        return torch.randint(0, 256, (n * st,), dtype=torch.uint8, generator=g)
+
+    strides = {c: pkg.column_stride(lay, i) for i, c in enumerate("xyz")}
+    strides.update({"w": pkg.WORDS_ROWS, **{c: pkg.key_column_stride(lay, i) for i, c in enumerate(("kx", "ky", "kz"))}})
+    sets = [SimpleNamespace(**{c: col(strides[c]) for c in "xyz"}, key=SimpleNamespace(**{c: col(strides[c]) for c in ("w", "kx", "ky", "kz")}))
+            for _ in range(3)]
+    runner = SimpleNamespace(torch=torch, pkg=pkg, n=n, layout=lay, key_slab=True, sets=sets, nsets=3, graph_steps=5)
+    shapes = b.dump_outputs(runner, tmp_path / "a", blocks=256)
+    assert sorted(shapes) == ["blocks.npy", "kx.npy", "ky.npy", "kz.npy", "w.npy", "x.npy", "y.npy", "z.npy"]
+    idx = np.load(tmp_path / "a" / "blocks.npy")
+    assert idx.dtype == np.float64 and idx.size == 256 and idx[0] == 0 and idx[-1] == n - 1 and np.all(np.diff(idx) > 0)
+    last = sets[(5 - 1) % 3]
+    for c, st in strides.items():
+        got = np.load(tmp_path / "a" / ("%s.npy" % c))
+        src = getattr(last, c) if c in "xyz" else getattr(last.key, c)
+        assert got.dtype == np.float32 and got.shape == (256, st) and shapes["%s.npy" % c] == [256, st]
+        assert np.array_equal(got, src.view(n, st).numpy()[idx.astype(np.int64)].astype(np.float32)), c
+    b.dump_outputs(runner, tmp_path / "b", blocks=256)
+    for f in shapes:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    for layout in (pkg.LAYOUT_PACKED, pkg.LAYOUT_DENSE, pkg.LAYOUT_VALUES):  # the headline's 2^20-block batch with its key slab
+        per_block = sum(pkg.column_stride(layout, i) for i in range(3)) + pkg.WORDS_ROWS + sum(pkg.key_column_stride(layout, i) for i in range(3))
+        assert b.DUMP_BLOCKS * (per_block * 4 + 8) <= b.DUMP_MAX_BYTES == 64 << 20
 
 
 def test_cpu_baseline_leg(pkg):

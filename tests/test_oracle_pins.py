@@ -3,8 +3,8 @@ path: constant.rs tables, the xor KAT, the EXPANDED zero-key
 round keys, AES_ROWS / KEY_SCHEDULE_ROWS, MockProver-style satisfaction of the
 reference's two integration tests, the capacity panic, and FIPS-197 KATs that
 are valid for the reference's (non-FIPS) S-box."""
+import hashlib
 import json
-import re
 from pathlib import Path
 
 import numpy as np
@@ -14,7 +14,6 @@ import oracle_lib as ol
 import slab_map
 
 GOLD = Path(__file__).resolve().parent / "golden"
-REF = Path("/root/reference")
 
 
 @pytest.fixture(scope="module")
@@ -34,12 +33,29 @@ def test_tables_match_reference_constants(oracle, consts):
     assert sorted(sbox.tolist()) != list(range(256))
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree only exists in the build container")
+def _rustfmt_table(name, vals, width=99):
+    """The declaration of a [u8; 256] table as src/constant.rs writes it: rustfmt fills each line to 99 columns."""
+    lines, cur = [], "   "
+    for v in vals:
+        tok = " %d," % v
+        if len(cur) + len(tok) > width:
+            lines.append(cur)
+            cur = "    %d," % v
+        else:
+            cur += tok
+    lines.append(cur)
+    return "pub const %s: [u8; 256] = [\n%s\n];" % (name, "\n".join(lines))
+
+
 def test_fixture_still_matches_reference_text(consts):
-    src = (REF / "src" / "constant.rs").read_text()
+    """The fixture's tables, laid out as src/constant.rs lays them out, hash to the SHA-256 digests that
+    tests/golden/make_golden.py took of the reference's own declarations: one changed entry anywhere changes a digest."""
     for name in ("S_BOX", "MUL_BY_2", "MUL_BY_3"):
-        m = re.search(r"pub const %s: \[u8; 256\] = \[(.*?)\];" % name, src, re.S)
-        assert [int(v) for v in m.group(1).replace("\n", " ").split(",") if v.strip()] == consts[name]
+        text = _rustfmt_table(name, consts[name])
+        assert hashlib.sha256(text.encode()).hexdigest() == consts["TABLE_TEXT_SHA256"][name], name
+        bad = list(consts[name])
+        bad[255] ^= 1
+        assert hashlib.sha256(_rustfmt_table(name, bad).encode()).hexdigest() != consts["TABLE_TEXT_SHA256"][name]
 
 
 def test_product_host_constants_match_reference(pkg, consts):

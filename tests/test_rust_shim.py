@@ -5,25 +5,27 @@ one thing that is silent undefined behaviour when it drifts: that every prototyp
 constant of rust/aesw-sys/src/lib.rs says exactly what include/aesw.h says.  Both files are parsed into the same
 canonical form (name, [(parameter, type)], return type) and compared item by item; the test then MUTATES the header text
 in memory (one more argument, a dropped const, a widened integer, swapped struct fields, a changed constant) and requires
-the comparison to notice.  Further: the unified diff of rust/halo2-aes-patch applies cleanly to the reference's files
-(only where /root/reference exists: never on the GPU box) and the cursor arithmetic of src/aesw.rs -- one row per chip
+the comparison to notice.  Further: the unified diff of rust/halo2-aes-patch is well formed and applies to the upstream
+files with no fuzz and no offset (checked against digests of the upstream lines in tests/golden/patch_upstream.json) and
+the patched chips read every value from the buffer, and the cursor arithmetic of src/aesw.rs -- one row per chip
 call, sixteen for the plaintext region -- replayed in Python lands on the oracle's region order (400 key rows, 1 360 rows
 per block) with every value-closure row reading a cell the PACKED layout really holds.
 """
+import json
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import patch_hunks
+
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / "include" / "aesw.h"
 RUST = ROOT / "rust" / "aesw-sys" / "src" / "lib.rs"
 PATCH = ROOT / "rust" / "halo2-aes-patch" / "aesw-witness.patch"
 AESW_RS = ROOT / "rust" / "halo2-aes-patch" / "src" / "aesw.rs"
-REFERENCE = Path("/root/reference")
 
 # ---------------------------------------------------------------------------------------------------------------------
 # canonical types: ("int", bits, signed) | ("ptr", const, pointee) | ("void",) | ("struct", name) | ("fn", name) | ...
@@ -343,21 +345,50 @@ def test_patch_touches_only_the_value_sources():
     assert len(text.splitlines()) < 300
 
 
-@pytest.mark.skipif(not REFERENCE.exists() or shutil.which("patch") is None, reason="needs /root/reference and patch(1): this container only")
-def test_patch_applies_to_the_reference(tmp_path):
-    for f in PATCHED_FILES:
-        (tmp_path / f).parent.mkdir(parents=True, exist_ok=True)
-        shutil.copy(REFERENCE / f, tmp_path / f)
-    r = subprocess.run(["patch", "-p1", "--fuzz=0", "-d", str(tmp_path), "-i", str(PATCH)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "fuzz" not in r.stdout and "offset" not in r.stdout, r.stdout
-    xor = (tmp_path / "src/chips/u8_xor_chip.rs").read_text()
-    assert "xor_bytes" not in xor and "aesw::z_at(at)" in xor and xor.count("copy_advice(") == 2
-    # every closure the patched files still hand to assign_advice for a VALUE is a buffer read
-    for f in ("src/chips/u8_xor_chip.rs", "src/chips/sbox_chip.rs", "src/chips/gf_mul_chip.rs"):
-        body = (tmp_path / f).read_text()
-        assert len(re.findall(r"\|\| (?:crate::)?aesw::[xyz]_at\(at\)", body)) == 1, f
-        assert len(re.findall(r"let at = (?:crate::)?aesw::advance\(1\);", body)) == 1, f
+def test_patch_hunks_are_well_formed():
+    """Every hunk's @@ header agrees with its body (context and removed lines on the old side, context and added lines on the
+    new side), hunks of a file run in order without overlap, and each one's new start is its old start moved by exactly the
+    lines the earlier hunks of that file added: patch(1) reads it as written, with no offset to guess."""
+    hunks = patch_hunks.parse(PATCH.read_text())
+    files = []
+    for path, a, b, c, d, body in hunks:
+        assert (len(patch_hunks.old_side(body)), len(patch_hunks.new_side(body))) == (b, d), (path, a)
+        if not files or files[-1][0] != path:
+            files.append((path, []))
+        files[-1][1].append((a, b, c, d))
+    assert [f for f, _ in files] == PATCHED_FILES
+    for f, fh in files:
+        shift, end = 0, 0
+        for a, b, c, d in fh:
+            assert a > end and c == a + shift, (f, a, c, shift)
+            shift, end = shift + d - b, a + b - 1
+
+
+def test_patch_applies_to_the_reference():
+    """The patch against the upstream files without the files (tests/golden/patch_upstream.json, written by make_golden.py
+    from the upstream checkout): the old side of every hunk -- its context and '-' lines -- hashes to the digest of the
+    upstream lines it claims to replace, so `patch -p1 --fuzz=0` applies every hunk where its header says; and the chip files'
+    upstream pattern counts, moved by the '-' and '+' lines, show the patched chips: no xor_bytes left, every value closure
+    a buffer read behind exactly one advance(1), copy_advice() untouched."""
+    gold = json.loads((ROOT / "tests" / "golden" / "patch_upstream.json").read_text())
+    hunks = patch_hunks.parse(PATCH.read_text())
+    assert [(h[0], h[1], h[2]) for h in hunks] == [(g["file"], g["old_start"], g["old_lines"]) for g in gold["hunks"]]
+    for (path, a, b, _c, _d, body), g in zip(hunks, gold["hunks"]):
+        assert patch_hunks.digest(patch_hunks.old_side(body)) == g["sha256"], "%s: hunk at line %d does not match upstream" % (path, a)
+    patched = {}
+    for f in patch_hunks.CHIP_FILES:
+        n = dict(gold["chip_counts"][f])
+        for path, _a, _b, _c, _d, body in hunks:
+            if path == f:
+                gone = patch_hunks.counts([l[1:] for l in body if l.startswith("-")])
+                came = patch_hunks.counts([l[1:] for l in body if l.startswith("+")])
+                n = {k: n[k] - gone[k] + came[k] for k in n}
+        patched[f] = n
+    xor = patched["src/chips/u8_xor_chip.rs"]
+    assert xor["xor_bytes"] == 0 and xor["z_at"] >= 1 and xor["copy_advice"] == 2, xor
+    for f in patch_hunks.CHIP_FILES:
+        assert patched[f]["value_closure"] == 1 and patched[f]["advance_1"] == 1, (f, patched[f])
+        assert patched[f]["copy_advice"] == gold["chip_counts"][f]["copy_advice"], f
 
 
 def test_cursor_walk_of_aesw_rs_matches_the_oracle_region_order():
