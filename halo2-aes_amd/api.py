@@ -83,6 +83,10 @@ SYMBOLS = {
     "aesw_create": (_I, [C.POINTER(_P), _I, _P, _P, _P]),
     "aesw_destroy": (None, [_P]),
     "aesw_device": (_I, [_P]),
+    "aesw_create_group": (_I, [C.POINTER(_P), _P, _U32, _P, _P, _P]),
+    "aesw_group_size": (_I, [_P]),
+    "aesw_group_member": (_P, [_P, _U32]),
+    "aesw_group_shard": (_I, [_U32, _U64, _U32, C.POINTER(_U64), C.POINTER(_U64)]),
     "aesw_column_stride": (_U32, [_I, _I]),
     "aesw_key_column_stride": (_U32, [_I, _I]),
     "aesw_packed_index": (_I, [_I, _P]),
@@ -820,11 +824,87 @@ class Context:
         self._check(rc, "aesw_key_schedule_witness")
         return KeyWitness(w, kx, ky, kz, rk)
 
+    def schedule_key_host(self, key, layout: int = K.LAYOUT_PACKED, key_slab: bool = True):
+        """aesw_schedule_key: FixedAes128Config::schedule_key from 16 host bytes; later encrypt_witness_host(pt, None) calls use
+        the key.  Returns its key slab (numpy KeyWitness, rk None) when key_slab."""
+        key = np.ascontiguousarray(key, dtype=np.uint8).reshape(-1)
+        if key.size != 16:
+            raise ValueError("key must be 16 bytes")
+        kw = ks = None
+        if key_slab:
+            kw = KeyWitness(np.empty(K.WORDS_ROWS, np.uint8), *[np.empty(key_column_stride(layout, c), np.uint8) for c in range(3)], None)
+            ks = KeySlab(*[a.ctypes.data for a in kw[:4]])
+        rc = self._lib.aesw_schedule_key(self._h, _np_ptr(key), layout, C.byref(ks) if ks is not None else None)
+        self._check(rc, "aesw_schedule_key")
+        return kw
+
     def lookup_table_host(self) -> np.ndarray:
         t = np.empty((4, K.TABLE_ROWS), dtype=np.uint8)
         rc = self._lib.aesw_lookup_table(self._h, *[_np_ptr(t[i]) for i in range(4)])
         self._check(rc, "aesw_lookup_table")
         return t
+
+
+def group_shard(members: int, n: int, i: int):
+    """aesw_group_shard: (first, count) of member i's blocks in a batch of n (the ranges of sharding.shard_range)."""
+    first, count = C.c_uint64(), C.c_uint64()
+    rc = load_library().aesw_group_shard(members, n, i, C.byref(first), C.byref(count))
+    if rc:
+        raise AeswError(rc, "aesw_group_shard(%d, %d, %d)" % (members, n, i))
+    return int(first.value), int(count.value)
+
+
+def _group_refuses(name):
+    def refuse(self, *args, **kwargs):
+        raise AeswError(ERR_INVALID_ARG, "Group.%s: device pointers belong to one GPU; use a member (Group.member_handle(i) is its aesw_ctx*)" % name)
+    refuse.__name__ = name
+    return refuse
+
+
+class Group(Context):
+    """A group context (aesw_create_group): one member context per listed device, driven from this one process.  The host-pointer
+    methods of Context split a batch into contiguous block shards, one member (and host thread) each, every GPU copying its shard
+    over its own link into the caller's arrays.  Methods that take device tensors raise: device memory belongs to one GPU."""
+
+    def __init__(self, devices=None, tables=None):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        sbox, mul2, mul3 = tables if tables is not None else K.reference_tables()
+        self._tables = tuple(np.ascontiguousarray(t, dtype=np.uint8) for t in (sbox, mul2, mul3))
+        for t in self._tables:
+            if t.shape != (256,):
+                raise ValueError("tables must be three uint8[256] arrays")
+        devs = None if devices is None else np.ascontiguousarray(list(devices), dtype=np.intc)
+        rc = self._lib.aesw_create_group(C.byref(self._h), _np_ptr(devs) if devs is not None else None,
+                                         0 if devs is None else devs.size, *[_np_ptr(t) for t in self._tables])
+        if rc:
+            self._h = C.c_void_p()
+            raise AeswError(rc, "aesw_create_group(devices=%r)" % (devices,))
+        self.device = int(self._lib.aesw_device(self._h))
+        self._arenas = {}
+
+    @property
+    def size(self) -> int:
+        return int(self._lib.aesw_group_size(self._h))
+
+    def shard(self, n: int, i: int):
+        """(first, count) of member i's blocks in a batch of n."""
+        return group_shard(self.size, n, i)
+
+    def member_handle(self, i: int) -> int:
+        """aesw_group_member: the borrowed aesw_ctx* of member i (an int; valid while the group lives)."""
+        h = self._lib.aesw_group_member(self._h, i)
+        if not h:
+            raise IndexError("member %d of a group of %d" % (i, self.size))
+        return int(h)
+
+
+# the device-tensor methods of Context (the C ABI refuses them on a group as well)
+for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
+              "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
+              "assemble_advice_host"):
+    setattr(Group, _name, _group_refuses(_name))
+del _name
 
 
 class Comm:

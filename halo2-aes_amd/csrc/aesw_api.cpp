@@ -276,6 +276,7 @@ int aesw_create(aesw_ctx **out, int device, const uint8_t sbox[256], const uint8
 
 void aesw_destroy(aesw_ctx *ctx) {
     if (!ctx) return;
+    if (aesw_is_group(ctx)) return aesw_group_destroy(ctx);
     {
         DeviceGuard g(ctx->device);
         if (ctx->s_compute) (void)hipStreamDestroy(ctx->s_compute);
@@ -308,7 +309,10 @@ void aesw_destroy(aesw_ctx *ctx) {
 }
 
 int aesw_device(const aesw_ctx *ctx) { return ctx ? ctx->device : -1; }
-int aesw_uses_xtime_path(const aesw_ctx *ctx) { return ctx && ctx->xt ? 1 : 0; }
+int aesw_uses_xtime_path(const aesw_ctx *ctx) {
+    if (aesw_is_group(ctx)) return aesw_uses_xtime_path(ctx->members[0]);
+    return ctx && ctx->xt ? 1 : 0;
+}
 
 // ---- geometry ------------------------------------------------------------------
 
@@ -445,6 +449,7 @@ int aesw_assemble_selectors(uint32_t k, uint32_t n_sets, uint64_t n_blocks, uint
 // ---- options --------------------------------------------------------------------
 
 int aesw_set_option(aesw_ctx *ctx, const char *name, int64_t value) {
+    if (aesw_is_group(ctx)) return aesw_group_set_option(ctx, name, value);
     if (!ctx || !name) return AESW_ERR_INVALID_ARG;
     if (!std::strcmp(name, "waves_shared")) { if (value < 0 || value > 4) return AESW_ERR_INVALID_ARG; ctx->waves_shared = (int)value; return AESW_OK; }
     if (!std::strcmp(name, "waves_pbk")) { if (value < 0 || value > 4) return AESW_ERR_INVALID_ARG; ctx->waves_pbk = (int)value; return AESW_OK; }
@@ -507,7 +512,8 @@ static int auto_copy_threads(const aesw_ctx *ctx) {
     cpu_set_t set;
     int usable = 1;
     if (sched_getaffinity(0, sizeof set, &set) == 0) usable = CPU_COUNT(&set);
-    const int t = usable / 4;  // leave the host its cores: a quarter of what this process may run on, 1 ... 4
+    // leave the host its cores: a quarter of what this process may run on, 1 ... 4, shared among the members of a group
+    const int t = usable / (4 * ctx->group_size);
     return t < 1 ? 1 : (t > 4 ? 4 : t);
 }
 static void parallel_copy(const std::vector<CopyJob> &jobs, int threads) noexcept {
@@ -537,6 +543,7 @@ static void parallel_copy(const std::vector<CopyJob> &jobs, int threads) noexcep
 static int auto_waves_key(const aesw_ctx *ctx, int layout, bool want_rk);
 
 int aesw_get_option(const aesw_ctx *ctx, const char *name, int64_t *value) {
+    if (aesw_is_group(ctx)) return aesw_get_option(ctx->members[0], name, value);  // a group: member 0
     if (!ctx || !name || !value) return AESW_ERR_INVALID_ARG;
     if (!std::strcmp(name, "waves_shared")) { *value = ctx->waves_shared; return AESW_OK; }
     if (!std::strcmp(name, "waves_pbk")) { *value = ctx->waves_pbk; return AESW_OK; }
@@ -612,6 +619,7 @@ static int auto_waves_key(const aesw_ctx *ctx, int layout, bool want_rk) {
 }
 
 int aesw_schedule_key_device(aesw_ctx *ctx, const uint8_t *d_key, int layout, const aesw_key_slab *ks, void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_schedule_key_device");
     if (!ctx || !valid_layout(layout) || !d_key || !aligned4(d_key)) return AESW_ERR_INVALID_ARG;
     KeyOut ko{nullptr, nullptr, nullptr, nullptr};
     if (ks) {
@@ -663,6 +671,7 @@ int aesw_schedule_key_device(aesw_ctx *ctx, const uint8_t *d_key, int layout, co
 int aesw_encrypt_witness_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys,
                                 uint64_t n, int layout, uint8_t *d_x, uint8_t *d_y, uint8_t *d_z, uint8_t *d_ct,
                                 const aesw_key_slab *ks, void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_encrypt_witness_device");
     if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
     if (!d_keys) {
         if (per_block_keys) return AESW_ERR_INVALID_ARG;
@@ -757,6 +766,7 @@ int aesw_encrypt_witness_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_
 
 int aesw_encrypt_witness_batches_device(aesw_ctx *ctx, const aesw_batch *batches, uint32_t count, int per_block_keys, int layout,
                                         void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_encrypt_witness_batches_device");
     if (!ctx || !valid_layout(layout) || (count && !batches)) return AESW_ERR_INVALID_ARG;
     if (count == 0) return AESW_OK;
     DeviceGuard g(ctx->device);
@@ -799,6 +809,7 @@ int aesw_encrypt_witness_batches_device(aesw_ctx *ctx, const aesw_batch *batches
 
 int aesw_key_schedule_witness_device(aesw_ctx *ctx, const uint8_t *d_keys, uint64_t n, int layout, uint8_t *d_w,
                                      uint8_t *d_kx, uint8_t *d_ky, uint8_t *d_kz, uint8_t *d_rk, void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_key_schedule_witness_device");
     if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
     if (n == 0) return AESW_OK;
     if (!d_keys || !aligned4(d_keys)) return AESW_ERR_INVALID_ARG;
@@ -813,6 +824,7 @@ int aesw_key_schedule_witness_device(aesw_ctx *ctx, const uint8_t *d_keys, uint6
 }
 
 int aesw_lookup_table_device(aesw_ctx *ctx, uint8_t *d_t0, uint8_t *d_t1, uint8_t *d_t2, uint8_t *d_t3, void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_lookup_table_device");
     if (!ctx || !d_t0 || !d_t1 || !d_t2 || !d_t3) return AESW_ERR_INVALID_ARG;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
@@ -853,6 +865,7 @@ uint64_t now_ns() {
 int aesw_assemble_advice_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
                                 const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, int as_fr, uint8_t *d_out,
                                 void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_assemble_advice_device");
     if (!d_out || !aligned16(d_out)) return AESW_ERR_INVALID_ARG;
     AssembleParams p;
     const int rc = fill_assemble_params(ctx, k, n_sets, n_blocks, layout, d_x, d_y, d_z, ks, &p);
@@ -871,6 +884,7 @@ static int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t 
 int aesw_check_witness_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys, uint64_t n, int layout,
                               const uint8_t *d_x, const uint8_t *d_y, const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *ks,
                               aesw_check_report *d_report, void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_check_witness_device");
     return check_witness_impl(ctx, d_pt, d_keys, per_block_keys, n, layout, d_x, d_y, d_z, d_ct, ks, d_report, stream, false);
 }
 
@@ -904,6 +918,7 @@ static int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t 
 }
 
 int aesw_expand_fr_device(aesw_ctx *ctx, const uint8_t *d_cells, uint64_t n_cells, uint8_t *d_fr, void *stream) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_expand_fr_device");
     if (!ctx) return AESW_ERR_INVALID_ARG;
     if (n_cells == 0) return AESW_OK;
     if (!d_cells || !d_fr || !aligned16(d_fr)) return AESW_ERR_INVALID_ARG;
@@ -975,6 +990,7 @@ struct HostCol {
 
 int aesw_encrypt_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n,
                          int layout, uint8_t *x, uint8_t *y, uint8_t *z, uint8_t *ct, const aesw_key_slab *ks) {
+    if (aesw_is_group(ctx)) return aesw_group_encrypt_witness(ctx, pt, keys, per_block_keys, n, layout, x, y, z, ct, ks);
     if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
     if (n == 0) return AESW_OK;
     if (!pt) return AESW_ERR_INVALID_ARG;  // x / y / z: a null column is computed but not copied back
@@ -1116,6 +1132,7 @@ int aesw_encrypt_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, 
 
 int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n, int layout,
                                 aesw_chunk_fn consume, void *user) {
+    if (aesw_is_group(ctx)) return aesw_group_encrypt_witness_stream(ctx, pt, keys, per_block_keys, n, layout, consume, user);
     if (!ctx || !valid_layout(layout) || !consume) return AESW_ERR_INVALID_ARG;
     if (n == 0) return AESW_OK;
     if (!pt || (!keys && per_block_keys)) return AESW_ERR_INVALID_ARG;
@@ -1300,6 +1317,7 @@ int aesw_last_stream_stats(const aesw_ctx *ctx, aesw_stream_stats *out) {
 int aesw_assemble_advice_stream(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
                                 const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, int as_fr, aesw_column_fn consume,
                                 void *user) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_assemble_advice_stream");
     if (!consume) return AESW_ERR_INVALID_ARG;
     AssembleParams p;
     int rc = fill_assemble_params(ctx, k, n_sets, n_blocks, layout, d_x, d_y, d_z, ks, &p);
@@ -1380,6 +1398,7 @@ int aesw_assemble_advice_stream(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint
 // otherwise.  Column j+1 is assembled while column j travels.
 int aesw_assemble_advice_host(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
                               const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, int as_fr, uint8_t *out) {
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_assemble_advice_host");
     if (!out) return AESW_ERR_INVALID_ARG;
     AssembleParams p;
     int rc = fill_assemble_params(ctx, k, n_sets, n_blocks, layout, d_x, d_y, d_z, ks, &p);
@@ -1465,6 +1484,7 @@ int aesw_host_unregister(void *p) {
 
 int aesw_key_schedule_witness(aesw_ctx *ctx, const uint8_t *keys, uint64_t n, int layout, uint8_t *w, uint8_t *kx,
                               uint8_t *ky, uint8_t *kz, uint8_t *rk) {
+    if (aesw_is_group(ctx)) return aesw_group_key_schedule_witness(ctx, keys, n, layout, w, kx, ky, kz, rk);
     if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
     if (n == 0) return AESW_OK;
     if (!keys) return AESW_ERR_INVALID_ARG;
@@ -1494,6 +1514,7 @@ int aesw_key_schedule_witness(aesw_ctx *ctx, const uint8_t *keys, uint64_t n, in
 
 int aesw_check_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n, int layout, const uint8_t *x,
                        const uint8_t *y, const uint8_t *z, const uint8_t *ct, const aesw_key_slab *ks, aesw_check_report *report) {
+    if (aesw_is_group(ctx)) return aesw_group_check_witness(ctx, pt, keys, per_block_keys, n, layout, x, y, z, ct, ks, report);
     if (!ctx || !report || (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED)) return AESW_ERR_INVALID_ARG;
     if (per_block_keys && n && !keys) return AESW_ERR_INVALID_ARG;
     if (n && (!pt || !x || !y || !z || !ks || !ks->w || !ks->kx || !ks->ky || !ks->kz)) return AESW_ERR_INVALID_ARG;
@@ -1553,6 +1574,7 @@ int aesw_check_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, in
 }
 
 int aesw_schedule_key(aesw_ctx *ctx, const uint8_t key[16], int layout, const aesw_key_slab *ks) {
+    if (aesw_is_group(ctx)) return aesw_group_schedule_key(ctx, key, layout, ks);
     if (!ctx || !valid_layout(layout) || !key) return AESW_ERR_INVALID_ARG;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
@@ -1589,6 +1611,7 @@ void aesw_host_free(void *p) {
 }
 
 int aesw_lookup_table(aesw_ctx *ctx, uint8_t *t0, uint8_t *t1, uint8_t *t2, uint8_t *t3) {
+    if (aesw_is_group(ctx)) return aesw_group_lookup_table(ctx, t0, t1, t2, t3);
     if (!ctx || !t0 || !t1 || !t2 || !t3) return AESW_ERR_INVALID_ARG;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;

@@ -86,6 +86,7 @@ void cache_trim(aesw_ctx *ctx, uint64_t keep) {
 int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab, int with_ct, aesw_columns *out) {
     if (!ctx || !out || !valid_layout(layout) || n == 0 || n > ((uint64_t)1 << 40)) return AESW_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof *out);
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_columns_alloc");
     // with_key_slab 2: the key-schedule witness alone (aesw_key_schedule_witness_device): no encrypt columns
     const bool key_only = with_key_slab == 2;
     const uint64_t sx = key_only ? 0 : aesw_column_stride(layout, 0), sy = key_only ? 0 : aesw_column_stride(layout, 1),
@@ -333,6 +334,7 @@ extern "C" {
 
 int aesw_columns_free(aesw_ctx *ctx, aesw_columns *cols) {
     if (!ctx || !cols) return AESW_ERR_INVALID_ARG;
+    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_columns_free");
     if (cols->base) {
         DeviceGuard g(ctx->device);
         if (!g.ok) return AESW_ERR_NO_DEVICE;

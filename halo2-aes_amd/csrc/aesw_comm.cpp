@@ -100,6 +100,10 @@ int aesw_comm_unique_id(uint8_t id[AESW_COMM_ID_BYTES]) {
 int aesw_comm_create(aesw_ctx *ctx, int nranks, int rank, const uint8_t id[AESW_COMM_ID_BYTES], aesw_comm **out) {
     if (!ctx || !out || nranks < 1 || rank < 0 || rank >= nranks || (nranks > 1 && !id)) return AESW_ERR_INVALID_ARG;
     *out = nullptr;
+    if (aesw_group_size(ctx) > 0) {  // a group context drives several GPUs: a rank is one of them (aesw_group_member)
+        g_comm_error = "aesw_comm_create: a group context cannot be a rank; create the communicator on a member";
+        return AESW_ERR_INVALID_ARG;
+    }
     aesw_comm *c = new (std::nothrow) aesw_comm;
     if (!c) return AESW_ERR_NOMEM;
     c->device = aesw_device(ctx);

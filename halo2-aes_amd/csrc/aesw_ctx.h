@@ -104,7 +104,28 @@ struct aesw_ctx {
     int stream_check = 0;          // option: aesw_encrypt_witness_stream checks every chunk on the device before it travels (aesw_check.h)
     int64_t stream_poison = 0;     // diagnostic (tests): block index + 1 whose y / z cells the stream overwrites before its chunk is checked and shipped
     aesw_check_report stream_report = {0, 0, 0, 0, 0, 0, ~0ull};  // of the last streaming call with "stream_check" on
+    // Group context (aesw_create_group, aesw_group.cpp): one member context per listed device, nothing on a device of its own; the
+    // host-pointer entry points split a batch into block shards over the members.  Empty for a plain context.
+    std::vector<aesw_ctx *> members;
+    int group_size = 1;  // of a MEMBER: the members of its group (its automatic "copy_threads" is its share of the CPUs)
 };
+
+// aesw_group.cpp: what the entry points of aesw_api.cpp hand a group context to (a short branch at their top)
+inline bool aesw_is_group(const aesw_ctx *ctx) { return ctx && !ctx->members.empty(); }
+int aesw_group_refuse(aesw_ctx *group, const char *entry);  // AESW_ERR_INVALID_ARG: device pointers belong to one GPU
+void aesw_group_destroy(aesw_ctx *group);
+int aesw_group_set_option(aesw_ctx *group, const char *name, int64_t value);
+int aesw_group_encrypt_witness(aesw_ctx *group, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n, int layout,
+                               uint8_t *x, uint8_t *y, uint8_t *z, uint8_t *ct, const aesw_key_slab *ks);
+int aesw_group_encrypt_witness_stream(aesw_ctx *group, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n, int layout,
+                                      aesw_chunk_fn consume, void *user);
+int aesw_group_key_schedule_witness(aesw_ctx *group, const uint8_t *keys, uint64_t n, int layout, uint8_t *w, uint8_t *kx, uint8_t *ky,
+                                    uint8_t *kz, uint8_t *rk);
+int aesw_group_check_witness(aesw_ctx *group, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n, int layout,
+                             const uint8_t *x, const uint8_t *y, const uint8_t *z, const uint8_t *ct, const aesw_key_slab *ks,
+                             aesw_check_report *report);
+int aesw_group_schedule_key(aesw_ctx *group, const uint8_t key[16], int layout, const aesw_key_slab *ks);
+int aesw_group_lookup_table(aesw_ctx *group, uint8_t *t0, uint8_t *t1, uint8_t *t2, uint8_t *t3);
 
 inline int fail_hip(aesw_ctx *ctx, hipError_t e, const char *what) {
     if (ctx) {

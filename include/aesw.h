@@ -421,6 +421,52 @@ int aesw_check_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, in
 int aesw_schedule_key(aesw_ctx *ctx, const uint8_t key[16], int layout, const aesw_key_slab *key_slab);
 int aesw_lookup_table(aesw_ctx *ctx, uint8_t *t0, uint8_t *t1, uint8_t *t2, uint8_t *t3);
 
+/* ---- device groups: one process, several GPUs, each over its own link ------- */
+/* A group is an aesw_ctx that owns one member context per listed device.  The host-pointer entry points above, called on a
+ * group, split the batch into contiguous block shards -- member i takes blocks [n*i/G, n*(i+1)/G) of G members, the ranges of
+ * aesw_group_shard -- and every member runs its shard on a host thread of its own (the calling thread serves member 0), so each
+ * GPU moves its shard over its own link straight into the caller's buffers at the shard's offsets.  A caller of
+ * aesw_encrypt_witness gets several GPUs by changing the create call alone.  Per entry point:
+ *   aesw_encrypt_witness         reads pt / keys and writes x, y, z, ct and per-block key slabs at each shard's offsets; with one
+ *                                shared 16-byte key its one key slab is written by the first member with blocks (member 0 when
+ *                                n >= G); members with an empty shard (n < G) do nothing.  Returns when every member has joined:
+ *                                no copy is still touching the caller's buffers.
+ *   aesw_encrypt_witness_stream  `consume` still runs on the CALLING thread and never concurrently; first_block is batch-wide;
+ *                                within a member chunks arrive in block order, across members in arrival order.  A member hands
+ *                                each chunk over and waits until `consume` has returned (the pointers are valid only during the
+ *                                call).  A non-zero return stops every member at its next chunk boundary; AESW_ERR_MISMATCH is
+ *                                returned once all have joined.
+ *   aesw_schedule_key            on every member; member 0 writes the optional key slab.
+ *   aesw_key_schedule_witness    split by key; aesw_check_witness: split by block, a shared key's slab goes to every member
+ *                                (and is counted in report->keys once per member with blocks); `first` in batch-wide units.
+ *   aesw_last_stream_check       summed over the members, `first` in batch-wide units; aesw_last_stream_stats: counters summed
+ *                                over the members, wall_ns the group call's own wall time.
+ *   aesw_set_option              applied to every member; aesw_get_option, aesw_lookup_table, aesw_uses_xtime_path: member 0.
+ *   aesw_device                  member 0's device.
+ *   everything else              every *_device entry point, aesw_columns_alloc / _free, the aesw_assemble_advice_* entry points
+ *                                and aesw_comm_create return AESW_ERR_INVALID_ARG: device pointers belong to one GPU.  Use a
+ *                                member (aesw_group_member) for them.
+ * The status of a group call is the first non-OK one in member order; aesw_last_error(group) names that member and its device.
+ * Host threads: a member's automatic "copy_threads" is its share of the CPUs, a quarter of them divided among the G members
+ * (1 ... 4 each), so a group of one behaves exactly as a plain context; an explicit "copy_threads" applies per member.
+ * Destinations: the multi-GPU path is fast only into PAGE-LOCKED memory (aesw_host_alloc, aesw_host_register: both portable, so
+ * every member's DMA lands in them directly).  Pageable destinations go through each member's bounce buffers and a CPU copy of
+ * about 20 GB/s per copy thread: the CPUs, not the links, bound them.  Groups are not measured beyond one GPU (README).
+ *
+ * aesw_create_group: member i on devices[i], count members (1 ... 64; a device may repeat, and its members then share that GPU);
+ * devices == NULL: one member per device aesw_device_count() reports (count is ignored).  Tables as for aesw_create.
+ * AESW_ERR_INVALID_ARG for out == NULL, a missing table or count 0; AESW_ERR_NO_DEVICE for a device out of range (or no device);
+ * a member's aesw_create status otherwise.  aesw_destroy(group) destroys the members. */
+int aesw_create_group(aesw_ctx **out, const int *devices, uint32_t count, const uint8_t sbox[256], const uint8_t mul2[256],
+                      const uint8_t mul3[256]);
+/* Members of a group; 0 for a plain context. */
+int aesw_group_size(const aesw_ctx *ctx);
+/* Member i (borrowed: owned by the group), NULL when i is out of range or ctx is not a group. */
+aesw_ctx *aesw_group_member(aesw_ctx *ctx, uint32_t i);
+/* Block range of member i of `members` for a batch of n blocks: [n*i/G, n*(i+1)/G) (sharding.shard_range).  Pure host.
+ * AESW_ERR_INVALID_ARG for members == 0 or i >= members. */
+int aesw_group_shard(uint32_t members, uint64_t n, uint32_t i, uint64_t *first, uint64_t *count);
+
 /* ---- multi-GPU exchange (one process per GPU, RCCL over xGMI) -------------- */
 /* Blocks shard by contiguous index range and need no collective to be generated
  * (SURVEY 8(e)); handing the whole witness to one consumer is ONE gather: every

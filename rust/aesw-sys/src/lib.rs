@@ -389,6 +389,20 @@ extern "C" {
         t3: *mut u8,
     ) -> c_int;
 
+    // ---- device groups: one process, several GPUs, each over its own link ----
+    // The result is an ordinary `*mut aesw_ctx`: the host-pointer calls above split their batch over the members.
+    pub fn aesw_create_group(
+        out: *mut *mut aesw_ctx,
+        devices: *const c_int,
+        count: u32,
+        sbox: *const u8,
+        mul2: *const u8,
+        mul3: *const u8,
+    ) -> c_int;
+    pub fn aesw_group_size(ctx: *const aesw_ctx) -> c_int;
+    pub fn aesw_group_member(ctx: *mut aesw_ctx, i: u32) -> *mut aesw_ctx;
+    pub fn aesw_group_shard(members: u32, n: u64, i: u32, first: *mut u64, count: *mut u64) -> c_int;
+
     // ---- multi-GPU exchange (one process per GPU, RCCL over xGMI) ----
     pub fn aesw_comm_unique_id(id: *mut u8) -> c_int;
     pub fn aesw_comm_create(
