@@ -7,6 +7,7 @@ size-independent properties (see test_gpu_full_size.py).
 import numpy as np
 import pytest
 
+import guarded
 import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
@@ -80,15 +81,18 @@ def test_per_block_keys_without_key_slab(ctx, oracle, layout):
 
 @pytest.mark.parametrize("layout", [ol.DENSE, ol.PACKED])
 @pytest.mark.parametrize("n", [1, 15, 16, 100])
-def test_key_schedule_kernel(ctx, oracle, layout, n):
-    import torch
+def test_key_schedule_kernel(ctx, pkg, oracle, layout, n):
     _, keys = _inputs(n)
     exp = oracle.key_schedule_witness(keys, layout=layout)
     try:
-        for mode in (1, 0, 2):  # nontemporal (default), plain, write-through
+        for i, mode in enumerate((1, 0, 2)):  # nontemporal (default), plain, write-through
             ctx.set_option("key_store_mode", mode)
-            got = ctx.key_schedule_witness(torch.from_numpy(keys).cuda(), layout=layout)
-            torch.cuda.synchronize()
+            # every mode writes into its own poisoned, guard-banded outputs: none can pass on the previous mode's bytes
+            a = guarded.DeviceArena(guarded.CANARIES[i % 2])
+            got = a.key_witness(pkg, n, layout, want_rk=True)
+            assert all(a.poisoned(t) for t in got)
+            guarded.key_schedule(ctx, a.input("keys", keys), layout, got)
+            a.check()
             for c in ("w", "kx", "ky", "kz", "rk"):
                 _cmp(c, getattr(got, c), getattr(exp, c))
     finally:
@@ -183,9 +187,11 @@ def test_launch_options(pkg, oracle, waves, nt):
     pt, keys = _inputs(300)
     for layout in (ol.DENSE, ol.PACKED, ol.VALUES):
         for k_host in (keys[0], keys):
+            a = guarded.DeviceArena(guarded.CANARIES[k_host.ndim - 1])  # poisoned: no case passes on the previous case's bytes
+            out = a.witness(pkg, 300, layout, want_ct=False, key_slab=True, n_keys=1 if k_host.ndim == 1 else 300)
             got = c.encrypt_witness(torch.from_numpy(pt).cuda(), torch.from_numpy(np.ascontiguousarray(k_host)).cuda(),
-                                    layout=layout, key_slab=True)
-            torch.cuda.synchronize()
+                                    layout=layout, key_slab=True, out=out)
+            a.check()
             exp = oracle.encrypt_witness(pt, k_host, layout=layout)
             for col in "xyz":
                 _cmp(col, getattr(got, col), getattr(exp, col))
@@ -235,9 +241,11 @@ def test_xcd_remap(pkg, oracle, remap):
     for n in (64 * 11 + 5, 64 * 8, 37):
         pt, keys = _inputs(n)
         for k_host in (keys[0], keys):
+            a = guarded.DeviceArena(guarded.CANARIES[remap])  # poisoned: the other remap's bytes cannot be inherited
+            out = a.witness(pkg, n, ol.PACKED, want_ct=True, key_slab=False)
             got = c.encrypt_witness(torch.from_numpy(pt).cuda(), torch.from_numpy(np.ascontiguousarray(k_host)).cuda(),
-                                    layout=ol.PACKED, want_ct=True)
-            torch.cuda.synchronize()
+                                    layout=ol.PACKED, want_ct=True, out=out)
+            a.check()
             exp = oracle.encrypt_witness(pt, k_host, layout=ol.PACKED)
             for col in "xyz":
                 _cmp(col, getattr(got, col), getattr(exp, col))
@@ -254,9 +262,11 @@ def test_group_striding(pkg, oracle, cap):
     pt, keys = _inputs(1111)
     for layout in (ol.DENSE, ol.PACKED, ol.VALUES):
         for k_host in (keys[0], keys):
+            a = guarded.DeviceArena(guarded.CANARIES[cap % 2])  # poisoned: the previous cap's bytes cannot be inherited
+            out = a.witness(pkg, 1111, layout, want_ct=True, key_slab=True, n_keys=1 if k_host.ndim == 1 else 1111)
             got = c.encrypt_witness(torch.from_numpy(pt).cuda(), torch.from_numpy(np.ascontiguousarray(k_host)).cuda(),
-                                    layout=layout, want_ct=True, key_slab=True)
-            torch.cuda.synchronize()
+                                    layout=layout, want_ct=True, key_slab=True, out=out)
+            a.check()
             exp = oracle.encrypt_witness(pt, k_host, layout=layout)
             for col in "xyz":
                 _cmp(col, getattr(got, col), getattr(exp, col))

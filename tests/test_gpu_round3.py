@@ -4,6 +4,7 @@ restated synthesize()."""
 import numpy as np
 import pytest
 
+import guarded
 import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
@@ -338,9 +339,16 @@ def test_assemble_oneshot_geometry_equals_the_striding_kernel_and_synthesize(ctx
     kw = ctx.schedule_key(torch.from_numpy(key).cuda(), layout=pkg.LAYOUT_PACKED, key_slab=True)
     wit = ctx.encrypt_witness(torch.from_numpy(pts).cuda(), None, layout=pkg.LAYOUT_PACKED)
     outs = []
+    shape = (3 * n_sets + 1, 1 << k, 32)
     for geo in range(5):
         ctx.set_option("assemble_geometry", geo)
-        outs.append(ctx.assemble_advice(k, n_sets, wit, kw, n, layout=pkg.LAYOUT_PACKED, as_fr=True).cpu().numpy())
+        # a fresh poisoned, guard-banded output per geometry: no geometry can pass on the previous one's bytes
+        a = guarded.DeviceArena(guarded.CANARIES[geo % 2])
+        out = a.out("advice", int(np.prod(shape)), shape)
+        assert a.poisoned(out)
+        ctx.assemble_advice(k, n_sets, wit, kw, n, layout=pkg.LAYOUT_PACKED, as_fr=True, out=out)
+        a.check()
+        outs.append(out.cpu().numpy())
     ctx.set_option("assemble_geometry", 4)
     assert all(np.array_equal(outs[0], o) for o in outs[1:])
     fr_mod = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001

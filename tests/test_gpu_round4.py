@@ -6,6 +6,7 @@ asynchronous and may name different streams; include/aesw.h states what is guara
 import numpy as np
 import pytest
 
+import guarded
 import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
@@ -454,10 +455,19 @@ def test_assemble_geometries_at_the_fallback_boundary_and_with_a_partly_filled_l
     else:
         expect = _small_k_expectation(oracle, k, n_sets, key)
     try:
+        ncol = 3 * n_sets + 1
         for geo in range(5):
             ctx.set_option("assemble_geometry", geo)
-            fr = ctx.assemble_advice(k, n_sets, wit, kw, n, layout=pkg.LAYOUT_PACKED, as_fr=True).cpu().numpy()
-            by = ctx.assemble_advice(k, n_sets, wit, kw, n, layout=pkg.LAYOUT_PACKED, as_fr=False).cpu().numpy()
+            # fresh poisoned, guard-banded outputs per geometry: no geometry can pass on the previous one's bytes, and the
+            # never-assigned cells must be written as 0, not inherited
+            a = guarded.DeviceArena(guarded.CANARIES[geo % 2])
+            fr_out = a.out("fr", ncol * (32 << k), (ncol, 1 << k, 32))
+            by_out = a.out("bytes", ncol << k, (ncol, 1 << k))
+            assert a.poisoned(fr_out) and a.poisoned(by_out)
+            ctx.assemble_advice(k, n_sets, wit, kw, n, layout=pkg.LAYOUT_PACKED, as_fr=True, out=fr_out)
+            ctx.assemble_advice(k, n_sets, wit, kw, n, layout=pkg.LAYOUT_PACKED, as_fr=False, out=by_out)
+            a.check()
+            fr, by = fr_out.cpu().numpy(), by_out.cpu().numpy()
             assert np.array_equal(by, expect), (geo, "bytes")
             assert np.array_equal(fr, lut[expect]), (geo, "Fr cells")
     finally:
