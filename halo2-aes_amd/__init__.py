@@ -18,13 +18,13 @@ from . import constants
 from .constants import (AES_ROWS, KEY_ROWS, KEY_SCHEDULE_ROWS, LAYOUT_DENSE, LAYOUT_PACKED, LAYOUT_VALUES, TABLE_ROWS, WORDS_ROWS,
                         fips_tables, reference_tables)
 from .api import (AeswError, Comm, Context, Group, HostCircuit, group_shard, assemble_selectors, KeyWitness, Witness, block_capacity, block_copy_graph, block_placement,
-                  column_stride, key_copy_graph,
+                  circuit_offsets, column_stride, key_copy_graph,
                   device_count, key_column_stride, key_packed_index, layout_index, load_library, packed_index, selector_tags)
 from . import sharding
 
 __all__ = [
     "constants", "AES_ROWS", "KEY_ROWS", "KEY_SCHEDULE_ROWS", "LAYOUT_DENSE", "LAYOUT_PACKED", "LAYOUT_VALUES", "TABLE_ROWS",
     "WORDS_ROWS", "fips_tables", "reference_tables", "AeswError", "Comm", "Context", "Group", "HostCircuit", "group_shard", "assemble_selectors", "KeyWitness", "Witness",
-    "block_capacity", "block_copy_graph", "block_placement", "column_stride", "key_copy_graph", "device_count", "key_column_stride", "key_packed_index",
+    "block_capacity", "block_copy_graph", "block_placement", "circuit_offsets", "column_stride", "key_copy_graph", "device_count", "key_column_stride", "key_packed_index",
     "layout_index", "load_library", "packed_index", "selector_tags", "sharding",
 ]

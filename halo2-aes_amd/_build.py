@@ -66,7 +66,8 @@ def build_host(force: bool = False) -> Path:
 
 
 def build_product(force: bool = False) -> Path:
-    srcs = [CSRC / "aesw_kernels.hip", CSRC / "aesw_api.cpp", CSRC / "aesw_arena.cpp", CSRC / "aesw_comm.cpp", CSRC / "aesw_group.cpp"]
+    srcs = [CSRC / "aesw_kernels.hip", CSRC / "aesw_api.cpp", CSRC / "aesw_arena.cpp", CSRC / "aesw_comm.cpp", CSRC / "aesw_group.cpp",
+            CSRC / "aesw_circuits.cpp"]
     deps = srcs + [CSRC / "aesw_lane.h", CSRC / "aesw_layout.h", CSRC / "aesw_check.h", CSRC / "aesw_internal.h", CSRC / "aesw_ctx.h", ROOT / "include" / "aesw.h"]
     if not force and _newer(LIB, deps):
         return LIB

@@ -109,6 +109,7 @@ SYMBOLS = {
     "aesw_check_witness": (_I, [_P, _P, _P, _I, _U64, _I, _P, _P, _P, _P, C.POINTER(KeySlab), C.POINTER(CheckReport)]),
     "aesw_last_stream_check": (_I, [_P, C.POINTER(CheckReport)]),
     "aesw_assemble_advice_device": (_I, [_P, _U32, _U32, _U64, _I, _P, _P, _P, C.POINTER(KeySlab), _I, _P, _P]),
+    "aesw_assemble_advice_circuits_device": (_I, [_P, _U32, _U32, _U32, _P, _I, _P, _P, _P, C.POINTER(KeySlab), _I, _P, _P]),
     "aesw_columns_alloc": (_I, [_P, _U64, _I, _I, _I, C.POINTER(Columns)]),
     "aesw_columns_free": (_I, [_P, C.POINTER(Columns)]),
     "aesw_encrypt_witness": (_I, [_P, _P, _P, _I, _U64, _I, _P, _P, _P, _P, C.POINTER(KeySlab)]),
@@ -266,6 +267,24 @@ def block_placement(k: int, n_sets: int, b: int):
 
 def block_capacity(k: int, n_sets: int) -> int:
     return int(load_library().aesw_block_capacity(k, n_sets))
+
+
+def circuit_offsets(k: int, n_sets: int, counts, n: int) -> np.ndarray:
+    """uint64[C+1] block offsets of C FixedAes128Config<k, n_sets> circuits (circuit c owns blocks [offsets[c], offsets[c+1]))
+    from their block counts; ValueError unless there is at least one circuit, every count is 0 ... block_capacity(k, n_sets)
+    (the reference panics "AES calls too many") and the counts sum to n."""
+    counts = [int(c) for c in counts]
+    if not counts:
+        raise ValueError("at least one circuit is needed")
+    cap = block_capacity(k, n_sets)
+    for i, c in enumerate(counts):
+        if c < 0 or c > cap:
+            raise ValueError("circuit %d: %d blocks, a FixedAes128Config<%d, %d> holds 0 ... %d" % (i, c, k, n_sets, cap))
+    if sum(counts) != n:
+        raise ValueError("the circuits' counts sum to %d, the batch has %d blocks" % (sum(counts), n))
+    offs = np.zeros(len(counts) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(counts, dtype=np.uint64)
+    return offs
 
 
 def selector_tags():
@@ -709,6 +728,57 @@ class Context:
         self._check(rc, "aesw_assemble_advice_device")
         return out
 
+    # -- many circuits per launch
+    def _offsets_tensor(self, offs: np.ndarray):
+        return self._torch().from_numpy(offs.view(np.int64)).to(self._dev())
+
+    def assemble_advice_circuits(self, k: int, n_sets: int, witness: Witness, key_witness: KeyWitness, counts, as_fr: bool = False,
+                                 layout: int = K.LAYOUT_PACKED, n_blocks: int | None = None, out=None, _offsets=None):
+        """aesw_assemble_advice_circuits_device: the advice columns of C FixedAes128Config<k, n_sets> circuits as
+        [C, 3*n_sets+1, 2^k] bytes, or [C, 3*n_sets+1, 2^k, 32] Fr cells with as_fr; circuit c is counts[c] blocks of
+        `witness` (in order) and key slab c of `key_witness`.  n_blocks (default: the blocks `witness` holds) must equal
+        sum(counts); the counts are checked before anything is launched."""
+        if n_blocks is None:
+            n_blocks = int(witness.y.numel()) // column_stride(layout, 1)
+        offs = circuit_offsets(k, n_sets, counts, n_blocks)
+        nc = len(offs) - 1
+        if key_witness is None or int(key_witness.w.numel()) < nc * K.WORDS_ROWS:
+            raise ValueError("key_witness must hold one key slab per circuit")
+        torch = self._torch()
+        shape = (nc, 3 * n_sets + 1, 1 << k) + ((32,) if as_fr else ())
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(out.shape) != shape:
+            raise ValueError("out must have shape %r" % (shape,))
+        self._u8(out, "out")
+        ks = KeySlab(*[self._u8(t, "key_witness").data_ptr() for t in key_witness[:4]])
+        d_offs = self._offsets_tensor(offs) if _offsets is None else _offsets
+        rc = self._lib.aesw_assemble_advice_circuits_device(
+            self._h, k, n_sets, nc, d_offs.data_ptr(), layout, witness.x.data_ptr(), witness.y.data_ptr(), witness.z.data_ptr(),
+            C.byref(ks), 1 if as_fr else 0, out.data_ptr(), self._stream())
+        self._check(rc, "aesw_assemble_advice_circuits_device")
+        return out
+
+    def circuits(self, k: int, n_sets: int, keys, pt, counts, as_fr: bool = True):
+        """C FixedAes128Config<k, n_sets> circuits on torch's current stream: the key schedule of keys (uint8[C,16]), the
+        witness of pt (uint8[n,16]; circuit c takes the next counts[c] blocks) with each block under its circuit's key, and
+        the advice columns of every circuit in one launch.  Returns (witness, key_witness, advice): the PACKED block slabs and
+        ciphertexts, the C key slabs and advice [C, 3*n_sets+1, 2^k] (bytes) or [..., 32] (Fr)."""
+        offs = circuit_offsets(k, n_sets, counts, int(pt.shape[0]))
+        keys = self._u8(keys, "keys")
+        if tuple(keys.shape) != (len(offs) - 1, 16):
+            raise ValueError("keys must be [C,16] for C = len(counts)")
+        torch = self._torch()
+        d_offs = self._offsets_tensor(offs)
+        kw = self.key_schedule_witness(keys, K.LAYOUT_PACKED, want_rk=False)
+        # every block under its circuit's key: the per-block-key launch on the keys gathered by circuit (16 B per block)
+        per_block = torch.repeat_interleave(keys, torch.as_tensor(counts, dtype=torch.int64, device=keys.device), dim=0)
+        n = int(pt.shape[0])
+        wit = self.encrypt_witness(pt, per_block, K.LAYOUT_PACKED, want_ct=True) if n else \
+            self.alloc_witness(1, K.LAYOUT_PACKED, want_ct=True)  # no block: key rows only (the slabs are never read)
+        adv = self.assemble_advice_circuits(k, n_sets, wit, kw, counts, as_fr=as_fr, n_blocks=n, _offsets=d_offs)
+        return wit, kw, adv
+
     # -- host entry points (numpy in, numpy out)
     def encrypt_witness_host(self, pt: np.ndarray, keys: np.ndarray, layout: int = K.LAYOUT_PACKED,
                              want_ct: bool = False, key_slab: bool = False, out_cols=None):
@@ -902,7 +972,7 @@ class Group(Context):
 # the device-tensor methods of Context (the C ABI refuses them on a group as well)
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
-              "assemble_advice_host"):
+              "assemble_advice_host", "assemble_advice_circuits", "circuits"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 

@@ -89,3 +89,21 @@ hipError_t launch_check(const CheckParams &p, hipStream_t s);
 hipError_t launch_expand_fr(const uint8_t *cells, uint64_t n_cells, const void *fr_lut, void *out, int store_mode, int geometry, hipStream_t s);
 
 }  // namespace aesw
+
+// Many circuits per launch (aesw_kernels.hip, namespace aesw_circ): circuit c owns blocks [offsets[c], offsets[c+1]).
+namespace aesw_circ {
+struct CircAsmParams {
+    const uint8_t *x, *y, *z;          // the batch's block slabs
+    const uint8_t *kw, *kx, *ky, *kz;  // n_circuits key slabs (any may be null)
+    const void *fr_lut;
+    uint8_t *out;                      // n_circuits x (3 n_sets + 1) << k cells
+    const uint64_t *offsets;           // n_circuits + 1 (device)
+    uint64_t cap0, capn, cap;          // filled by the launcher
+    uint32_t k, n_sets;
+    uint32_t sx, sy, sz, kxs, kys, kzs;
+    int packed;
+    uint32_t c_first, cshift;          // filled by the launcher
+};
+hipError_t launch_assemble_circuits(const CircAsmParams &p, uint32_t n_circuits, bool as_fr, hipStream_t s);
+}  // namespace aesw_circ
+

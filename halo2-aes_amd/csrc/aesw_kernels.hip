@@ -1351,3 +1351,96 @@ hipError_t launch_expand_fr(const uint8_t *cells, uint64_t n_cells, const void *
 }
 
 }  // namespace aesw
+
+// ---------------------------------------------------------------------------
+// many circuits per launch (aesw_assemble_advice_circuits_device)
+// ---------------------------------------------------------------------------
+// A namespace of their own: tests/kernel_cases.py pins the set of aesw:: kernels, tests/test_circuits_coverage.py these.
+namespace aesw_circ {
+using namespace aesw;
+
+// The advice columns of many circuits: assemble_fr_aligned_kernel's geometry 4 (AS_FR: 128 threads x two 16-byte half cells,
+// 4 KiB of 128 rows per workgroup) and, for bytes, 128 threads x 4 cells (512 rows, one dword store each).  Workgroup x =
+// (circuit - c_first) << cshift | chunk, y = column; everything that depends on the circuit and the column is scalar.
+// A circuit places at most `cap` (aesw_block_capacity) blocks whatever its offsets say, and writes only its own cells.
+template <bool AS_FR>
+__global__ void __launch_bounds__(128) circuit_assemble_kernel(const CircAsmParams a) {
+    constexpr uint32_t RPW = AS_FR ? 128 : 512;  // rows per workgroup
+    const uint32_t ci = a.c_first + (blockIdx.x >> a.cshift);
+    const uint32_t chunk = blockIdx.x & ((1u << a.cshift) - 1u);
+    const uint32_t col = blockIdx.y, cols = 3 * a.n_sets + 1;
+    const uint64_t o0 = a.offsets[ci], o1 = a.offsets[ci + 1];
+    const uint64_t n_c = o1 > o0 ? (o1 - o0 < a.cap ? o1 - o0 : a.cap) : 0;
+    const bool words = col == 3 * a.n_sets;
+    const uint32_t set = col / 3, c = col - 3 * set;
+    const uint32_t base = (!words && set == 0) ? KEY_ROWS : 0;
+    const uint8_t *kc0 = c == 0 ? a.kx : c == 1 ? a.ky : a.kz;
+    const uint32_t kstride = c == 0 ? a.kxs : c == 1 ? a.kys : a.kzs;
+    const uint8_t *kc = kc0 ? kc0 + (uint64_t)ci * kstride : nullptr;
+    const uint8_t *kw = a.kw ? a.kw + (uint64_t)ci * WORDS_ROWS : nullptr;
+    const uint32_t stride = c == 0 ? a.sx : c == 1 ? a.sy : a.sz;
+    const uint8_t *sc = (c == 0 ? a.x : c == 1 ? a.y : a.z) + o0 * stride;  // dereferenced only below n_c
+    const uint64_t cap = set == 0 ? a.cap0 : a.capn;
+    const uint64_t b0 = set == 0 ? 0 : a.cap0 + (uint64_t)(set - 1) * a.capn;
+    const uint32_t rows = 1u << a.k;
+    const uint64_t first_cell = ((uint64_t)ci * cols + col) << a.k;
+    // the cell code is written out as in assemble_fr_aligned_kernel (no lambda): the index helpers then see the same
+    // argument ranges from every caller, and the aesw:: kernels that share them compile to the code they had before
+    constexpr int PER = AS_FR ? 2 : 4;
+    const uint32_t half = threadIdx.x & 1;
+    uint32_t row[PER], v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        row[j] = AS_FR ? ((chunk * 2 + j) * 128 + threadIdx.x) >> 1 : chunk * RPW + threadIdx.x * 4 + j;  // rows % 4 == 0 (k >= 2)
+        v[j] = 0;
+        if (row[j] >= rows) continue;
+        if (words) {
+            if (row[j] < WORDS_ROWS && kw) v[j] = kw[row[j]];
+        } else if (row[j] < base) {
+            const int idx = a.packed ? packed_index_key((int)c, (int)row[j]) : (int)row[j];
+            if (kc && idx >= 0) v[j] = kc[idx];
+        } else {
+            const uint32_t rr = row[j] - base, bi = rr / AES_ROWS, r = rr - bi * AES_ROWS;
+            const int idx = a.packed ? packed_index_enc((int)c, (int)r) : (int)r;
+            if (bi < cap && b0 + bi < n_c && idx >= 0) v[j] = sc[(b0 + bi) * stride + idx];
+        }
+    }
+    if (AS_FR) {
+        const u32x4 *lut = reinterpret_cast<const u32x4 *>(a.fr_lut);
+        u32x4 *out = reinterpret_cast<u32x4 *>(a.out) + first_cell * 2 + half;
+        u32x4 f[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) f[j] = lut[v[j] * 2 + half];
+#pragma unroll
+        for (int j = 0; j < PER; ++j)
+            if (row[j] < rows) gstore<1>(out + (uint64_t)row[j] * 2, f[j]);
+    } else if (row[0] < rows) {
+        *reinterpret_cast<uint32_t *>(a.out + first_cell + row[0]) = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
+    }
+}
+
+hipError_t launch_assemble_circuits(const CircAsmParams &p0, uint32_t n_circuits, bool as_fr, hipStream_t s) {
+    if (n_circuits == 0 || p0.k < 2 || p0.k > 30) return hipErrorInvalidValue;
+    CircAsmParams p = p0;
+    const uint64_t rows = (uint64_t)1 << p.k;
+    p.cap0 = rows >= 1760 ? (rows - 1760) / AES_ROWS : 0;
+    p.capn = rows / AES_ROWS;
+    p.cap = p.cap0 + (uint64_t)(p.n_sets - 1) * p.capn;
+    const uint32_t rpw_log = as_fr ? 7 : 9;
+    p.cshift = p.k > rpw_log ? p.k - rpw_log : 0;
+    // the grid's x dimension stays below 2^31 workgroups: circuits in slices (one launch for all but the largest shapes)
+    const uint32_t per = (uint32_t)(0x7fffffffu >> p.cshift);
+    const dim3 block(128);
+    for (uint32_t c0 = 0; c0 < n_circuits; c0 += per) {
+        const uint32_t m = n_circuits - c0 < per ? n_circuits - c0 : per;
+        p.c_first = c0;
+        const dim3 grid(m << p.cshift, 3 * p.n_sets + 1);
+        if (as_fr) hipLaunchKernelGGL((circuit_assemble_kernel<true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((circuit_assemble_kernel<false>), grid, block, 0, s, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace aesw_circ

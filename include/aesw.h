@@ -289,6 +289,29 @@ int aesw_assemble_advice_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint
                                 const uint8_t *d_z, const aesw_key_slab *d_key_slab, int as_fr,
                                 uint8_t *d_out, void *stream);
 
+/* ---- many circuits ----------------------------------------------------------
+ * A prover's create_proof takes a slice of FixedAes128Config<k, n_sets> circuits: each schedules one key and encrypts up to
+ * aesw_block_capacity(k, n_sets) blocks (src/aes128.rs:143-165).  C such circuits as one batch: aesw_key_schedule_witness_device
+ * over the C keys (C key slabs), the blocks' witness (aesw_encrypt_witness_device with each block's circuit key), then ONE
+ * call below for the advice columns of all C circuits.  Circuit c owns blocks [d_offsets[c], d_offsets[c+1]) of the batch:
+ * d_offsets is a DEVICE array of C+1 uint64_t (8-byte aligned) with offsets[0] = 0, non-decreasing, offsets[C] = n and every
+ * count offsets[c+1] - offsets[c] <= aesw_block_capacity(k, n_sets).  The device cannot report offsets that break this, so callers validate them first:
+ * the kernel then still reads and writes only inside each circuit's own ranges (a count is clamped to the capacity), but
+ * what it computes for such offsets is unspecified.  The call is asynchronous on `stream`, neither allocates nor waits on
+ * the host, and may be captured into a hipGraph.  A group context returns AESW_ERR_INVALID_ARG. */
+/* The advice columns of C FixedAes128Config<k, n_sets> circuits, circuit after circuit: circuit c's (3 n_sets + 1) << k
+ * cells start at cell c (3 n_sets + 1) << k of d_out (16-byte aligned) and are exactly what aesw_assemble_advice_device
+ * writes for blocks [offsets[c], offsets[c+1]) of d_x / d_y / d_z (the batch's slabs in `layout`, DENSE or PACKED) and key
+ * slab c, never-assigned cells 0 included.  d_key_slabs: ONE aesw_key_slab whose columns hold C contiguous key slabs (key
+ * slab c at w + 96 c, kx + c aesw_key_column_stride(layout, 0), ...), as aesw_key_schedule_witness_device writes them; NULL
+ * or a NULL member leaves those cells 0.  as_fr: 0 one byte per cell, 1 AESW_FR_BYTES per cell.  k: 2 ... 30, n_sets:
+ * 1 ... 1024, n_circuits >= 1.  The store-flavour options ("fr_store_mode") and "assemble_geometry" do not apply: Fr cells
+ * leave with nontemporal stores from one-shot workgroups of 4 KiB. */
+int aesw_assemble_advice_circuits_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32_t n_circuits,
+                                         const uint64_t *d_offsets, int layout, const uint8_t *d_x,
+                                         const uint8_t *d_y, const uint8_t *d_z,
+                                         const aesw_key_slab *d_key_slabs, int as_fr, uint8_t *d_out, void *stream);
+
 /* The device-side home of what FixedAes128Config::encrypt (src/aes128.rs:154-265) and schedule_keys
  * (src/key_schedule.rs:80-96) assign: every output column of a batch of n blocks -- x, y, z, optionally the
  * ciphertext and n key slabs (w, kx, ky, kz) -- allocated together ("arena").  The reference has no counterpart (its
@@ -443,9 +466,10 @@ int aesw_lookup_table(aesw_ctx *ctx, uint8_t *t0, uint8_t *t1, uint8_t *t2, uint
  *                                over the members, wall_ns the group call's own wall time.
  *   aesw_set_option              applied to every member; aesw_get_option, aesw_lookup_table, aesw_uses_xtime_path: member 0.
  *   aesw_device                  member 0's device.
- *   everything else              every *_device entry point, aesw_columns_alloc / _free, the aesw_assemble_advice_* entry points
- *                                and aesw_comm_create return AESW_ERR_INVALID_ARG: device pointers belong to one GPU.  Use a
- *                                member (aesw_group_member) for them.
+ *   everything else              every *_device entry point (aesw_assemble_advice_circuits_device among them),
+ *                                aesw_columns_alloc / _free, the aesw_assemble_advice_* entry points and aesw_comm_create
+ *                                return AESW_ERR_INVALID_ARG: device pointers belong to one GPU.  Use a member
+ *                                (aesw_group_member) for them.
  * The status of a group call is the first non-OK one in member order; aesw_last_error(group) names that member and its device.
  * Host threads: a member's automatic "copy_threads" is its share of the CPUs, a quarter of them divided among the G members
  * (1 ... 4 each), so a group of one behaves exactly as a plain context; an explicit "copy_threads" applies per member.

@@ -260,6 +260,23 @@ extern "C" {
         d_out: *mut u8,
         stream: *mut c_void,
     ) -> c_int;
+    /// Many circuits per launch: the advice columns of n_circuits circuits, circuit after circuit; circuit c owns
+    /// blocks [d_offsets[c], d_offsets[c+1]) (device array of n_circuits + 1 u64); d_key_slabs: one key slab per circuit.
+    pub fn aesw_assemble_advice_circuits_device(
+        ctx: *mut aesw_ctx,
+        k: u32,
+        n_sets: u32,
+        n_circuits: u32,
+        d_offsets: *const u64,
+        layout: c_int,
+        d_x: *const u8,
+        d_y: *const u8,
+        d_z: *const u8,
+        d_key_slabs: *const aesw_key_slab,
+        as_fr: c_int,
+        d_out: *mut u8,
+        stream: *mut c_void,
+    ) -> c_int;
     pub fn aesw_encrypt_witness_batches_device(
         ctx: *mut aesw_ctx,
         batches: *const aesw_batch,
