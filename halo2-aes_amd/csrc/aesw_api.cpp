@@ -279,6 +279,8 @@ void aesw_destroy(aesw_ctx *ctx) {
     if (aesw_is_group(ctx)) return aesw_group_destroy(ctx);
     {
         DeviceGuard g(ctx->device);
+        // nothing below may unmap, free or recycle what a launch still queued on any stream uses
+        (void)hipDeviceSynchronize();
         if (ctx->s_compute) (void)hipStreamDestroy(ctx->s_compute);
         if (ctx->s_copy) (void)hipStreamDestroy(ctx->s_copy);
         for (int j = 0; j < 8; ++j) {
@@ -583,6 +585,7 @@ int aesw_get_option(const aesw_ctx *ctx, const char *name, int64_t *value) {
         return AESW_OK;
     }
     if (!std::strcmp(name, "key_reader_waits")) { *value = (int64_t)ctx->key_waits; return AESW_OK; }  // read-only statistics
+    if (!std::strcmp(name, "key_writer_waits")) { *value = (int64_t)ctx->key_writer_waits; return AESW_OK; }
     if (!std::strcmp(name, "key_slots_allocated")) { *value = (int64_t)ctx->key_slots.size(); return AESW_OK; }
     if (!std::strcmp(name, "key_slots_pinned")) {
         int64_t n = 0;
@@ -633,6 +636,12 @@ int aesw_schedule_key_device(aesw_ctx *ctx, const uint8_t *d_key, int layout, co
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool cap = stream_capturing(s);
     int slot = -1;
+    // an eager schedule that fails before its key launch is issued leaves the slot as it was: keep its readers (still tracked)
+    // and step the ring back, so that the next schedule comes back to the slot with them intact
+    auto unwind = [&](hipError_t e, const char *what) {
+        if (!cap) ctx->key_pos = (ctx->key_pos + (int)ctx->key_ring_slots.size() - 1) % (int)ctx->key_ring_slots.size();
+        return fail_hip(ctx, e, what);
+    };
     if (cap) {
         // a captured schedule writes its slot on every replay of the graph, whenever that is: a slot of its own, never reused
         const int rc = key_new_slot(ctx, &slot);
@@ -643,25 +652,31 @@ int aesw_schedule_key_device(aesw_ctx *ctx, const uint8_t *d_key, int layout, co
         if (rc != AESW_OK) return rc;
         // write-after-read: every launch that may still read this slot's previous key, on whatever stream, comes first
         aesw_ctx::KeySlot &sl = ctx->key_slots[slot];
-        hipError_t e = hipSuccess;
         for (auto &r : sl.readers) {
-            if (e == hipSuccess) e = hipStreamWaitEvent(s, r.e, 0);
-            if (e != hipSuccess) break;
+            const hipError_t e = hipStreamWaitEvent(s, r.e, 0);
+            if (e != hipSuccess) return unwind(e, "hipStreamWaitEvent(key readers)");
             ++ctx->key_waits;
         }
-        if (e != hipSuccess) {
-            // keep the readers: the slot has not been written, and the ring must come back to it with them intact
-            ctx->key_pos = (ctx->key_pos + (int)ctx->key_ring_slots.size() - 1) % (int)ctx->key_ring_slots.size();
-            return fail_hip(ctx, e, "hipStreamWaitEvent(key readers)");
+        // write-after-write: the key launch that wrote the slot last may still be queued on its own stream; run behind it, or it
+        // lands on top of this key and its older key becomes the current one
+        if (sl.written && sl.writer != s) {
+            const hipError_t e = hipStreamWaitEvent(s, sl.ready, 0);
+            if (e != hipSuccess) return unwind(e, "hipStreamWaitEvent(key writer)");
+            ++ctx->key_writer_waits;
         }
-        for (auto &r : sl.readers) ctx->event_pool.push_back(r.e);
-        sl.readers.clear();
     }
     aesw_ctx::KeySlot &sl = ctx->key_slots[slot];
     KeyParams kp{d_key, ctx->d_tables, ko, sl.d, 1, 0, 0};
-    HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, s));
-    // a later encrypt on ANOTHER stream (the host-pointer entry points use the context's own) waits for these round keys
-    if (!cap) HIP_TRY(ctx, hipEventRecord(sl.ready, s));
+    const hipError_t le = launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, s);
+    if (le != hipSuccess) return unwind(le, "launch_key");
+    sl.written = true;
+    if (!cap) {
+        // the new key is issued behind every earlier reader: their events are free again
+        for (auto &r : sl.readers) ctx->event_pool.push_back(r.e);
+        sl.readers.clear();
+        // a later encrypt on ANOTHER stream (the host-pointer entry points use the context's own) waits for these round keys
+        HIP_TRY(ctx, hipEventRecord(sl.ready, s));
+    }
     sl.writer = s;
     ctx->key_cur = slot;
     ctx->have_key = true;

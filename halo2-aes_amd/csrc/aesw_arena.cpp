@@ -341,6 +341,9 @@ int aesw_columns_free(aesw_ctx *ctx, aesw_columns *cols) {
         bool vmm = false;
         for (size_t i = 0; i < ctx->vmm_arenas.size(); ++i)
             if (ctx->vmm_arenas[i].key == cols->base) {
+                // what hipFree guarantees on the unprobed path: launches still queued into the arena finish first (a cached
+                // arena goes to the next caller of this shape at once, an uncached one is unmapped)
+                HIP_TRY(ctx, hipDeviceSynchronize());
                 if (ctx->arena_cache_on && ctx->vmm_arenas[i].cols.bytes <= ctx->arena_cache_max_bytes) {
                     // keep the placement: the next arena of this shape takes it over (freed memory would be handed out again
                     // in some other combination, and the search would start over)

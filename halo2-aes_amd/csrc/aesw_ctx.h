@@ -20,12 +20,14 @@ struct aesw_ctx {
     // ring and every scheduled-key launch bakes the pointer of the slot that is current when it is ENQUEUED, so a launch never sees
     // a later key.  A slot is rewritten only behind every launch that reads it: one event per distinct reader stream (re-recorded
     // by that stream's later launches, which are ordered behind its earlier ones), all of them waited on by the schedule that
-    // reuses the slot.  Slots a hipGraph capture has touched (a captured schedule writes one, a captured launch reads one on every
-    // replay) are PINNED: the ring never hands them out again.
+    // reuses the slot.  That schedule is also ordered behind the key launch that wrote the slot last, when it ran on another
+    // stream (its `ready` event).  Slots a hipGraph capture has touched (a captured schedule writes one, a captured launch reads one
+    // on every replay) are PINNED: the ring never hands them out again.
     struct KeyReader { hipStream_t s; hipEvent_t e; };
     struct KeySlot {
         uint8_t *d = nullptr;
         bool pinned = false;
+        bool written = false;        // a key launch has been issued into the slot (`writer` may be the null stream: no marker)
         hipEvent_t ready = nullptr;  // recorded behind the key launch that wrote the slot: launches on other streams wait on it
         hipStream_t writer = nullptr;
         std::vector<KeyReader> readers;  // launches that may still be reading the slot
@@ -39,6 +41,7 @@ struct aesw_ctx {
     int key_cur = -1;       // slot of the current key (-1: none scheduled)
     int key_ring = 4;       // option "key_slots": un-pinned slots the ring cycles through (1 = every schedule waits for all readers)
     uint64_t key_waits = 0;  // statistics: reader events a schedule had to wait on (option "key_reader_waits", read-only)
+    uint64_t key_writer_waits = 0;  // statistics: schedules ordered behind another stream's writer of their slot ("key_writer_waits", read-only)
     bool have_key = false;
     bool xt = false;
     int waves_shared = 0;  // waves per group, shared-key kernels (0 = auto)

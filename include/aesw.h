@@ -182,6 +182,10 @@ int aesw_key_copy_graph(aesw_copy_edge edges[AESW_KEY_COPIES]);
  *    (on the scheduling stream, no host wait) by the schedule that takes the slot again.  More than 16 distinct reader streams
  *    per slot are folded (the 17th stream waits for the first one's launches AFTER its own launch).  Streams that carried
  *    scheduled-key launches may be destroyed at any time (hipStreamDestroy drains a stream in the ROCm runtime).
+ *  - A schedule that takes a slot again is ordered behind the key kernel that last wrote it: on the same stream by stream
+ *    order, on another stream (aesw_schedule_key's null stream included) by that kernel's event, waited on by the scheduling
+ *    stream, no host wait.  A key kernel still queued on a busy stream therefore never lands on top of a later key.
+ *    Read-only statistic "key_writer_waits": the schedules that waited for another stream's writer this way.
  *  - Under hipGraph capture nothing can be tracked per replay, so slots are frozen instead: a schedule captured into a graph
  *    writes a slot of its own, and a slot read by a captured launch is pinned -- in both cases the ring never hands that slot
  *    out again (256 B each, until aesw_destroy).  A captured launch therefore reads, on every replay, the key that was current
@@ -348,7 +352,10 @@ int aesw_assemble_advice_circuits_device(aesw_ctx *ctx, uint32_t k, uint32_t n_s
  * for a new shape finds less free memory than twice its size + 16 GB, by aesw_set_option("arena_cache", 0) and by
  * aesw_destroy.  Arenas allocated with probing off are plain hipMalloc / hipFree and never cached.
  * Unused members are NULL.  aesw_columns_free releases the arena (or hands it to the cache) and clears the struct; cols must
- * come from aesw_columns_alloc on the same context. */
+ * come from aesw_columns_alloc on the same context.  Like hipFree, aesw_columns_free waits for the device's outstanding work
+ * before the arena is released or cached: a launch enqueued into the arena on any stream before the call finishes first, so
+ * it can neither write into the columns of the arena's next owner nor run on unmapped memory.  aesw_destroy waits the same
+ * way before it releases anything. */
 typedef struct aesw_columns {
     uint8_t *base;  /* the allocation (arena_probe 0) / the handle of the arena */
     uint64_t bytes; /* device memory held */
@@ -549,7 +556,8 @@ int aesw_gather_columns_device(aesw_comm *comm, int root, int n_cols, const uint
  * (bytes the cache may hold, default 65536), "arena_probe_budget_ms" (wall-time bound of one placement search, default 3000, 0 = none).
  * aesw_get_option reads back every option aesw_set_option accepts, plus "effective_waves_shared" / "effective_waves_pbk" /
  * "effective_waves_key": the group size a packed-layout launch really uses (auto resolved, limits applied; for the key kernel: its witness-only form, without round-key output), and "effective_copy_threads", and the
- * read-only statistics "key_reader_waits" (reader events schedules have waited on), "key_slots_allocated", "key_slots_pinned",
+ * read-only statistics "key_reader_waits" (reader events schedules have waited on), "key_writer_waits" (schedules that waited
+ * for the key kernel another stream had issued into their slot), "key_slots_allocated", "key_slots_pinned",
  * "arena_cache_hits", "arena_cached_bytes".
  * Unknown -> INVALID_ARG */
 int aesw_set_option(aesw_ctx *ctx, const char *name, int64_t value);
