@@ -65,24 +65,33 @@ def build_host(force: bool = False) -> Path:
     return HOST_LIB
 
 
-def build_product(force: bool = False) -> Path:
-    srcs = [CSRC / "aesw_kernels.hip", CSRC / "aesw_api.cpp", CSRC / "aesw_arena.cpp", CSRC / "aesw_comm.cpp", CSRC / "aesw_group.cpp",
-            CSRC / "aesw_circuits.cpp"]
-    deps = srcs + [CSRC / "aesw_lane.h", CSRC / "aesw_layout.h", CSRC / "aesw_check.h", CSRC / "aesw_internal.h", CSRC / "aesw_ctx.h", ROOT / "include" / "aesw.h"]
-    if not force and _newer(LIB, deps):
-        return LIB
+# The one list of what libaesw.so is made of: tools that build a private variant of the library (tools/trace.py, parts.py,
+# key_ab.py, sanitize.sh) take it from here.
+PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp", "aesw_comm.cpp",
+                                      "aesw_group.cpp", "aesw_circuits.cpp")]
+PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_check.h", "aesw_internal.h", "aesw_ctx.h")] + \
+    [ROOT / "include" / "aesw.h"]
+
+
+def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_sources=()) -> Path:
+    """libaesw.so, or with `extra_flags` / `extra_sources` and another `out` a diagnostic variant of it (-DAESW_TRACE, ...)."""
+    out = Path(out)
+    srcs = PRODUCT_SOURCES + [Path(s) for s in extra_sources]
+    deps = srcs + PRODUCT_HEADERS
+    if not force and _newer(out, deps):
+        return out
     # several ranks may get here at once (torchrun): serialise on a lock file, build under a
     # private name, publish with an atomic rename
     import fcntl
     with open(PKG / ".build.lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if not force and _newer(LIB, deps):
-                return LIB  # another process built it while we waited
-            tmp = LIB.with_suffix(".so.tmp%d" % os.getpid())
-            _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread",
-                  "-o", str(tmp)] + [str(s) for s in srcs])
-            os.replace(tmp, LIB)
+            if not force and _newer(out, deps):
+                return out  # another process built it while we waited
+            tmp = out.with_suffix(".so.tmp%d" % os.getpid())
+            _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread"] + list(extra_flags) +
+                 ["-o", str(tmp)] + [str(s) for s in srcs])
+            os.replace(tmp, out)
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB
+    return out

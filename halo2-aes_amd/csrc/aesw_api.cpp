@@ -1,19 +1,16 @@
-// aesw_api.cpp -- the C ABI of include/aesw.h on top of the gfx950 kernels.
+// aesw_api.cpp -- the C ABI of include/aesw.h on top of the gfx950 kernels: context, geometry, options and the
+// device-pointer entry points (the host-pointer ones are aesw_hostpath.cpp).
 // Host code only (compiled by hipcc for the HIP runtime API).  There is no CPU
 // compute path: without a usable device every computing entry point fails.
 #include <hip/hip_runtime.h>
-#include <sched.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-#include <ctime>
 #include <mutex>
 #include <new>
 #include <string>
-#include <atomic>
-#include <thread>
 #include <vector>
 
 #include "../../include/aesw.h"
@@ -30,6 +27,12 @@ namespace {
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 bool valid_layout(int l) { return aesw_valid_layout(l); }
+
+// The output columns of a key slab (null slab = none wanted); false if one of them is not 16-byte aligned.
+bool key_out_of(const aesw_key_slab *ks, KeyOut *ko) {
+    *ko = ks ? KeyOut{ks->w, ks->kx, ks->ky, ks->kz} : KeyOut{nullptr, nullptr, nullptr, nullptr};
+    return (!ko->w || aligned16(ko->w)) && (!ko->kx || aligned16(ko->kx)) && (!ko->ky || aligned16(ko->ky)) && (!ko->kz || aligned16(ko->kz));
+}
 
 uint8_t xtime(uint8_t a) { return (uint8_t)((a << 1) ^ ((a & 0x80) ? 0x1b : 0)); }
 
@@ -79,26 +82,6 @@ void build_fr_lut(uint8_t out[256 * 32]) {
 static void vmm_release_arena(void *va, size_t total) {
     (void)hipMemUnmap(va, total);
     (void)hipMemAddressFree(va, total);
-}
-
-extern "C" {
-
-int aesw_version(void) { return AESW_VERSION; }
-
-const char *aesw_strerror(int status) {
-    switch (status) {
-    case AESW_OK: return "ok";
-    case AESW_ERR_INVALID_ARG: return "invalid argument";
-    case AESW_ERR_NO_DEVICE: return "no usable gfx950 device (this library has no CPU path)";
-    case AESW_ERR_HIP: return "HIP runtime error";
-    case AESW_ERR_NOMEM: return "out of memory";
-    case AESW_ERR_CAPACITY: return "AES calls too many. doesn't fit in the rows";
-    case AESW_ERR_NO_KEY: return "Keys should be scheduled";
-    case AESW_ERR_MISMATCH: return "host value disagrees with the device witness";
-    case AESW_ERR_UNSATISFIED: return "constraint system not satisfied";
-    case AESW_ERR_COMM: return "RCCL unavailable or a collective call failed";
-    default: return "unknown status";
-    }
 }
 
 // ---- the scheduled key's round-key slots (aesw_ctx.h) ----------------------------------------------------------
@@ -180,8 +163,11 @@ int key_next_ring_slot(aesw_ctx *ctx, int *out) {
     return AESW_OK;
 }
 
+}  // namespace
+
 // An un-captured launch on `s` reads slot `sl`: the schedule that reuses the slot will wait for it.  One event per distinct
-// stream: a stream's later record is ordered behind its earlier launches, so re-recording loses nobody.
+// stream: a stream's later record is ordered behind its earlier launches, so re-recording loses nobody.  (Declared in
+// aesw_ctx.h: the streaming entry point of aesw_hostpath.cpp reads the slot of a scheduled key on the context's own stream.)
 int key_track_reader(aesw_ctx *ctx, aesw_ctx::KeySlot &sl, hipStream_t s) {
     for (auto &r : sl.readers)
         if (r.s == s) { HIP_TRY(ctx, hipEventRecord(r.e, s)); return AESW_OK; }
@@ -200,7 +186,102 @@ int key_track_reader(aesw_ctx *ctx, aesw_ctx::KeySlot &sl, hipStream_t s) {
     sl.readers.push_back(aesw_ctx::KeyReader{s, e});
     return AESW_OK;
 }
-}  // namespace
+
+// Waves per group when the option is 0 (auto): as many 16-block waves as keep
+// 6-8 waves resident per CU given the LDS windows (DESIGN.md "occupancy").
+static int auto_waves(const aesw_ctx *ctx, int layout, bool pbk) {
+    // upper bound: a group's staging must stay below 64 KiB (16-bit LDS addresses in the flush descriptors)
+    const int max_waves = layout == AESW_LAYOUT_DENSE ? 2 : layout == AESW_LAYOUT_VALUES ? 4 : 3;
+    int w;
+    // per-block keys: one-wave groups (7 resident per CU instead of two 3-wave groups) measured +1.3 ... +2.4 % at 2^20
+    // blocks on two boxes and -0.6 % on a third (tools/sweep.py 20 c2 packed waves); shared key: 3-wave groups
+    if (pbk) w = ctx->waves_pbk ? ctx->waves_pbk : 1;
+    else w = ctx->waves_shared ? ctx->waves_shared : (layout == AESW_LAYOUT_DENSE ? 2 : 3);
+    return w > max_waves ? max_waves : w;
+}
+
+// key_kernel alone (tools/keysweep.py, 2^20 keys): packed 4-wave groups, dense 2-wave groups
+static int auto_waves_key(const aesw_ctx *ctx, int layout, bool want_rk) {
+    // packed, witness only (no round-key output: no 2.8 KB round-key staging per wave since round 4): three 3-wave groups fit a CU
+    // (45.7 KB each) and run 143.7 us against 146.3 for 4-wave groups and 148.0 / 154.9 for 2 / 1 (tools/keyarena.py,
+    // profiles/r04_study/key_kernel_kz.md); with round keys a 3-wave group is 54 KB (two per CU): 4-wave groups as before
+    if (ctx->waves_pbk) return ctx->waves_pbk;
+    if (layout == AESW_LAYOUT_DENSE) return 2;
+    return want_rk ? 4 : 3;
+}
+
+// ---- shared with aesw_hostpath.cpp (declared in aesw_ctx.h) --------------------------------------------------------
+int fill_assemble_params(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x, const uint8_t *d_y,
+                         const uint8_t *d_z, const aesw_key_slab *ks, AssembleParams *p) {
+    if (!ctx || !valid_layout(layout) || layout == AESW_LAYOUT_VALUES /* whole columns need every cell */ || k < 2 || k > 32 ||
+        n_sets == 0 || n_sets > 1024)
+        return AESW_ERR_INVALID_ARG;
+    if (n_blocks && (!d_x || !d_y || !d_z)) return AESW_ERR_INVALID_ARG;
+    if (n_blocks > aesw_block_capacity(k, n_sets)) return AESW_ERR_CAPACITY;  // panic in the reference, src/aes128.rs:160-162
+    *p = AssembleParams{};
+    p->x = d_x; p->y = d_y; p->z = d_z;
+    if (ks) { p->kw = ks->w; p->kx = ks->kx; p->ky = ks->ky; p->kz = ks->kz; }
+    p->fr_lut = ctx->d_fr_lut;
+    p->n_blocks = n_blocks;
+    p->k = k;
+    p->n_sets = n_sets;
+    p->col_first = 0;
+    p->col_count = 3 * n_sets + 1;
+    p->sx = aesw_column_stride(layout, 0); p->sy = aesw_column_stride(layout, 1); p->sz = aesw_column_stride(layout, 2);
+    p->kxs = aesw_key_column_stride(layout, 0); p->kys = aesw_key_column_stride(layout, 1); p->kzs = aesw_key_column_stride(layout, 2);
+    p->packed = layout == AESW_LAYOUT_PACKED;
+    p->geometry = ctx->asm_geo;
+    return AESW_OK;
+}
+
+int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys, uint64_t n, int layout,
+                       const uint8_t *d_x, const uint8_t *d_y, const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *ks,
+                       aesw_check_report *d_report, void *stream, bool skip_shared_key) {
+    static_assert(sizeof(aesw_check_report) == 7 * sizeof(uint64_t), "the kernels address the report as seven u64");
+    if (!ctx || !d_report || (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED)) return AESW_ERR_INVALID_ARG;
+    if (per_block_keys && n && !d_keys) return AESW_ERR_INVALID_ARG;
+    if (n && (!d_pt || !d_x || !d_y || !d_z || !ks || !ks->w || !ks->kx || !ks->ky || !ks->kz)) return AESW_ERR_INVALID_ARG;
+    if (n && (!aligned4(d_pt) || !aligned4(d_x) || !aligned4(d_y) || !aligned4(d_z) || !aligned4(ks->w) || !aligned4(ks->kx) || !aligned4(ks->ky) ||
+              !aligned4(ks->kz) || (reinterpret_cast<uintptr_t>(d_report) & 7u)))
+        return AESW_ERR_INVALID_ARG;
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return AESW_ERR_NO_DEVICE;
+    const int li = layout == AESW_LAYOUT_DENSE ? 0 : 1;  // the check tables were uploaded by aesw_create(): nothing is allocated here
+    const CheckGeo cg = check_geo(layout);
+    CheckParams p{};
+    p.pt = d_pt; p.keys = d_keys; p.x = d_x; p.y = d_y; p.z = d_z; p.ct = d_ct;
+    if (ks) { p.kw = ks->w; p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
+    p.table = ctx->d_chktab[li];
+    p.tab768 = ctx->d_tables;
+    p.report = reinterpret_cast<uint64_t *>(d_report);
+    p.n = n;
+    p.per_block_keys = per_block_keys ? 1u : 0u;
+    p.skip_shared_key = skip_shared_key ? 1u : 0u;
+    p.sx = cg.sx; p.sy = cg.sy; p.sz = cg.sz; p.kxs = cg.kxs; p.kys = cg.kys; p.kzs = cg.kzs; p.bi = cg.bi;
+    p.img = (cg.bi + cg.ki + 15u) & ~15u;
+    HIP_TRY(ctx, launch_check(p, reinterpret_cast<hipStream_t>(stream)));
+    return AESW_OK;
+}
+
+extern "C" {
+
+int aesw_version(void) { return AESW_VERSION; }
+
+const char *aesw_strerror(int status) {
+    switch (status) {
+    case AESW_OK: return "ok";
+    case AESW_ERR_INVALID_ARG: return "invalid argument";
+    case AESW_ERR_NO_DEVICE: return "no usable gfx950 device (this library has no CPU path)";
+    case AESW_ERR_HIP: return "HIP runtime error";
+    case AESW_ERR_NOMEM: return "out of memory";
+    case AESW_ERR_CAPACITY: return "AES calls too many. doesn't fit in the rows";
+    case AESW_ERR_NO_KEY: return "Keys should be scheduled";
+    case AESW_ERR_MISMATCH: return "host value disagrees with the device witness";
+    case AESW_ERR_UNSATISFIED: return "constraint system not satisfied";
+    case AESW_ERR_COMM: return "RCCL unavailable or a collective call failed";
+    default: return "unknown status";
+    }
+}
 
 const char *aesw_last_error(const aesw_ctx *ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 
@@ -504,46 +585,6 @@ int aesw_set_option(aesw_ctx *ctx, const char *name, int64_t value) {
     return AESW_ERR_INVALID_ARG;
 }
 
-static int auto_waves(const aesw_ctx *ctx, int layout, bool pbk);
-// Pageable destinations of the host-pointer entry points: a stage arrives in the page-locked bounce buffer by DMA and is
-// moved on from there by the CPU.  One thread moves ~20 GB/s (less into memory it touches for the first time), the link
-// delivers 55: the move is cut into 4 MiB slices handed out to "copy_threads" threads (the caller is one of them).
-struct CopyJob { uint8_t *dst; const uint8_t *src; size_t bytes; };
-static int auto_copy_threads(const aesw_ctx *ctx) {
-    if (ctx->copy_threads >= 0) return ctx->copy_threads < 1 ? 1 : ctx->copy_threads;
-    cpu_set_t set;
-    int usable = 1;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) usable = CPU_COUNT(&set);
-    // leave the host its cores: a quarter of what this process may run on, 1 ... 4, shared among the members of a group
-    const int t = usable / (4 * ctx->group_size);
-    return t < 1 ? 1 : (t > 4 ? 4 : t);
-}
-static void parallel_copy(const std::vector<CopyJob> &jobs, int threads) noexcept {
-    constexpr size_t SLICE = (size_t)4 << 20;
-    std::vector<CopyJob> slices;
-    std::vector<std::thread> pool;
-    try {
-        for (const CopyJob &j : jobs)
-            for (size_t o = 0; o < j.bytes; o += SLICE) slices.push_back(CopyJob{j.dst + o, j.src + o, j.bytes - o < SLICE ? j.bytes - o : SLICE});
-        pool.reserve(threads > 1 ? (size_t)threads - 1 : 0);
-    } catch (...) {  // no memory for the bookkeeping: copy on this thread (nothing has been started yet)
-        for (const CopyJob &j : jobs) std::memcpy(j.dst, j.src, j.bytes);
-        return;
-    }
-    if ((int)slices.size() < threads) threads = (int)slices.size();
-    std::atomic<size_t> next{0};
-    auto work = [&]() noexcept {
-        for (size_t i = next.fetch_add(1); i < slices.size(); i = next.fetch_add(1)) std::memcpy(slices[i].dst, slices[i].src, slices[i].bytes);
-    };
-    for (int t = 1; t < threads; ++t) {
-        try { pool.emplace_back(work); } catch (...) { break; }  // no thread to be had: the others and the caller copy the rest
-    }
-    work();
-    for (std::thread &t : pool) t.join();
-}
-
-static int auto_waves_key(const aesw_ctx *ctx, int layout, bool want_rk);
-
 int aesw_get_option(const aesw_ctx *ctx, const char *name, int64_t *value) {
     if (aesw_is_group(ctx)) return aesw_get_option(ctx->members[0], name, value);  // a group: member 0
     if (!ctx || !name || !value) return AESW_ERR_INVALID_ARG;
@@ -598,39 +639,11 @@ int aesw_get_option(const aesw_ctx *ctx, const char *name, int64_t *value) {
 
 // ---- device-pointer entry points ------------------------------------------------
 
-// Waves per group when the option is 0 (auto): as many 16-block waves as keep
-// 6-8 waves resident per CU given the LDS windows (DESIGN.md "occupancy").
-static int auto_waves(const aesw_ctx *ctx, int layout, bool pbk) {
-    // upper bound: a group's staging must stay below 64 KiB (16-bit LDS addresses in the flush descriptors)
-    const int max_waves = layout == AESW_LAYOUT_DENSE ? 2 : layout == AESW_LAYOUT_VALUES ? 4 : 3;
-    int w;
-    // per-block keys: one-wave groups (7 resident per CU instead of two 3-wave groups) measured +1.3 ... +2.4 % at 2^20
-    // blocks on two boxes and -0.6 % on a third (tools/sweep.py 20 c2 packed waves); shared key: 3-wave groups
-    if (pbk) w = ctx->waves_pbk ? ctx->waves_pbk : 1;
-    else w = ctx->waves_shared ? ctx->waves_shared : (layout == AESW_LAYOUT_DENSE ? 2 : 3);
-    return w > max_waves ? max_waves : w;
-}
-
-// key_kernel alone (tools/keysweep.py, 2^20 keys): packed 4-wave groups, dense 2-wave groups
-static int auto_waves_key(const aesw_ctx *ctx, int layout, bool want_rk) {
-    // packed, witness only (no round-key output: no 2.8 KB round-key staging per wave since round 4): three 3-wave groups fit a CU
-    // (45.7 KB each) and run 143.7 us against 146.3 for 4-wave groups and 148.0 / 154.9 for 2 / 1 (tools/keyarena.py,
-    // profiles/r04_study/key_kernel_kz.md); with round keys a 3-wave group is 54 KB (two per CU): 4-wave groups as before
-    if (ctx->waves_pbk) return ctx->waves_pbk;
-    if (layout == AESW_LAYOUT_DENSE) return 2;
-    return want_rk ? 4 : 3;
-}
-
 int aesw_schedule_key_device(aesw_ctx *ctx, const uint8_t *d_key, int layout, const aesw_key_slab *ks, void *stream) {
     if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_schedule_key_device");
     if (!ctx || !valid_layout(layout) || !d_key || !aligned4(d_key)) return AESW_ERR_INVALID_ARG;
-    KeyOut ko{nullptr, nullptr, nullptr, nullptr};
-    if (ks) {
-        ko = KeyOut{ks->w, ks->kx, ks->ky, ks->kz};
-        if ((ko.w && !aligned16(ko.w)) || (ko.kx && !aligned16(ko.kx)) || (ko.ky && !aligned16(ko.ky)) ||
-            (ko.kz && !aligned16(ko.kz)))
-            return AESW_ERR_INVALID_ARG;
-    }
+    KeyOut ko;
+    if (!key_out_of(ks, &ko)) return AESW_ERR_INVALID_ARG;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -698,13 +711,8 @@ int aesw_encrypt_witness_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_
     if ((has_x && !aligned16(d_x)) || !aligned16(d_y) || !aligned16(d_z) || !aligned4(d_pt) || (d_keys && !aligned4(d_keys)) ||
         (d_ct && !aligned4(d_ct)))
         return AESW_ERR_INVALID_ARG;
-    KeyOut ko{nullptr, nullptr, nullptr, nullptr};
-    if (ks) {
-        ko = KeyOut{ks->w, ks->kx, ks->ky, ks->kz};
-        if ((ko.w && !aligned16(ko.w)) || (ko.kx && !aligned16(ko.kx)) || (ko.ky && !aligned16(ko.ky)) ||
-            (ko.kz && !aligned16(ko.kz)))
-            return AESW_ERR_INVALID_ARG;
-    }
+    KeyOut ko;
+    if (!key_out_of(ks, &ko)) return AESW_ERR_INVALID_ARG;
     const bool kemit = ko.w || ko.kx || ko.ky || ko.kz;
     if (!d_keys && kemit) return AESW_ERR_INVALID_ARG;  // the key slab of a scheduled key comes from aesw_schedule_key*
     if (ctx->split_small > 1 && !ctx->in_split && !per_block_keys && !kemit && n >= ((uint64_t)1 << 15) && n <= ((uint64_t)1 << 17)) {
@@ -828,12 +836,12 @@ int aesw_key_schedule_witness_device(aesw_ctx *ctx, const uint8_t *d_keys, uint6
     if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
     if (n == 0) return AESW_OK;
     if (!d_keys || !aligned4(d_keys)) return AESW_ERR_INVALID_ARG;
-    if ((d_w && !aligned16(d_w)) || (d_kx && !aligned16(d_kx)) || (d_ky && !aligned16(d_ky)) ||
-        (d_kz && !aligned16(d_kz)) || (d_rk && !aligned16(d_rk)))
-        return AESW_ERR_INVALID_ARG;
+    const aesw_key_slab slab{d_w, d_kx, d_ky, d_kz};
+    KeyOut ko;
+    if (!key_out_of(&slab, &ko) || (d_rk && !aligned16(d_rk))) return AESW_ERR_INVALID_ARG;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
-    KeyParams kp{d_keys, ctx->d_tables, KeyOut{d_w, d_kx, d_ky, d_kz}, d_rk, n, 0, 0};
+    KeyParams kp{d_keys, ctx->d_tables, ko, d_rk, n, 0, 0};
     HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, auto_waves_key(ctx, layout, d_rk != nullptr), ctx->key_nt, ctx->xcd_remap, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;
 }
@@ -846,36 +854,6 @@ int aesw_lookup_table_device(aesw_ctx *ctx, uint8_t *d_t0, uint8_t *d_t1, uint8_
     HIP_TRY(ctx, launch_table(ctx->d_tables, d_t0, d_t1, d_t2, d_t3, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;
 }
-
-namespace {
-int fill_assemble_params(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x, const uint8_t *d_y,
-                         const uint8_t *d_z, const aesw_key_slab *ks, AssembleParams *p) {
-    if (!ctx || !valid_layout(layout) || layout == AESW_LAYOUT_VALUES /* whole columns need every cell */ || k < 2 || k > 32 ||
-        n_sets == 0 || n_sets > 1024)
-        return AESW_ERR_INVALID_ARG;
-    if (n_blocks && (!d_x || !d_y || !d_z)) return AESW_ERR_INVALID_ARG;
-    if (n_blocks > aesw_block_capacity(k, n_sets)) return AESW_ERR_CAPACITY;  // panic in the reference, src/aes128.rs:160-162
-    *p = AssembleParams{};
-    p->x = d_x; p->y = d_y; p->z = d_z;
-    if (ks) { p->kw = ks->w; p->kx = ks->kx; p->ky = ks->ky; p->kz = ks->kz; }
-    p->fr_lut = ctx->d_fr_lut;
-    p->n_blocks = n_blocks;
-    p->k = k;
-    p->n_sets = n_sets;
-    p->col_first = 0;
-    p->col_count = 3 * n_sets + 1;
-    p->sx = aesw_column_stride(layout, 0); p->sy = aesw_column_stride(layout, 1); p->sz = aesw_column_stride(layout, 2);
-    p->kxs = aesw_key_column_stride(layout, 0); p->kys = aesw_key_column_stride(layout, 1); p->kzs = aesw_key_column_stride(layout, 2);
-    p->packed = layout == AESW_LAYOUT_PACKED;
-    p->geometry = ctx->asm_geo;
-    return AESW_OK;
-}
-uint64_t now_ns() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
-}  // namespace
 
 int aesw_assemble_advice_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
                                 const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, int as_fr, uint8_t *d_out,
@@ -892,44 +870,11 @@ int aesw_assemble_advice_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint
     return AESW_OK;
 }
 
-static int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys, uint64_t n, int layout,
-                              const uint8_t *d_x, const uint8_t *d_y, const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *ks,
-                              aesw_check_report *d_report, void *stream, bool skip_shared_key);
-
 int aesw_check_witness_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys, uint64_t n, int layout,
                               const uint8_t *d_x, const uint8_t *d_y, const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *ks,
                               aesw_check_report *d_report, void *stream) {
     if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_check_witness_device");
     return check_witness_impl(ctx, d_pt, d_keys, per_block_keys, n, layout, d_x, d_y, d_z, d_ct, ks, d_report, stream, false);
-}
-
-static int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys, uint64_t n, int layout,
-                              const uint8_t *d_x, const uint8_t *d_y, const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *ks,
-                              aesw_check_report *d_report, void *stream, bool skip_shared_key) {
-    static_assert(sizeof(aesw_check_report) == 7 * sizeof(uint64_t), "the kernels address the report as seven u64");
-    if (!ctx || !d_report || (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED)) return AESW_ERR_INVALID_ARG;
-    if (per_block_keys && n && !d_keys) return AESW_ERR_INVALID_ARG;
-    if (n && (!d_pt || !d_x || !d_y || !d_z || !ks || !ks->w || !ks->kx || !ks->ky || !ks->kz)) return AESW_ERR_INVALID_ARG;
-    if (n && (!aligned4(d_pt) || !aligned4(d_x) || !aligned4(d_y) || !aligned4(d_z) || !aligned4(ks->w) || !aligned4(ks->kx) || !aligned4(ks->ky) ||
-              !aligned4(ks->kz) || (reinterpret_cast<uintptr_t>(d_report) & 7u)))
-        return AESW_ERR_INVALID_ARG;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    const int li = layout == AESW_LAYOUT_DENSE ? 0 : 1;  // the check tables were uploaded by aesw_create(): nothing is allocated here
-    const CheckGeo cg = check_geo(layout);
-    CheckParams p{};
-    p.pt = d_pt; p.keys = d_keys; p.x = d_x; p.y = d_y; p.z = d_z; p.ct = d_ct;
-    if (ks) { p.kw = ks->w; p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
-    p.table = ctx->d_chktab[li];
-    p.tab768 = ctx->d_tables;
-    p.report = reinterpret_cast<uint64_t *>(d_report);
-    p.n = n;
-    p.per_block_keys = per_block_keys ? 1u : 0u;
-    p.skip_shared_key = skip_shared_key ? 1u : 0u;
-    p.sx = cg.sx; p.sy = cg.sy; p.sz = cg.sz; p.kxs = cg.kxs; p.kys = cg.kys; p.kzs = cg.kzs; p.bi = cg.bi;
-    p.img = (cg.bi + cg.ki + 15u) & ~15u;
-    HIP_TRY(ctx, launch_check(p, reinterpret_cast<hipStream_t>(stream)));
-    return AESW_OK;
 }
 
 int aesw_expand_fr_device(aesw_ctx *ctx, const uint8_t *d_cells, uint64_t n_cells, uint8_t *d_fr, void *stream) {
@@ -940,706 +885,6 @@ int aesw_expand_fr_device(aesw_ctx *ctx, const uint8_t *d_cells, uint64_t n_cell
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     HIP_TRY(ctx, launch_expand_fr(d_cells, n_cells, ctx->d_fr_lut, d_fr, ctx->fr_nt, ctx->fr_geo, reinterpret_cast<hipStream_t>(stream)));
-    return AESW_OK;
-}
-
-// ---- host-pointer entry points ----------------------------------------------------
-// Pipeline: blocks are cut into chunks; chunk i's kernel runs on s_compute
-// while chunk i-1's columns travel D2H on s_copy (two device buffer sets).
-
-namespace {
-
-struct DevBuf {
-    uint8_t *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), n ? n : 16); }
-};
-
-int ensure_streams(aesw_ctx *ctx) {
-    if (!ctx->s_compute) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->s_compute, hipStreamNonBlocking));
-    if (!ctx->s_copy) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->s_copy, hipStreamNonBlocking));
-    return AESW_OK;
-}
-
-bool is_pinned(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeHost;
-}
-
-int ensure_bounce(aesw_ctx *ctx, size_t bytes) {
-    if (ctx->bounce_bytes >= bytes) return AESW_OK;
-    for (int i = 0; i < 2; ++i) {
-        if (ctx->bounce[i]) (void)hipHostFree(ctx->bounce[i]);
-        ctx->bounce[i] = nullptr;
-    }
-    ctx->bounce_bytes = 0;
-    for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->bounce[i]), bytes, hipHostMallocDefault));
-    ctx->bounce_bytes = bytes;
-    return AESW_OK;
-}
-
-int ensure_scratch(aesw_ctx *ctx, size_t bytes) {
-    if (ctx->scratch_bytes >= bytes) return AESW_OK;
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->scratch), bytes));
-    ctx->scratch_bytes = bytes;
-    return AESW_OK;
-}
-
-// One output column of the host path: where chunk data goes and how.
-struct HostCol {
-    uint8_t *dst;       // caller buffer (null = not wanted)
-    const uint8_t *dev[2];
-    size_t stride;      // bytes per block
-    bool direct;        // caller buffer is page-locked: DMA straight into it
-    size_t boff;        // offset inside the bounce buffer
-};
-
-}  // namespace
-
-int aesw_encrypt_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n,
-                         int layout, uint8_t *x, uint8_t *y, uint8_t *z, uint8_t *ct, const aesw_key_slab *ks) {
-    if (aesw_is_group(ctx)) return aesw_group_encrypt_witness(ctx, pt, keys, per_block_keys, n, layout, x, y, z, ct, ks);
-    if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
-    if (n == 0) return AESW_OK;
-    if (!pt) return AESW_ERR_INVALID_ARG;  // x / y / z: a null column is computed but not copied back
-    if (!keys && (per_block_keys || (ks && (ks->w || ks->kx || ks->ky || ks->kz)))) return AESW_ERR_INVALID_ARG;
-    if (!keys && !ctx->have_key) return AESW_ERR_NO_KEY;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    int rc = ensure_streams(ctx);
-    if (rc != AESW_OK) return rc;
-    const size_t sx = aesw_column_stride(layout, 0), sy = aesw_column_stride(layout, 1), sz = aesw_column_stride(layout, 2);
-    const size_t kxs = aesw_key_column_stride(layout, 0), kys = aesw_key_column_stride(layout, 1),
-                 kzs = aesw_key_column_stride(layout, 2);
-    const bool kemit = ks && (ks->w || ks->kx || ks->ky || ks->kz);
-    const bool pbk = per_block_keys != 0;
-    uint64_t chunk = (uint64_t)ctx->chunk_blocks;
-    if (chunk > n) chunk = n;
-    chunk = (chunk + 63) / 64 * 64;
-
-    // carve the context's device scratch: inputs, ciphertext, two sets of output columns
-    struct Carve { uint8_t *p = nullptr; };
-    Carve d_pt, d_keys, d_ct, dx[2], dy[2], dz[2], dw[2], dkx[2], dky[2], dkz[2];
-    {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-        const size_t o_pt = take(n * 16), o_keys = take(pbk ? n * 16 : 16), o_ct = take(ct ? n * 16 : 0);
-        size_t o_x[2], o_y[2], o_z[2], o_w[2], o_kx[2], o_ky[2], o_kz[2];
-        for (int i = 0; i < 2; ++i) {
-            o_x[i] = take(chunk * sx); o_y[i] = take(chunk * sy); o_z[i] = take(chunk * sz);
-            const size_t kn = kemit ? (pbk ? chunk : 1) : 0;  // per-block keys: a key slab per block; shared key: one
-            o_w[i] = take(kn * WORDS_ROWS); o_kx[i] = take(kn * kxs);
-            o_ky[i] = take(kn * kys); o_kz[i] = take(kn * kzs);
-        }
-        rc = ensure_scratch(ctx, off ? off : 256);
-        if (rc != AESW_OK) return rc;
-        uint8_t *b = ctx->scratch;
-        d_pt.p = b + o_pt; d_keys.p = b + o_keys; d_ct.p = b + o_ct;
-        for (int i = 0; i < 2; ++i) {
-            dx[i].p = b + o_x[i]; dy[i].p = b + o_y[i]; dz[i].p = b + o_z[i];
-            dw[i].p = b + o_w[i]; dkx[i].p = b + o_kx[i]; dky[i].p = b + o_ky[i]; dkz[i].p = b + o_kz[i];
-        }
-    }
-    HostCol cols[7] = {
-        {sx ? x : nullptr, {dx[0].p, dx[1].p}, sx, false, 0}, {y, {dy[0].p, dy[1].p}, sy, false, 0}, {z, {dz[0].p, dz[1].p}, sz, false, 0},
-        {pbk && kemit ? ks->w : nullptr, {dw[0].p, dw[1].p}, WORDS_ROWS, false, 0},
-        {pbk && kemit ? ks->kx : nullptr, {dkx[0].p, dkx[1].p}, kxs, false, 0},
-        {pbk && kemit ? ks->ky : nullptr, {dky[0].p, dky[1].p}, kys, false, 0},
-        {pbk && kemit ? ks->kz : nullptr, {dkz[0].p, dkz[1].p}, kzs, false, 0}};
-    size_t bounce_need = 0;
-    for (HostCol &c : cols) {
-        if (!c.dst) continue;
-        c.direct = is_pinned(c.dst);
-        if (!c.direct) {
-            c.boff = bounce_need;
-            bounce_need += (chunk * c.stride + 255) / 256 * 256;
-        }
-    }
-    if (bounce_need) {
-        rc = ensure_bounce(ctx, bounce_need);
-        if (rc != AESW_OK) return rc;
-    }
-    // Whatever happens below, no copy may still be reading or writing the caller's buffers when we return.
-    struct SyncGuard {
-        aesw_ctx *c;
-        ~SyncGuard() {
-            (void)hipStreamSynchronize(c->s_copy);
-            (void)hipStreamSynchronize(c->s_compute);
-        }
-    } sync_guard{ctx};
-    hipEvent_t done[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *a, *b;
-        ~EvGuard() { for (int i = 0; i < 2; ++i) { if (a[i]) (void)hipEventDestroy(a[i]); if (b[i]) (void)hipEventDestroy(b[i]); } }
-    } evg{done, copied};
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&copied[i], hipEventDisableTiming));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d_pt.p, pt, n * 16, hipMemcpyHostToDevice, ctx->s_compute));
-    if (keys) HIP_TRY(ctx, hipMemcpyAsync(d_keys.p, keys, pbk ? n * 16 : 16, hipMemcpyHostToDevice, ctx->s_compute));
-
-    if (!pbk && kemit) {
-        // shared key: one key slab, staged in stage 0's (still unused) key buffers of the scratch, copied back on s_compute
-        rc = aesw_key_schedule_witness_device(ctx, d_keys.p, 1, layout, dw[0].p, dkx[0].p, dky[0].p, dkz[0].p, nullptr, ctx->s_compute);
-        if (rc != AESW_OK) return rc;
-        if (ks->w) HIP_TRY(ctx, hipMemcpyAsync(ks->w, dw[0].p, WORDS_ROWS, hipMemcpyDeviceToHost, ctx->s_compute));
-        if (ks->kx) HIP_TRY(ctx, hipMemcpyAsync(ks->kx, dkx[0].p, kxs, hipMemcpyDeviceToHost, ctx->s_compute));
-        if (ks->ky) HIP_TRY(ctx, hipMemcpyAsync(ks->ky, dky[0].p, kys, hipMemcpyDeviceToHost, ctx->s_compute));
-        if (ks->kz) HIP_TRY(ctx, hipMemcpyAsync(ks->kz, dkz[0].p, kzs, hipMemcpyDeviceToHost, ctx->s_compute));
-    }
-
-    // Drain stage s: wait for its D2H, then move bounce data into pageable destinations.
-    uint64_t stage_b0[2] = {0, 0}, stage_m[2] = {0, 0};
-    bool stage_busy[2] = {false, false};
-    auto drain = [&](int s) -> int {
-        if (!stage_busy[s]) return AESW_OK;
-        HIP_TRY(ctx, hipEventSynchronize(copied[s]));
-        std::vector<CopyJob> jobs;
-        for (const HostCol &c : cols)
-            if (c.dst && !c.direct) jobs.push_back(CopyJob{c.dst + stage_b0[s] * c.stride, ctx->bounce[s] + c.boff, (size_t)(stage_m[s] * c.stride)});
-        if (!jobs.empty()) parallel_copy(jobs, auto_copy_threads(ctx));
-        stage_busy[s] = false;
-        return AESW_OK;
-    };
-    uint64_t b0 = 0;
-    int it = 0;
-    while (b0 < n) {
-        const uint64_t m = n - b0 < chunk ? n - b0 : chunk;
-        const int s = it & 1;
-        rc = drain(s);  // device buffers and bounce buffer of this stage are free again
-        if (rc != AESW_OK) return rc;
-        aesw_key_slab dks{dw[s].p, dkx[s].p, dky[s].p, dkz[s].p};
-        rc = aesw_encrypt_witness_device(ctx, d_pt.p + 16 * b0, !keys ? nullptr : (pbk ? d_keys.p + 16 * b0 : d_keys.p), per_block_keys, m,
-                                         layout, dx[s].p, dy[s].p, dz[s].p, ct ? d_ct.p + 16 * b0 : nullptr,
-                                         pbk && kemit ? &dks : nullptr, ctx->s_compute);
-        if (rc != AESW_OK) return rc;
-        HIP_TRY(ctx, hipEventRecord(done[s], ctx->s_compute));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_copy, done[s], 0));
-        for (const HostCol &c : cols) {
-            if (!c.dst) continue;
-            uint8_t *to = c.direct ? c.dst + b0 * c.stride : ctx->bounce[s] + c.boff;
-            HIP_TRY(ctx, hipMemcpyAsync(to, c.dev[s], m * c.stride, hipMemcpyDeviceToHost, ctx->s_copy));
-        }
-        HIP_TRY(ctx, hipEventRecord(copied[s], ctx->s_copy));
-        stage_b0[s] = b0;
-        stage_m[s] = m;
-        stage_busy[s] = true;
-        b0 += m;
-        ++it;
-    }
-    rc = drain(it & 1);
-    if (rc != AESW_OK) return rc;
-    rc = drain((it + 1) & 1);
-    if (rc != AESW_OK) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->s_copy));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->s_compute));
-    if (ct) HIP_TRY(ctx, hipMemcpy(ct, d_ct.p, n * 16, hipMemcpyDeviceToHost));
-    return AESW_OK;
-}
-
-int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n, int layout,
-                                aesw_chunk_fn consume, void *user) {
-    if (aesw_is_group(ctx)) return aesw_group_encrypt_witness_stream(ctx, pt, keys, per_block_keys, n, layout, consume, user);
-    if (!ctx || !valid_layout(layout) || !consume) return AESW_ERR_INVALID_ARG;
-    if (n == 0) return AESW_OK;
-    if (!pt || (!keys && per_block_keys)) return AESW_ERR_INVALID_ARG;
-    if (!keys && !ctx->have_key) return AESW_ERR_NO_KEY;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    int rc = ensure_streams(ctx);
-    if (rc != AESW_OK) return rc;
-    const size_t strides[3] = {aesw_column_stride(layout, 0), aesw_column_stride(layout, 1), aesw_column_stride(layout, 2)};
-    const bool pbk = per_block_keys != 0;
-    uint64_t chunk = (uint64_t)ctx->chunk_blocks;
-    if (chunk > n) chunk = n;
-    chunk = (chunk + 63) / 64 * 64;
-    // device scratch: inputs + two sets of columns; page-locked bounce: two sets of columns
-    size_t off = 0, col_off[2][3], boff[3], bneed = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_pt = take(n * 16), o_keys = take(pbk ? n * 16 : 16);
-    for (int s = 0; s < 2; ++s)
-        for (int c = 0; c < 3; ++c) col_off[s][c] = take(chunk * strides[c]);
-    for (int c = 0; c < 3; ++c) { boff[c] = bneed; bneed += (chunk * strides[c] + 255) / 256 * 256; }
-    // "stream_check": every chunk is checked on the device behind its kernel (aesw_check.h).  Needs the key slab(s) the blocks' AddRoundKey
-    // rows copy from -- one for a shared / scheduled key (made once, below), one per block with per-block keys (emitted by the chunk's
-    // own launch into two more scratch sets) -- and one report per chunk, summed after the last one.
-    const bool checking = ctx->stream_check && layout != AESW_LAYOUT_VALUES;
-    const uint64_t n_chunks = (n + chunk - 1) / chunk;
-    const size_t kstr[3] = {aesw_key_column_stride(layout, 0), aesw_key_column_stride(layout, 1), aesw_key_column_stride(layout, 2)};
-    size_t ks_off[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, o_rep = 0;
-    if (checking) {
-        const uint64_t nk = pbk ? chunk : 1;
-        for (int s = 0; s < (pbk ? 2 : 1); ++s) {
-            ks_off[s][0] = take(nk * WORDS_ROWS);
-            for (int c = 0; c < 3; ++c) ks_off[s][1 + c] = take(nk * kstr[c]);
-        }
-        if (!pbk) for (int c = 0; c < 4; ++c) ks_off[1][c] = ks_off[0][c];
-        o_rep = take(n_chunks * sizeof(aesw_check_report));
-    }
-    ctx->stream_report = aesw_check_report{0, 0, 0, 0, 0, 0, AESW_CHECK_NONE};
-    rc = ensure_scratch(ctx, off);
-    if (rc != AESW_OK) return rc;
-    rc = ensure_bounce(ctx, bneed);
-    if (rc != AESW_OK) return rc;
-    uint8_t *d = ctx->scratch;
-    struct SyncGuard {
-        aesw_ctx *c;
-        ~SyncGuard() { (void)hipStreamSynchronize(c->s_copy); (void)hipStreamSynchronize(c->s_compute); }
-    } sync_guard{ctx};
-    HIP_TRY(ctx, hipMemcpyAsync(d + o_pt, pt, n * 16, hipMemcpyHostToDevice, ctx->s_compute));
-    if (keys) HIP_TRY(ctx, hipMemcpyAsync(d + o_keys, keys, pbk ? n * 16 : 16, hipMemcpyHostToDevice, ctx->s_compute));
-    auto slab_of = [&](int s) { return aesw_key_slab{d + ks_off[s][0], d + ks_off[s][1], d + ks_off[s][2], d + ks_off[s][3]}; };
-    const uint8_t *d_key16 = nullptr;  // the 16 key bytes of a shared / scheduled key on the device (the literal rows of words_column)
-    if (checking && !pbk) {
-        // a scheduled key's bytes are the first round key of its slot (rk[0] = the key, src/key_schedule.rs:107-114)
-        d_key16 = keys ? d + o_keys : ctx->key_slots[ctx->key_cur].d;
-        if (!keys) {
-            aesw_ctx::KeySlot &sl = ctx->key_slots[ctx->key_cur];
-            if (!sl.pinned && sl.writer != ctx->s_compute) HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_compute, sl.ready, 0));
-        }
-        const aesw_key_slab one = slab_of(0);
-        KeyParams kp{d_key16, ctx->d_tables, KeyOut{one.w, one.kx, one.ky, one.kz}, nullptr, 1, 0, 0};
-        HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, ctx->s_compute));
-        if (!keys) { const int r = key_track_reader(ctx, ctx->key_slots[ctx->key_cur], ctx->s_compute); if (r != AESW_OK) return r; }
-    }
-    uint64_t chunk_index = 0;
-    // per stage: kernel start / end, copy start / end (timed: aesw_last_stream_stats reports where the time went)
-    hipEvent_t started[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, copy0[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *e[4];
-        ~EvGuard() { for (auto *v : e) for (int i = 0; i < 2; ++i) if (v[i]) (void)hipEventDestroy(v[i]); }
-    } evg{{started, done, copy0, copied}};
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(ctx, hipEventCreate(&started[i]));
-        HIP_TRY(ctx, hipEventCreate(&done[i]));
-        HIP_TRY(ctx, hipEventCreate(&copy0[i]));
-        HIP_TRY(ctx, hipEventCreate(&copied[i]));
-    }
-    aesw_stream_stats st = {};
-    const uint64_t t_begin = now_ns();
-    uint64_t first[2] = {0, 0}, count[2] = {0, 0};
-    bool busy[2] = {false, false};
-    auto issue = [&](int s, uint64_t b0, uint64_t m) -> int {
-        HIP_TRY(ctx, hipEventRecord(started[s], ctx->s_compute));
-        const aesw_key_slab stage_slab = slab_of(s);
-        int r = aesw_encrypt_witness_device(ctx, d + o_pt + 16 * b0, !keys ? nullptr : (pbk ? d + o_keys + 16 * b0 : d + o_keys), per_block_keys, m,
-                                            layout, d + col_off[s][0], d + col_off[s][1], d + col_off[s][2], nullptr,
-                                            checking && pbk ? &stage_slab : nullptr, ctx->s_compute);
-        if (r != AESW_OK) return r;
-        if (ctx->stream_poison > 0 && (uint64_t)ctx->stream_poison - 1 >= b0 && (uint64_t)ctx->stream_poison - 1 < b0 + m) {
-            // diagnostic: two cells of one block are overwritten between the kernel and the check (tests/test_gpu_round4.py shows the
-            // stream check names that block, by its batch-wide index, in whatever chunk it lies)
-            const uint64_t pb = (uint64_t)ctx->stream_poison - 1 - b0;
-            HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][1] + pb * strides[1] + 5, 0x5A, 1, ctx->s_compute));
-            HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][2] + pb * strides[2] + 7, 0xA5, 1, ctx->s_compute));
-        }
-        if (checking) {
-            r = check_witness_impl(ctx, d + o_pt + 16 * b0, pbk ? d + o_keys + 16 * b0 : d_key16, per_block_keys, m, layout, d + col_off[s][0],
-                                   d + col_off[s][1], d + col_off[s][2], nullptr, &stage_slab,
-                                   reinterpret_cast<aesw_check_report *>(d + o_rep) + chunk_index, ctx->s_compute, !pbk && chunk_index != 0);
-            if (r != AESW_OK) return r;
-            if (!keys) { r = key_track_reader(ctx, ctx->key_slots[ctx->key_cur], ctx->s_compute); if (r != AESW_OK) return r; }
-            ++chunk_index;
-        }
-        HIP_TRY(ctx, hipEventRecord(done[s], ctx->s_compute));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_copy, done[s], 0));
-        HIP_TRY(ctx, hipEventRecord(copy0[s], ctx->s_copy));
-        for (int c = 0; c < 3; ++c)
-            if (strides[c])
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->bounce[s] + boff[c], d + col_off[s][c], m * strides[c], hipMemcpyDeviceToHost, ctx->s_copy));
-        HIP_TRY(ctx, hipEventRecord(copied[s], ctx->s_copy));
-        first[s] = b0; count[s] = m; busy[s] = true;
-        return AESW_OK;
-    };
-    // two stages in flight: while the host consumes stage s, stage s^1 is computed and copied
-    uint64_t b0 = 0;
-    int it = 0;
-    for (; it < 2 && b0 < n; ++it) {
-        const uint64_t m = n - b0 < chunk ? n - b0 : chunk;
-        rc = issue(it, b0, m);
-        if (rc != AESW_OK) return rc;
-        b0 += m;
-    }
-    for (int s = 0;; s ^= 1) {
-        if (!busy[s]) break;
-        const uint64_t t0 = now_ns();
-        HIP_TRY(ctx, hipEventSynchronize(copied[s]));
-        const uint64_t t1 = now_ns();
-        busy[s] = false;
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, started[s], done[s]) == hipSuccess) st.kernel_ns += (uint64_t)(ms * 1e6);
-        if (hipEventElapsedTime(&ms, copy0[s], copied[s]) == hipSuccess) st.d2h_ns += (uint64_t)(ms * 1e6);
-        const int cr = consume(user, first[s], count[s], strides[0] ? ctx->bounce[s] + boff[0] : nullptr /* AESW_LAYOUT_VALUES: no x */,
-                               ctx->bounce[s] + boff[1], ctx->bounce[s] + boff[2]);
-        const uint64_t t2 = now_ns();
-        st.wait_ns += t1 - t0;
-        st.consumer_ns += t2 - t1;
-        st.chunks += 1;
-        st.bytes_to_host += count[s] * (strides[0] + strides[1] + strides[2]);
-        if (cr != 0) { st.wall_ns = now_ns() - t_begin; ctx->stats = st; return AESW_ERR_MISMATCH; }
-        if (b0 < n) {
-            const uint64_t m = n - b0 < chunk ? n - b0 : chunk;
-            rc = issue(s, b0, m);
-            if (rc != AESW_OK) return rc;
-            b0 += m;
-        }
-    }
-    st.wall_ns = now_ns() - t_begin;
-    ctx->stats = st;
-    if (checking) {  // every chunk's kernel and check have finished (their columns have been copied): sum the reports
-        std::vector<aesw_check_report> reps((size_t)n_chunks);
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->s_compute));  // (a non-blocking stream: the copy below does not wait for it by itself)
-        HIP_TRY(ctx, hipMemcpy(reps.data(), d + o_rep, reps.size() * sizeof(aesw_check_report), hipMemcpyDeviceToHost));
-        aesw_check_report &t = ctx->stream_report;
-        for (uint64_t i = 0; i < n_chunks; ++i) {
-            const aesw_check_report &r = reps[i];
-            t.blocks += r.blocks; t.keys += r.keys;
-            t.lookup_failures += r.lookup_failures; t.copy_failures += r.copy_failures;
-            t.gate_failures += r.gate_failures; t.input_failures += r.input_failures;
-            if (r.first != AESW_CHECK_NONE) {
-                const uint64_t unit = (r.first >> 20) + ((!pbk && ((r.first >> 19) & 1)) ? 0 : i * chunk);
-                const uint64_t f = unit << 20 | (r.first & 0xfffffu);
-                if (f < t.first) t.first = f;
-            }
-        }
-    }
-    return AESW_OK;
-}
-
-int aesw_last_stream_check(const aesw_ctx *ctx, aesw_check_report *out) {
-    if (!ctx || !out) return AESW_ERR_INVALID_ARG;
-    *out = ctx->stream_report;
-    return AESW_OK;
-}
-
-int aesw_last_stream_stats(const aesw_ctx *ctx, aesw_stream_stats *out) {
-    if (!ctx || !out) return AESW_ERR_INVALID_ARG;
-    *out = ctx->stats;
-    return AESW_OK;
-}
-
-// Whole advice columns of a K/N circuit to the host, column by column ("the host can bulk-copy into
-// halo2's advice polynomials"): column j is assembled on s_compute into one of two device buffers, travels D2H on
-// s_copy into one of two page-locked buffers, and is handed to `consume` while column j+1 is assembled and copied.
-int aesw_assemble_advice_stream(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
-                                const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, int as_fr, aesw_column_fn consume,
-                                void *user) {
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_assemble_advice_stream");
-    if (!consume) return AESW_ERR_INVALID_ARG;
-    AssembleParams p;
-    int rc = fill_assemble_params(ctx, k, n_sets, n_blocks, layout, d_x, d_y, d_z, ks, &p);
-    if (rc != AESW_OK) return rc;
-    if (k > 28) return AESW_ERR_INVALID_ARG;  // one column must fit the staging buffers
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    rc = ensure_streams(ctx);
-    if (rc != AESW_OK) return rc;
-    const uint64_t rows = (uint64_t)1 << k;
-    const size_t col_bytes = (size_t)rows * (as_fr ? AESW_FR_BYTES : 1);
-    const size_t slot = (col_bytes + 255) / 256 * 256;
-    rc = ensure_scratch(ctx, 2 * slot);
-    if (rc != AESW_OK) return rc;
-    rc = ensure_bounce(ctx, slot);
-    if (rc != AESW_OK) return rc;
-    struct SyncGuard {
-        aesw_ctx *c;
-        ~SyncGuard() { (void)hipStreamSynchronize(c->s_copy); (void)hipStreamSynchronize(c->s_compute); }
-    } sync_guard{ctx};
-    hipEvent_t ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};  // per stage: kernel start/end, copy start/end
-    struct EvGuard {
-        hipEvent_t (*e)[4];
-        ~EvGuard() { for (int i = 0; i < 2; ++i) for (int j = 0; j < 4; ++j) if (e[i][j]) (void)hipEventDestroy(e[i][j]); }
-    } evg{ev};
-    for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 4; ++j) HIP_TRY(ctx, hipEventCreate(&ev[i][j]));
-    // the caller's slabs were produced on some stream of theirs: they must be complete before this call (documented)
-    const uint32_t ncols = 3 * n_sets + 1;
-    aesw_stream_stats st = {};
-    const uint64_t t_begin = now_ns();
-    auto issue = [&](int s, uint32_t col) -> int {
-        AssembleParams q = p;
-        q.col_first = col;
-        q.col_count = 1;
-        q.out = ctx->scratch + (size_t)s * slot;
-        HIP_TRY(ctx, hipEventRecord(ev[s][0], ctx->s_compute));
-        HIP_TRY(ctx, launch_assemble(q, as_fr != 0, ctx->fr_nt, ctx->s_compute));
-        HIP_TRY(ctx, hipEventRecord(ev[s][1], ctx->s_compute));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_copy, ev[s][1], 0));
-        HIP_TRY(ctx, hipEventRecord(ev[s][2], ctx->s_copy));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->bounce[s], q.out, col_bytes, hipMemcpyDeviceToHost, ctx->s_copy));
-        HIP_TRY(ctx, hipEventRecord(ev[s][3], ctx->s_copy));
-        return AESW_OK;
-    };
-    uint32_t next = 0;
-    for (; next < 2 && next < ncols; ++next) {
-        rc = issue((int)next, next);
-        if (rc != AESW_OK) return rc;
-    }
-    for (uint32_t col = 0; col < ncols; ++col) {
-        const int s = (int)(col & 1);
-        const uint64_t t0 = now_ns();
-        HIP_TRY(ctx, hipEventSynchronize(ev[s][3]));
-        const uint64_t t1 = now_ns();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[s][0], ev[s][1]) == hipSuccess) st.kernel_ns += (uint64_t)(ms * 1e6);
-        if (hipEventElapsedTime(&ms, ev[s][2], ev[s][3]) == hipSuccess) st.d2h_ns += (uint64_t)(ms * 1e6);
-        const int r = consume(user, col, ctx->bounce[s], rows);
-        const uint64_t t2 = now_ns();
-        st.wait_ns += t1 - t0;
-        st.consumer_ns += t2 - t1;
-        st.chunks += 1;
-        st.bytes_to_host += col_bytes;
-        if (r != 0) { st.wall_ns = now_ns() - t_begin; ctx->stats = st; return AESW_ERR_MISMATCH; }
-        if (next < ncols) {
-            rc = issue(s, next++);
-            if (rc != AESW_OK) return rc;
-        }
-    }
-    st.wall_ns = now_ns() - t_begin;
-    ctx->stats = st;
-    return AESW_OK;
-}
-
-// The same columns straight into ONE host buffer (column after column): DMA directly when the buffer is page-locked
-// (aesw_host_alloc, or the host's own advice-polynomial memory after aesw_host_register), through the bounce buffers
-// otherwise.  Column j+1 is assembled while column j travels.
-int aesw_assemble_advice_host(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
-                              const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, int as_fr, uint8_t *out) {
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_assemble_advice_host");
-    if (!out) return AESW_ERR_INVALID_ARG;
-    AssembleParams p;
-    int rc = fill_assemble_params(ctx, k, n_sets, n_blocks, layout, d_x, d_y, d_z, ks, &p);
-    if (rc != AESW_OK) return rc;
-    if (k > 28) return AESW_ERR_INVALID_ARG;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    rc = ensure_streams(ctx);
-    if (rc != AESW_OK) return rc;
-    const uint64_t rows = (uint64_t)1 << k;
-    const size_t col_bytes = (size_t)rows * (as_fr ? AESW_FR_BYTES : 1);
-    const size_t slot = (col_bytes + 255) / 256 * 256;
-    const uint32_t ncols = 3 * n_sets + 1;
-    const bool direct = is_pinned(out) && is_pinned(out + (size_t)ncols * col_bytes - 1);
-    rc = ensure_scratch(ctx, 2 * slot);
-    if (rc != AESW_OK) return rc;
-    if (!direct) {
-        rc = ensure_bounce(ctx, slot);
-        if (rc != AESW_OK) return rc;
-    }
-    struct SyncGuard {
-        aesw_ctx *c;
-        ~SyncGuard() { (void)hipStreamSynchronize(c->s_copy); (void)hipStreamSynchronize(c->s_compute); }
-    } sync_guard{ctx};
-    hipEvent_t done[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *a, *b;
-        ~EvGuard() { for (int i = 0; i < 2; ++i) { if (a[i]) (void)hipEventDestroy(a[i]); if (b[i]) (void)hipEventDestroy(b[i]); } }
-    } evg{done, copied};
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&copied[i], hipEventDisableTiming));
-    }
-    bool busy[2] = {false, false};
-    uint32_t held[2] = {0, 0};
-    auto drain = [&](int s) -> int {  // the device slot (and bounce buffer) of stage s is free again after this
-        if (!busy[s]) return AESW_OK;
-        HIP_TRY(ctx, hipEventSynchronize(copied[s]));
-        if (!direct) parallel_copy({CopyJob{out + (size_t)held[s] * col_bytes, ctx->bounce[s], (size_t)col_bytes}}, auto_copy_threads(ctx));
-        busy[s] = false;
-        return AESW_OK;
-    };
-    for (uint32_t col = 0; col < ncols; ++col) {
-        const int s = (int)(col & 1);
-        rc = drain(s);
-        if (rc != AESW_OK) return rc;
-        AssembleParams q = p;
-        q.col_first = col;
-        q.col_count = 1;
-        q.out = ctx->scratch + (size_t)s * slot;
-        HIP_TRY(ctx, launch_assemble(q, as_fr != 0, ctx->fr_nt, ctx->s_compute));
-        HIP_TRY(ctx, hipEventRecord(done[s], ctx->s_compute));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_copy, done[s], 0));
-        HIP_TRY(ctx, hipMemcpyAsync(direct ? out + (size_t)col * col_bytes : ctx->bounce[s], q.out, col_bytes, hipMemcpyDeviceToHost, ctx->s_copy));
-        HIP_TRY(ctx, hipEventRecord(copied[s], ctx->s_copy));
-        // no stream wait on copied[s] here: the next launch goes into the OTHER slot and may run while this column travels;
-        // this slot is written again only after drain(s) has host-synchronised copied[s]
-        busy[s] = true;
-        held[s] = col;
-    }
-    rc = drain(0);
-    if (rc != AESW_OK) return rc;
-    return drain(1);
-}
-
-int aesw_host_register(void *p, size_t bytes) {
-    if (!p || !bytes) return AESW_ERR_INVALID_ARG;
-    if (hipHostRegister(p, bytes, hipHostRegisterDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return AESW_ERR_HIP;
-    }
-    return AESW_OK;
-}
-
-int aesw_host_unregister(void *p) {
-    if (!p) return AESW_ERR_INVALID_ARG;
-    if (hipHostUnregister(p) != hipSuccess) {
-        (void)hipGetLastError();
-        return AESW_ERR_HIP;
-    }
-    return AESW_OK;
-}
-
-int aesw_key_schedule_witness(aesw_ctx *ctx, const uint8_t *keys, uint64_t n, int layout, uint8_t *w, uint8_t *kx,
-                              uint8_t *ky, uint8_t *kz, uint8_t *rk) {
-    if (aesw_is_group(ctx)) return aesw_group_key_schedule_witness(ctx, keys, n, layout, w, kx, ky, kz, rk);
-    if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
-    if (n == 0) return AESW_OK;
-    if (!keys) return AESW_ERR_INVALID_ARG;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    const size_t kxs = aesw_key_column_stride(layout, 0), kys = aesw_key_column_stride(layout, 1),
-                 kzs = aesw_key_column_stride(layout, 2);
-    DevBuf dk, dw, dkx, dky, dkz, drk;
-    HIP_TRY(ctx, dk.alloc(n * 16));
-    if (w) HIP_TRY(ctx, dw.alloc(n * WORDS_ROWS));
-    if (kx) HIP_TRY(ctx, dkx.alloc(n * kxs));
-    if (ky) HIP_TRY(ctx, dky.alloc(n * kys));
-    if (kz) HIP_TRY(ctx, dkz.alloc(n * kzs));
-    if (rk) HIP_TRY(ctx, drk.alloc(n * RK_BYTES));
-    HIP_TRY(ctx, hipMemcpy(dk.p, keys, n * 16, hipMemcpyHostToDevice));
-    int rc = aesw_key_schedule_witness_device(ctx, dk.p, n, layout, w ? dw.p : nullptr, kx ? dkx.p : nullptr,
-                                              ky ? dky.p : nullptr, kz ? dkz.p : nullptr, rk ? drk.p : nullptr, nullptr);
-    if (rc != AESW_OK) return rc;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (w) HIP_TRY(ctx, hipMemcpy(w, dw.p, n * WORDS_ROWS, hipMemcpyDeviceToHost));
-    if (kx) HIP_TRY(ctx, hipMemcpy(kx, dkx.p, n * kxs, hipMemcpyDeviceToHost));
-    if (ky) HIP_TRY(ctx, hipMemcpy(ky, dky.p, n * kys, hipMemcpyDeviceToHost));
-    if (kz) HIP_TRY(ctx, hipMemcpy(kz, dkz.p, n * kzs, hipMemcpyDeviceToHost));
-    if (rk) HIP_TRY(ctx, hipMemcpy(rk, drk.p, n * RK_BYTES, hipMemcpyDeviceToHost));
-    return AESW_OK;
-}
-
-int aesw_check_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, int per_block_keys, uint64_t n, int layout, const uint8_t *x,
-                       const uint8_t *y, const uint8_t *z, const uint8_t *ct, const aesw_key_slab *ks, aesw_check_report *report) {
-    if (aesw_is_group(ctx)) return aesw_group_check_witness(ctx, pt, keys, per_block_keys, n, layout, x, y, z, ct, ks, report);
-    if (!ctx || !report || (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED)) return AESW_ERR_INVALID_ARG;
-    if (per_block_keys && n && !keys) return AESW_ERR_INVALID_ARG;
-    if (n && (!pt || !x || !y || !z || !ks || !ks->w || !ks->kx || !ks->ky || !ks->kz)) return AESW_ERR_INVALID_ARG;
-    *report = aesw_check_report{0, 0, 0, 0, 0, 0, AESW_CHECK_NONE};
-    if (n == 0) return AESW_OK;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    const CheckGeo cg = check_geo(layout);
-    const uint64_t chunk = (uint64_t)ctx->chunk_blocks < n ? (uint64_t)ctx->chunk_blocks : n;
-    const uint64_t nk = per_block_keys ? chunk : 1;
-    DevBuf dpt, dkeys, dx, dy, dz, dct, dw, dkx, dky, dkz, drep;
-    HIP_TRY(ctx, dpt.alloc(chunk * 16));
-    HIP_TRY(ctx, dkeys.alloc(nk * 16));
-    HIP_TRY(ctx, dx.alloc(chunk * cg.sx)); HIP_TRY(ctx, dy.alloc(chunk * cg.sy)); HIP_TRY(ctx, dz.alloc(chunk * cg.sz));
-    HIP_TRY(ctx, dct.alloc(chunk * 16));
-    HIP_TRY(ctx, dw.alloc(nk * WORDS_ROWS)); HIP_TRY(ctx, dkx.alloc(nk * cg.kxs)); HIP_TRY(ctx, dky.alloc(nk * cg.kys)); HIP_TRY(ctx, dkz.alloc(nk * cg.kzs));
-    HIP_TRY(ctx, drep.alloc(sizeof(aesw_check_report)));
-    const aesw_key_slab dks{dw.p, dkx.p, dky.p, dkz.p};
-    if (!per_block_keys) {  // the one key slab of the batch travels once
-        if (keys) HIP_TRY(ctx, hipMemcpy(dkeys.p, keys, 16, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dw.p, ks->w, WORDS_ROWS, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dkx.p, ks->kx, cg.kxs, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dky.p, ks->ky, cg.kys, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dkz.p, ks->kz, cg.kzs, hipMemcpyHostToDevice));
-    }
-    for (uint64_t lo = 0; lo < n; lo += chunk) {
-        const uint64_t m = n - lo < chunk ? n - lo : chunk;
-        HIP_TRY(ctx, hipMemcpy(dpt.p, pt + lo * 16, m * 16, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dx.p, x + lo * cg.sx, m * cg.sx, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dy.p, y + lo * cg.sy, m * cg.sy, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dz.p, z + lo * cg.sz, m * cg.sz, hipMemcpyHostToDevice));
-        if (ct) HIP_TRY(ctx, hipMemcpy(dct.p, ct + lo * 16, m * 16, hipMemcpyHostToDevice));
-        if (per_block_keys) {
-            HIP_TRY(ctx, hipMemcpy(dkeys.p, keys + lo * 16, m * 16, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(dw.p, ks->w + lo * WORDS_ROWS, m * WORDS_ROWS, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(dkx.p, ks->kx + lo * cg.kxs, m * cg.kxs, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(dky.p, ks->ky + lo * cg.kys, m * cg.kys, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(dkz.p, ks->kz + lo * cg.kzs, m * cg.kzs, hipMemcpyHostToDevice));
-        }
-        const int rc = check_witness_impl(ctx, dpt.p, (per_block_keys || keys) ? dkeys.p : nullptr, per_block_keys, m, layout, dx.p, dy.p, dz.p,
-                                          ct ? dct.p : nullptr, &dks, reinterpret_cast<aesw_check_report *>(drep.p), nullptr,
-                                          /* skip the shared key slab */ !per_block_keys && lo != 0);
-        if (rc != AESW_OK) return rc;
-        aesw_check_report r;
-        HIP_TRY(ctx, hipMemcpy(&r, drep.p, sizeof r, hipMemcpyDeviceToHost));  // (synchronises with the null stream's launch)
-        report->blocks += r.blocks; report->keys += r.keys;
-        report->lookup_failures += r.lookup_failures; report->copy_failures += r.copy_failures;
-        report->gate_failures += r.gate_failures; report->input_failures += r.input_failures;
-        if (r.first != AESW_CHECK_NONE) {
-            // units of a stage count from its first block (the shared key slab is unit 0 of the batch as well)
-            const uint64_t unit = (r.first >> 20) + ((!per_block_keys && ((r.first >> 19) & 1)) ? 0 : lo);
-            const uint64_t f = unit << 20 | (r.first & 0xfffffu);
-            if (f < report->first) report->first = f;
-        }
-    }
-    return AESW_OK;
-}
-
-int aesw_schedule_key(aesw_ctx *ctx, const uint8_t key[16], int layout, const aesw_key_slab *ks) {
-    if (aesw_is_group(ctx)) return aesw_group_schedule_key(ctx, key, layout, ks);
-    if (!ctx || !valid_layout(layout) || !key) return AESW_ERR_INVALID_ARG;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    const size_t kxs = aesw_key_column_stride(layout, 0), kys = aesw_key_column_stride(layout, 1),
-                 kzs = aesw_key_column_stride(layout, 2);
-    DevBuf dk, dw, dkx, dky, dkz;
-    HIP_TRY(ctx, dk.alloc(16));
-    HIP_TRY(ctx, dw.alloc(WORDS_ROWS)); HIP_TRY(ctx, dkx.alloc(kxs)); HIP_TRY(ctx, dky.alloc(kys)); HIP_TRY(ctx, dkz.alloc(kzs));
-    HIP_TRY(ctx, hipMemcpy(dk.p, key, 16, hipMemcpyHostToDevice));
-    aesw_key_slab dks{dw.p, dkx.p, dky.p, dkz.p};
-    int rc = aesw_schedule_key_device(ctx, dk.p, layout, ks ? &dks : nullptr, nullptr);
-    if (rc != AESW_OK) return rc;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (ks) {
-        if (ks->w) HIP_TRY(ctx, hipMemcpy(ks->w, dw.p, WORDS_ROWS, hipMemcpyDeviceToHost));
-        if (ks->kx) HIP_TRY(ctx, hipMemcpy(ks->kx, dkx.p, kxs, hipMemcpyDeviceToHost));
-        if (ks->ky) HIP_TRY(ctx, hipMemcpy(ks->ky, dky.p, kys, hipMemcpyDeviceToHost));
-        if (ks->kz) HIP_TRY(ctx, hipMemcpy(ks->kz, dkz.p, kzs, hipMemcpyDeviceToHost));
-    }
-    return AESW_OK;
-}
-
-void *aesw_host_alloc(size_t bytes) {
-    void *p = nullptr;
-    if (hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return p;
-}
-
-void aesw_host_free(void *p) {
-    if (p) (void)hipHostFree(p);
-}
-
-int aesw_lookup_table(aesw_ctx *ctx, uint8_t *t0, uint8_t *t1, uint8_t *t2, uint8_t *t3) {
-    if (aesw_is_group(ctx)) return aesw_group_lookup_table(ctx, t0, t1, t2, t3);
-    if (!ctx || !t0 || !t1 || !t2 || !t3) return AESW_ERR_INVALID_ARG;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return AESW_ERR_NO_DEVICE;
-    DevBuf d;
-    HIP_TRY(ctx, d.alloc(4 * (size_t)AESW_TABLE_ROWS));
-    uint8_t *p = d.p;
-    int rc = aesw_lookup_table_device(ctx, p, p + AESW_TABLE_ROWS, p + 2 * (size_t)AESW_TABLE_ROWS,
-                                      p + 3 * (size_t)AESW_TABLE_ROWS, nullptr);
-    if (rc != AESW_OK) return rc;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    uint8_t *outs[4] = {t0, t1, t2, t3};
-    for (int i = 0; i < 4; ++i)
-        HIP_TRY(ctx, hipMemcpy(outs[i], p + i * (size_t)AESW_TABLE_ROWS, AESW_TABLE_ROWS, hipMemcpyDeviceToHost));
     return AESW_OK;
 }
 

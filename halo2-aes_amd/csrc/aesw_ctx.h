@@ -1,5 +1,7 @@
 // aesw_ctx.h -- the opaque context of include/aesw.h and the small helpers every translation unit of the C ABI uses
-// (aesw_api.cpp: entry points; aesw_arena.cpp: the probed column arena).  Not part of the public ABI.
+// (aesw_api.cpp: context, options and the device-pointer entry points; aesw_hostpath.cpp: the host-pointer entry points and their
+// two-stage pipeline; aesw_arena.cpp: the probed column arena; aesw_group.cpp: device groups; aesw_circuits.cpp: many circuits per
+// launch), and the few internal functions one of them takes from another.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -113,7 +115,7 @@ struct aesw_ctx {
     int group_size = 1;  // of a MEMBER: the members of its group (its automatic "copy_threads" is its share of the CPUs)
 };
 
-// aesw_group.cpp: what the entry points of aesw_api.cpp hand a group context to (a short branch at their top)
+// aesw_group.cpp: what the entry points of aesw_api.cpp and aesw_hostpath.cpp hand a group context to (a short branch at their top)
 inline bool aesw_is_group(const aesw_ctx *ctx) { return ctx && !ctx->members.empty(); }
 int aesw_group_refuse(aesw_ctx *group, const char *entry);  // AESW_ERR_INVALID_ARG: device pointers belong to one GPU
 void aesw_group_destroy(aesw_ctx *group);
@@ -160,3 +162,16 @@ struct DeviceGuard {
 void aesw_arena_cache_trim(aesw_ctx *ctx, uint64_t keep_bytes);  // aesw_arena.cpp: release cached arenas, oldest first, until keep_bytes stay
 
 inline bool aesw_valid_layout(int l) { return l == AESW_LAYOUT_DENSE || l == AESW_LAYOUT_PACKED || l == AESW_LAYOUT_VALUES; }
+
+// What aesw_hostpath.cpp takes from aesw_api.cpp, and the one thing aesw_get_option takes back.  Internal: not in the dynamic symbol table.
+#define AESW_INTERNAL __attribute__((visibility("hidden")))
+namespace aesw { struct AssembleParams; }
+AESW_INTERNAL int key_track_reader(aesw_ctx *ctx, aesw_ctx::KeySlot &sl, hipStream_t s);  // a launch on `s` reads round-key slot `sl`
+// the argument checks of the assemble entry points and the launch parameters of all 3 n_sets + 1 columns
+AESW_INTERNAL int fill_assemble_params(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
+                                       const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, aesw::AssembleParams *p);
+// aesw_check_witness_device, optionally without the shared key slab (a later chunk of a host-pointer call)
+AESW_INTERNAL int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys, uint64_t n, int layout,
+                                     const uint8_t *d_x, const uint8_t *d_y, const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *ks,
+                                     aesw_check_report *d_report, void *stream, bool skip_shared_key);
+AESW_INTERNAL int auto_copy_threads(const aesw_ctx *ctx);  // aesw_hostpath.cpp: what "copy_threads" resolves to ("effective_copy_threads")

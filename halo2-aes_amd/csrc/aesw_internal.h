@@ -1,5 +1,6 @@
 // aesw_internal.h -- kernel parameter blocks and launchers shared by
-// aesw_kernels.hip and aesw_api.cpp (not part of the public ABI).
+// aesw_kernels.hip and the host code that launches them (aesw_api.cpp,
+// aesw_hostpath.cpp; not part of the public ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -49,6 +49,20 @@ def test_python_tools_parse_and_use_names_that_exist(pkg):
     assert not problems, "\n".join(problems)
 
 
+def test_tools_take_the_product_sources_from_the_build_module():
+    """A tool that builds a private variant of the library uses _build.PRODUCT_SOURCES: no list of its own to fall behind."""
+    spec = importlib.util.spec_from_file_location("build_mod", ROOT / "halo2-aes_amd" / "_build.py")
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    csrc = ROOT / "halo2-aes_amd" / "csrc"
+    on_disk = sorted(p.name for p in csrc.iterdir() if p.suffix in (".cpp", ".hip"))
+    assert sorted(p.name for p in build.PRODUCT_SOURCES) == on_disk
+    assert all(p.exists() for p in build.PRODUCT_HEADERS)
+    scripts = sorted(TOOLS.glob("*.py")) + sorted(TOOLS.glob("*.sh"))
+    named = ["%s names %s" % (path.name, src) for path in scripts for src in on_disk if src in path.read_text()]
+    assert not named, "\n".join(named)
+
+
 def _syntax_only(path: Path):
     inc = ["-I", str(ROOT / "include"), "-I", str(ROOT / "halo2-aes_amd" / "csrc"), "-I", "/opt/rocm/include"]
     if path.suffix == ".hip":

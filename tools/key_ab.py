@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """key_kernel A/B in ONE process: the in-tree library against tools/libaesw_kz8.so (the same source built with -DAESW_KZ_PER_KEY:
 packed kz flushed as per-key 8-byte pieces, as up to round 3), 2^20 keys into the same probed key-only arena, interleaved rounds.
-Build the variant first:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -pthread -DAESW_KZ_PER_KEY -o tools/libaesw_kz8.so
-halo2-aes_amd/csrc/aesw_kernels.hip halo2-aes_amd/csrc/aesw_api.cpp halo2-aes_amd/csrc/aesw_arena.cpp halo2-aes_amd/csrc/aesw_comm.cpp"""
+The variant is built on first use (`key_ab.py build` builds it and stops)."""
 import ctypes as C
 import statistics
 import sys
@@ -12,13 +11,16 @@ sys.path.insert(0, str(ROOT))
 import torch  # noqa: E402
 import __graft_entry__ as ge  # noqa: E402
 ge.build()
+KZ8 = ge._load_build().build_product(extra_flags=["-DAESW_KZ_PER_KEY"], out=ROOT / "tools" / "libaesw_kz8.so")
+if sys.argv[1:] == ["build"]:
+    sys.exit(0)
 pkg = ge.load_package()
 nk = 1 << 20
 keys = torch.randint(0, 256, (nk, 16), dtype=torch.uint8, device="cuda")
 ctx = pkg.Context(0)
 ka = ctx.alloc_columns(nk, pkg.LAYOUT_PACKED, key_slab=True, key_only=True)
 print("arena", ctx.last_arena)
-other = C.CDLL(str(ROOT / "tools" / "libaesw_kz8.so"))
+other = C.CDLL(str(KZ8))
 for name in ("aesw_create", "aesw_key_schedule_witness_device"):
     res, args = pkg.api.SYMBOLS[name]
     getattr(other, name).restype, getattr(other, name).argtypes = res, args

@@ -4,20 +4,16 @@ store_mode 2 = the product kernel, 3 = compute + staging without the flush, 4 = 
 5 = stores only.  usage: parts.py [c1|c2] [LOG2N] [lds_pad ...]"""
 import ctypes as C
 import statistics
-import subprocess
 import sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 DIAG = ROOT / "tools" / "libaesw_diag.so"
-if not DIAG.exists():
-    csrc = ROOT / "halo2-aes_amd" / "csrc"
-    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DAESW_DIAGNOSTIC", "-o", str(DIAG),
-                           str(csrc / "aesw_kernels.hip"), str(csrc / "aesw_api.cpp"), str(csrc / "aesw_arena.cpp"), str(csrc / "aesw_comm.cpp")])
+import __graft_entry__ as ge  # noqa: E402
+ge._load_build().build_product(extra_flags=["-DAESW_DIAGNOSTIC"], out=DIAG)
 if "--build-only" in sys.argv:
     sys.exit(0)
 import torch  # noqa: E402
-import __graft_entry__ as ge  # noqa: E402
 ge.build()
 pkg = ge.load_package()
 import bench  # noqa: E402

@@ -6,7 +6,8 @@
 set -eu
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
-SRC="halo2-aes_amd/csrc/aesw_kernels.hip halo2-aes_amd/csrc/aesw_api.cpp halo2-aes_amd/csrc/aesw_arena.cpp halo2-aes_amd/csrc/aesw_comm.cpp halo2-aes_amd/host/host_capi.cpp"
+# the product's sources (one list: halo2-aes_amd/_build.py) and the C++ mirror above them
+SRC="$(python3 -B -c 'import sys; sys.path.insert(0, "halo2-aes_amd"); import _build; print(*_build.PRODUCT_SOURCES)') halo2-aes_amd/host/host_capi.cpp"
 if [ ! -f tools/libaesw_asan.so ] || [ -n "$(find $SRC halo2-aes_amd/csrc/*.h halo2-aes_amd/host/*.hpp -newer tools/libaesw_asan.so)" ]; then
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
         -Xarch_host -fno-omit-frame-pointer -Xarch_host -g -o tools/libaesw_asan.so $SRC

@@ -16,12 +16,8 @@ import __graft_entry__ as ge  # noqa: E402
 ge.build()
 pkg = ge.load_package()
 b = ge._load_build()
-lib_path = ROOT / "tools" / "libaesw_trace.so"
-csrc, host = ROOT / "halo2-aes_amd" / "csrc", ROOT / "halo2-aes_amd" / "host"
-srcs = [csrc / "aesw_kernels.hip", csrc / "aesw_api.cpp", csrc / "aesw_arena.cpp", host / "host_capi.cpp"]
-if not b._newer(lib_path, srcs + [csrc / "aesw_lane.h", csrc / "aesw_layout.h", csrc / "aesw_internal.h"]):
-    b._run([b.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DAESW_TRACE",
-            "-o", str(lib_path)] + [str(s) for s in srcs])
+lib_path = b.build_product(extra_flags=["-DAESW_TRACE"], out=ROOT / "tools" / "libaesw_trace.so",
+                           extra_sources=[ROOT / "halo2-aes_amd" / "host" / "host_capi.cpp"])
 if len(sys.argv) > 1 and sys.argv[1] == "build":
     sys.exit(0)
 pkg.api._lib = pkg.api.load_library(lib_path)
