@@ -3,6 +3,8 @@
   halo2-aes_amd/libaesw.so        HIP kernels + the C ABI of include/aesw.h (hipcc --offload-arch=gfx950)
   halo2-aes_amd/libaesw_host.so   the C++ mirror of the reference's host interface (include/aesw_host.h): plain g++,
                                   no device code, linked against libaesw.so -- it only calls the C ABI
+  halo2-aes_amd/libaesw_circ.so   the many-circuit witness checker of include/aesw_circ.h: one more gfx950 kernel and its
+                                  entry point (hipcc), linked against libaesw.so, whose context it takes
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -20,6 +22,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libaesw.so"
 HOST_LIB = PKG / "libaesw_host.so"
+CIRC_LIB = PKG / "libaesw_circ.so"
 
 
 def _newer(target: Path, sources) -> bool:
@@ -69,8 +72,35 @@ def build_host(force: bool = False) -> Path:
 # key_ab.py, sanitize.sh) take it from here.
 PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp", "aesw_comm.cpp",
                                       "aesw_group.cpp", "aesw_circuits.cpp")]
-PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_check.h", "aesw_internal.h", "aesw_ctx.h")] + \
+PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h")] + \
     [ROOT / "include" / "aesw.h"]
+
+
+# csrc/ itself holds exactly the sources of libaesw.so (PRODUCT_SOURCES); the second library's live one level down
+CIRC_SOURCES = [CSRC / "circ" / "aesw_circ_check.hip"]
+CIRC_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_circ_search.h", "aesw_check.h", "aesw_layout.h", "aesw_internal.h", "aesw_ctx.h")] + \
+    [ROOT / "include" / "aesw.h", ROOT / "include" / "aesw_circ.h"]
+
+
+def build_circ(force: bool = False) -> Path:
+    """libaesw_circ.so: the many-circuit checker kernel and its entry point (hipcc, gfx950), NEEDED libaesw.so found next to it
+    ($ORIGIN).  A library of its own: the set of kernels inside libaesw.so stays what it is."""
+    deps = CIRC_SOURCES + CIRC_HEADERS + [LIB]
+    if not force and _newer(CIRC_LIB, deps):
+        return CIRC_LIB
+    import fcntl
+    with open(PKG / ".build.lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if not force and _newer(CIRC_LIB, deps):
+                return CIRC_LIB
+            tmp = CIRC_LIB.with_suffix(".so.tmp%d" % os.getpid())
+            _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-o", str(tmp)] +
+                 [str(s) for s in CIRC_SOURCES] + ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"])
+            os.replace(tmp, CIRC_LIB)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return CIRC_LIB
 
 
 def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_sources=()) -> Path:

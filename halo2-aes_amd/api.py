@@ -19,6 +19,7 @@ from . import constants as K
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libaesw.so"            # HIP kernels + the C ABI of include/aesw.h
 HOST_LIB_PATH = _PKG / "libaesw_host.so"  # C++ mirror of the reference's host interface (include/aesw_host.h), above the C ABI
+CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
     0: "AESW_OK", 1: "AESW_ERR_INVALID_ARG", 2: "AESW_ERR_NO_DEVICE", 3: "AESW_ERR_HIP", 4: "AESW_ERR_NOMEM",
@@ -64,6 +65,11 @@ class CheckReport(C.Structure):
     """aesw_check_report: what aesw_check_witness_device found."""
     _fields_ = [("blocks", C.c_uint64), ("keys", C.c_uint64), ("lookup_failures", C.c_uint64), ("copy_failures", C.c_uint64),
                 ("gate_failures", C.c_uint64), ("input_failures", C.c_uint64), ("first", C.c_uint64)]
+
+
+class CircCheckReport(C.Structure):
+    """aesw_circ_check_report: what aesw_circ_check_witness_device found."""
+    _fields_ = CheckReport._fields_ + [("offset_failures", C.c_uint64)]
 
 
 class _DevView:
@@ -159,8 +165,36 @@ HOST_SYMBOLS = {
     "aesw_host_last_error": (C.c_char_p, []),
 }
 
+# include/aesw_circ.h
+CIRC_SYMBOLS = {
+    "aesw_circ_check_witness_device": (_I, [_P, _U32, _U32, _U32, _P, _U64, _P, _P, _I, _P, _P, _P, _P, C.POINTER(KeySlab), _P, _P]),
+    "aesw_circ_circuit_of_block": (_U32, [_P, _U32, _U64]),
+}
+
 _lib = None
 _host_lib = None
+_circ_lib = None
+
+
+def load_circ_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_circ.so (in-tree): the many-circuit checker.  It links against libaesw.so, whose contexts it takes; a missing
+    library is an error, there is no other implementation of Context.check_circuits."""
+    global _circ_lib
+    if _circ_lib is not None and path is None:
+        return _circ_lib
+    load_library()  # libaesw.so first: the NEEDED entry resolves to the copy already mapped
+    p = Path(path) if path else CIRC_LIB_PATH
+    if not p.exists():
+        raise FileNotFoundError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                "(hipcc --offload-arch=gfx950). There is no fallback implementation." % p)
+    lib = C.CDLL(str(p))
+    for name, (res, args) in CIRC_SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if path is None:
+        _circ_lib = lib
+    return lib
 
 
 def load_host_library(path: Path | None = None) -> C.CDLL:
@@ -287,6 +321,15 @@ def circuit_offsets(k: int, n_sets: int, counts, n: int) -> np.ndarray:
     return offs
 
 
+def circuit_of_block(offsets, b: int) -> int:
+    """aesw_circ_circuit_of_block: the circuit the many-circuit checker holds block b against (the kernel's own search, run on
+    the host); offsets: C+1 block offsets.  In [0, C) whatever the offsets hold."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if offs.ndim != 1 or offs.size < 2:
+        raise ValueError("offsets must hold C + 1 entries for C >= 1 circuits")
+    return int(load_circ_library().aesw_circ_circuit_of_block(_np_ptr(offs), offs.size - 1, int(b)))
+
+
 def selector_tags():
     """(enc_tag[1360], key_tag[400], q_eq_rcon[96], rcon_fixed[96]): fixed selector data for keygen."""
     e, k = np.zeros(K.AES_ROWS, np.uint8), np.zeros(K.KEY_ROWS, np.uint8)
@@ -367,6 +410,14 @@ def host_free(arr: np.ndarray):
 
 
 _pinned = {}
+
+
+def circ_report_dict(rep) -> dict:
+    """The uint64[8] report tensor of Context.check_circuits(sync=False), read back, as the dict sync=True returns."""
+    v = [int(x) & 0xFFFFFFFFFFFFFFFF for x in rep.cpu().tolist()]
+    first = None if v[6] == 0xFFFFFFFFFFFFFFFF else (v[6] >> 20, bool((v[6] >> 19) & 1), (v[6] >> 16) & 7, v[6] & 0xFFFF)
+    return {"blocks": v[0], "keys": v[1], "lookup_failures": v[2], "copy_failures": v[3], "gate_failures": v[4], "input_failures": v[5],
+            "first": first, "offset_failures": v[7], "satisfied": not any(v[2:6]) and v[7] == 0}
 
 Witness = namedtuple("Witness", "x y z ct key")
 KeyWitness = namedtuple("KeyWitness", "w kx ky kz rk")
@@ -759,6 +810,42 @@ class Context:
         self._check(rc, "aesw_assemble_advice_circuits_device")
         return out
 
+    def check_circuits(self, k: int, n_sets: int, pt, keys, witness: Witness, key_witness: KeyWitness, counts, layout: int = K.LAYOUT_PACKED,
+                       ct=None, sync: bool = True, _offsets=None):
+        """MockProver::assert_satisfied over C FixedAes128Config<k, n_sets> circuits in one launch (aesw_circ_check_witness_device,
+        libaesw_circ.so): block b of `witness` against the lookups, its copies resolved in key slab circuit(b) of `key_witness`, its
+        literal rows against pt (uint8[n,16]) and ct (uint8[n,16] or None); every one of the C key slabs, and its key bytes when
+        keys (uint8[C,16] or None) is given; and the offsets themselves.  counts: blocks per circuit, validated on the host like
+        assemble_advice_circuits; _offsets: a device int64[C+1] tensor passed through unvalidated instead (counts then only gives C).
+        Returns the dict of check_witness plus `offset_failures` (`satisfied` also needs that to be 0; a key slab's unit is its
+        circuit) after synchronising the stream; with sync=False the uint64[8] device tensor the report was written to."""
+        lib = load_circ_library()
+        torch = self._torch()
+        pt = self._u8(pt, "pt")
+        n = int(pt.shape[0])
+        nc = len(counts)
+        if _offsets is None:
+            d_offs = self._offsets_tensor(circuit_offsets(k, n_sets, counts, n))
+        else:
+            d_offs = _offsets
+            if int(d_offs.numel()) != nc + 1:
+                raise ValueError("_offsets must hold len(counts) + 1 entries")
+        if keys is not None and tuple(self._u8(keys, "keys").shape) != (nc, 16):
+            raise ValueError("keys must be [C,16] for C = len(counts)")
+        if key_witness is None or int(key_witness.w.numel()) < nc * K.WORDS_ROWS:
+            raise ValueError("key_witness must hold one key slab per circuit")
+        ks = KeySlab(*[self._u8(t, "key_witness").data_ptr() for t in key_witness[:4]])
+        rep = torch.empty(8, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_circ_check_witness_device(
+            self._h, k, n_sets, nc, d_offs.data_ptr(), n, pt.data_ptr() if n else None, keys.data_ptr() if keys is not None else None, layout,
+            witness.x.data_ptr() if n else None, witness.y.data_ptr() if n else None, witness.z.data_ptr() if n else None,
+            ct.data_ptr() if ct is not None and n else None, C.byref(ks), rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_circ_check_witness_device")
+        if not sync:
+            return rep
+        torch.cuda.current_stream().synchronize()
+        return circ_report_dict(rep)
+
     def circuits(self, k: int, n_sets: int, keys, pt, counts, as_fr: bool = True):
         """C FixedAes128Config<k, n_sets> circuits on torch's current stream: the key schedule of keys (uint8[C,16]), the
         witness of pt (uint8[n,16]; circuit c takes the next counts[c] blocks) with each block under its circuit's key, and
@@ -972,7 +1059,7 @@ class Group(Context):
 # the device-tensor methods of Context (the C ABI refuses them on a group as well)
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
-              "assemble_advice_host", "assemble_advice_circuits", "circuits"):
+              "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
