@@ -70,15 +70,17 @@ def build_host(force: bool = False) -> Path:
 
 # The one list of what libaesw.so is made of: tools that build a private variant of the library (tools/trace.py, parts.py,
 # key_ab.py, sanitize.sh) take it from here.
-PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp", "aesw_comm.cpp",
-                                      "aesw_group.cpp", "aesw_circuits.cpp")]
-PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h")] + \
+PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_keyring.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp",
+                                      "aesw_comm.cpp", "aesw_group.cpp", "aesw_circuits.cpp")]
+PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h",
+                                      "aesw_keyring.h")] + \
     [ROOT / "include" / "aesw.h"]
 
 
 # csrc/ itself holds exactly the sources of libaesw.so (PRODUCT_SOURCES); the second library's live one level down
 CIRC_SOURCES = [CSRC / "circ" / "aesw_circ_check.hip"]
-CIRC_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_circ_search.h", "aesw_check.h", "aesw_layout.h", "aesw_internal.h", "aesw_ctx.h")] + \
+CIRC_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_circ_search.h", "aesw_check.h", "aesw_layout.h", "aesw_internal.h", "aesw_ctx.h",
+                                   "aesw_keyring.h")] + \
     [ROOT / "include" / "aesw.h", ROOT / "include" / "aesw_circ.h"]
 
 

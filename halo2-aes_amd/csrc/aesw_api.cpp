@@ -84,109 +84,6 @@ static void vmm_release_arena(void *va, size_t total) {
     (void)hipMemAddressFree(va, total);
 }
 
-// ---- the scheduled key's round-key slots (aesw_ctx.h) ----------------------------------------------------------
-namespace {
-constexpr size_t KEY_CHUNK_SLOTS = 16, KEY_SLOT_BYTES = 256, KEY_MAX_READERS = 16;
-
-bool stream_capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    return cs != hipStreamCaptureStatusNone;
-}
-
-// Both streams are being captured into the SAME graph (one forked from the other with an event, like the internal streams of
-// the batch entry point from the caller's).
-bool same_capture(hipStream_t a, hipStream_t b) {
-    hipStreamCaptureStatus sa = hipStreamCaptureStatusNone, sb = hipStreamCaptureStatusNone;
-    unsigned long long ia = 0, ib = 0;
-    if (hipStreamGetCaptureInfo(a, &sa, &ia) != hipSuccess || hipStreamGetCaptureInfo(b, &sb, &ib) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return sa == hipStreamCaptureStatusActive && sb == hipStreamCaptureStatusActive && ia == ib;
-}
-
-// While some stream of this thread is being captured (global mode), allocation calls are refused: run them relaxed.
-struct RelaxedCapture {
-    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-    bool on;
-    RelaxedCapture() { on = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess; if (!on) (void)hipGetLastError(); }
-    ~RelaxedCapture() { if (on && hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) (void)hipGetLastError(); }
-};
-
-// A slot nobody has used yet (fresh memory; a new chunk every KEY_CHUNK_SLOTS slots).
-int key_new_slot(aesw_ctx *ctx, int *out) {
-    RelaxedCapture relaxed;
-    const size_t used = ctx->key_slots.size();
-    if (used == ctx->key_chunks.size() * KEY_CHUNK_SLOTS) {
-        uint8_t *c = nullptr;
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&c), KEY_CHUNK_SLOTS * KEY_SLOT_BYTES));
-        ctx->key_chunks.push_back(c);
-    }
-    aesw_ctx::KeySlot sl;
-    sl.d = ctx->key_chunks.back() + (used % KEY_CHUNK_SLOTS) * KEY_SLOT_BYTES;
-    HIP_TRY(ctx, hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
-    ctx->key_slots.push_back(sl);
-    *out = (int)used;
-    return AESW_OK;
-}
-
-// The slot an un-captured schedule writes next: the ring's next slot (spare slots and fresh ones fill the ring up to
-// "key_slots"; a slot a capture has pinned meanwhile is replaced).  The caller waits for the slot's readers.
-int key_next_ring_slot(aesw_ctx *ctx, int *out) {
-    auto &ring = ctx->key_ring_slots;
-    while ((int)ring.size() > ctx->key_ring) { ctx->key_spare.push_back(ring.back()); ring.pop_back(); }
-    auto take = [&](int *idx) -> int {
-        while (!ctx->key_spare.empty()) {
-            const int i = ctx->key_spare.back();
-            ctx->key_spare.pop_back();
-            if (!ctx->key_slots[i].pinned) { *idx = i; return AESW_OK; }
-        }
-        return key_new_slot(ctx, idx);
-    };
-    if ((int)ring.size() < ctx->key_ring) {
-        int idx = -1;
-        const int rc = take(&idx);
-        if (rc != AESW_OK) return rc;
-        ring.push_back(idx);
-        ctx->key_pos = (int)ring.size() - 1;
-    } else {
-        ctx->key_pos = (ctx->key_pos + 1) % (int)ring.size();
-        if (ctx->key_slots[ring[ctx->key_pos]].pinned) {
-            int idx = -1;
-            const int rc = take(&idx);
-            if (rc != AESW_OK) return rc;
-            ring[ctx->key_pos] = idx;
-        }
-    }
-    *out = ring[ctx->key_pos];
-    return AESW_OK;
-}
-
-}  // namespace
-
-// An un-captured launch on `s` reads slot `sl`: the schedule that reuses the slot will wait for it.  One event per distinct
-// stream: a stream's later record is ordered behind its earlier launches, so re-recording loses nobody.  (Declared in
-// aesw_ctx.h: the streaming entry point of aesw_hostpath.cpp reads the slot of a scheduled key on the context's own stream.)
-int key_track_reader(aesw_ctx *ctx, aesw_ctx::KeySlot &sl, hipStream_t s) {
-    for (auto &r : sl.readers)
-        if (r.s == s) { HIP_TRY(ctx, hipEventRecord(r.e, s)); return AESW_OK; }
-    if (sl.readers.size() >= KEY_MAX_READERS) {
-        // fold the oldest reader into this stream: `s` waits for it BEHIND the launch just issued, so the event recorded
-        // next on `s` stands for both
-        HIP_TRY(ctx, hipStreamWaitEvent(s, sl.readers.front().e, 0));
-        ctx->event_pool.push_back(sl.readers.front().e);
-        sl.readers.erase(sl.readers.begin());
-    }
-    hipEvent_t e = nullptr;
-    if (!ctx->event_pool.empty()) { e = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
-    else HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const hipError_t rc = hipEventRecord(e, s);
-    if (rc != hipSuccess) { ctx->event_pool.push_back(e); return fail_hip(ctx, rc, "hipEventRecord(key reader)"); }
-    sl.readers.push_back(aesw_ctx::KeyReader{s, e});
-    return AESW_OK;
-}
-
 // Waves per group when the option is 0 (auto): as many 16-block waves as keep
 // 6-8 waves resident per CU given the LDS windows (DESIGN.md "occupancy").
 static int auto_waves(const aesw_ctx *ctx, int layout, bool pbk) {
@@ -262,6 +159,118 @@ int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys
     HIP_TRY(ctx, launch_check(p, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;
 }
+
+// ---- one encrypt launch, and the internal streams several of them are dealt onto ----------------------------------
+namespace {
+
+// One aesw_encrypt_witness_device call whose arguments have passed validate_encrypt
+struct EncLaunch {
+    const uint8_t *d_pt, *d_keys;
+    int per_block_keys;
+    uint64_t n;
+    int layout;
+    uint8_t *d_x, *d_y, *d_z, *d_ct;
+    KeyOut ko;
+    bool kemit;  // a key slab is wanted
+};
+
+// The argument checks of aesw_encrypt_witness_device, statuses in this order.  True: *L is a launch to issue.  False: there is none,
+// and *status is what the call returns (an error, or AESW_OK for n == 0).
+bool validate_encrypt(const aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys, uint64_t n, int layout, uint8_t *d_x,
+                     uint8_t *d_y, uint8_t *d_z, uint8_t *d_ct, const aesw_key_slab *ks, EncLaunch *L, int *status) {
+    *status = AESW_ERR_INVALID_ARG;
+    if (!ctx || !valid_layout(layout)) return false;
+    if (!d_keys) {
+        if (per_block_keys) return false;
+        if (!ctx->keys.has_key()) { *status = AESW_ERR_NO_KEY; return false; }  // "Keys should be scheduled", src/aes128.rs:170
+    }
+    *L = EncLaunch{d_pt, d_keys, per_block_keys, n, layout, d_x, d_y, d_z, d_ct, KeyOut{nullptr, nullptr, nullptr, nullptr}, false};
+    *status = AESW_OK;
+    if (n == 0) return false;
+    *status = AESW_ERR_INVALID_ARG;
+    const bool has_x = aesw_column_stride(layout, 0) != 0;  // AESW_LAYOUT_VALUES has no x column: d_x is ignored
+    if (!d_pt || (has_x && !d_x) || !d_y || !d_z) return false;
+    if ((has_x && !aligned16(d_x)) || !aligned16(d_y) || !aligned16(d_z) || !aligned4(d_pt) || (d_keys && !aligned4(d_keys)) ||
+        (d_ct && !aligned4(d_ct)))
+        return false;
+    if (!key_out_of(ks, &L->ko)) return false;
+    L->kemit = L->ko.w || L->ko.kx || L->ko.ky || L->ko.kz;
+    if (!d_keys && L->kemit) return false;  // the key slab of a scheduled key comes from aesw_schedule_key*
+    *status = AESW_OK;
+    return true;
+}
+
+// One validated launch (n > 0) on one stream: the shared key's slab, the order behind a scheduled key, the kernel, the reader's mark.
+// The caller holds the DeviceGuard.
+int enqueue_encrypt(aesw_ctx *ctx, const EncLaunch &L, hipStream_t s) {
+    if (!L.per_block_keys && L.kemit) {
+        // shared key: its schedule witness is one key slab
+        KeyParams kp{L.d_keys, ctx->d_tables, L.ko, nullptr, 1, 0, 0};
+        HIP_TRY(ctx, launch_key(kp, L.layout, ctx->xt, 1, ctx->key_nt, 0u, s));
+    }
+    const int km = L.per_block_keys ? 0 : (L.d_keys ? 1 : 2);
+    KeyRing::Access rd;
+    if (km == 2) {  // capture status is asked for scheduled-key launches only: the other key modes make no runtime call but the launch
+        const int rc = ctx->keys.begin_read(ctx, s, &rd);
+        if (rc != AESW_OK) return rc;
+    }
+    EncParams p{L.d_pt, L.d_keys, reinterpret_cast<const uint32_t *>(rd.d), ctx->d_tables, ctx->d_ftab[L.layout], L.d_x, L.d_y, L.d_z, L.d_ct,
+                L.per_block_keys ? L.ko : KeyOut{nullptr, nullptr, nullptr, nullptr}, L.n, 0, 0};
+#ifdef AESW_TRACE
+    p.trace = ctx->trace;
+#endif
+    HIP_TRY(ctx, launch_encrypt(p, L.layout, ctx->xt, km, L.per_block_keys && L.kemit, auto_waves(ctx, L.layout, L.per_block_keys != 0),
+                                ctx->nt, (uint32_t)ctx->grid_cap, ctx->xcd_remap, (uint32_t)ctx->lds_pad, s));
+    return km == 2 ? ctx->keys.end_read(ctx, rd) : AESW_OK;  // this launch reads the current slot: nothing may overwrite the slot under it
+}
+
+// Fork / join of the internal streams: `ns` of them (at most 8, made on first use) start behind what `s` holds, issue(i, stream)
+// puts item i of `count` on internal stream i mod ns until one fails, and `s` continues behind all of them -- also after a failure:
+// what was issued must be ordered before whatever the caller does next on `s`.
+template <class Issue>
+int fork_join(aesw_ctx *ctx, hipStream_t s, uint32_t ns, uint32_t count, Issue &&issue) {
+    if (!ctx->ev_fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    for (uint32_t j = 0; j < ns; ++j) {
+        if (!ctx->s_batch[j]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->s_batch[j], hipStreamNonBlocking));
+        if (!ctx->ev_join[j]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join[j], hipEventDisableTiming));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
+    for (uint32_t j = 0; j < ns; ++j) HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_batch[j], ctx->ev_fork, 0));
+    int rc = AESW_OK;
+    for (uint32_t i = 0; i < count && rc == AESW_OK; ++i) rc = issue(i, ctx->s_batch[i % ns]);
+    for (uint32_t j = 0; j < ns; ++j) {
+        const hipError_t e1 = hipEventRecord(ctx->ev_join[j], ctx->s_batch[j]);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, ctx->ev_join[j], 0) : e1;
+        if (e2 != hipSuccess && rc == AESW_OK) rc = fail_hip(ctx, e2, "join of the batch streams");
+    }
+    return rc;
+}
+
+// A LONE launch on the caller's stream: aesw_encrypt_witness_device (the chunks of the host-pointer paths come through it), and the
+// batches of the batch entry point when it has one stream or one batch.  Only here does "split_small" apply.
+int encrypt_lone(aesw_ctx *ctx, const EncLaunch &L, hipStream_t s) {
+    if (ctx->split_small <= 1 || L.per_block_keys || L.kemit || L.n < ((uint64_t)1 << 15) || L.n > ((uint64_t)1 << 17)) return enqueue_encrypt(ctx, L, s);
+    // "split_small": the lone small batch as 2-3 sub-launches on the internal streams.  Sub-ranges are multiples of 48 blocks -- whole
+    // 3-wave groups, and 48 x 1360 / 1056 / 608 are multiples of the 128-byte line, so no two sub-launches share a line of any column.
+    // A split uses as many internal streams as it has parts (at most 8, at least 2 for these n), whatever "batch_streams" says.
+    const uint32_t parts = (uint32_t)ctx->split_small;
+    const uint64_t per = ((L.n + parts - 1) / parts + 47) / 48 * 48;
+    const uint32_t cnt = (uint32_t)((L.n + per - 1) / per);
+    const uint64_t sx = aesw_column_stride(L.layout, 0), sy = aesw_column_stride(L.layout, 1), sz = aesw_column_stride(L.layout, 2);
+    return fork_join(ctx, s, cnt, cnt, [&](uint32_t i, hipStream_t si) {
+        const uint64_t lo = i * per;
+        EncLaunch part = L;
+        part.d_pt += lo * 16;
+        part.n = L.n - lo < per ? L.n - lo : per;
+        if (L.d_x) part.d_x += lo * sx;
+        part.d_y += lo * sy;
+        part.d_z += lo * sz;
+        if (L.d_ct) part.d_ct += lo * 16;
+        return enqueue_encrypt(ctx, part, si);
+    });
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -343,7 +352,7 @@ int aesw_create(aesw_ctx **out, int device, const uint8_t sbox[256], const uint8
         T(hipMalloc(reinterpret_cast<void **>(&ctx->d_chktab[li]), ct.size() * sizeof(uint32_t)), "hipMalloc(check table)");
         if (rc == AESW_OK) T(hipMemcpy(ctx->d_chktab[li], ct.data(), ct.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(check table)");
     }
-    if (rc == AESW_OK) { int first = -1; rc = key_new_slot(ctx, &first); if (rc == AESW_OK) ctx->key_spare.push_back(first); }  // the first chunk of round-key slots
+    if (rc == AESW_OK) rc = ctx->keys.init(ctx);  // the first chunk of round-key slots
     if (rc == AESW_OK) T(warm_launch_attributes(), "hipFuncSetAttribute(max dynamic LDS)");
     if (rc == AESW_OK) T(hipMemcpy(ctx->d_tables, host, 768, hipMemcpyHostToDevice), "hipMemcpy(tables)");
     if (rc == AESW_OK) T(hipMemcpy(ctx->d_fr_lut, lut, sizeof lut, hipMemcpyHostToDevice), "hipMemcpy(fr_lut)");
@@ -377,12 +386,7 @@ void aesw_destroy(aesw_ctx *ctx) {
         aesw_arena_cache_trim(ctx, 0);
         if (ctx->d_tables) (void)hipFree(ctx->d_tables);
         if (ctx->d_fr_lut) (void)hipFree(ctx->d_fr_lut);
-        for (auto &sl : ctx->key_slots) {
-            if (sl.ready) (void)hipEventDestroy(sl.ready);
-            for (auto &r : sl.readers) (void)hipEventDestroy(r.e);
-        }
-        for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-        for (uint8_t *c : ctx->key_chunks) (void)hipFree(c);
+        ctx->keys.destroy();
         for (uint32_t *t : ctx->d_ftab)
             if (t) (void)hipFree(t);
         for (uint32_t *t : ctx->d_chktab)
@@ -565,7 +569,7 @@ int aesw_set_option(aesw_ctx *ctx, const char *name, int64_t value) {
     if (!std::strcmp(name, "chunk_blocks")) { if (value < 64) return AESW_ERR_INVALID_ARG; ctx->chunk_blocks = value; return AESW_OK; }
     if (!std::strcmp(name, "batch_streams")) { if (value < 1 || value > 8) return AESW_ERR_INVALID_ARG; ctx->batch_streams = (int)value; return AESW_OK; }
     if (!std::strcmp(name, "copy_threads")) { if (value < -1 || value > 64) return AESW_ERR_INVALID_ARG; ctx->copy_threads = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "key_slots")) { if (value < 1 || value > 64) return AESW_ERR_INVALID_ARG; ctx->key_ring = (int)value; return AESW_OK; }
+    if (!std::strcmp(name, "key_slots")) { if (value < 1 || value > 64) return AESW_ERR_INVALID_ARG; ctx->keys.set_ring_size((int)value); return AESW_OK; }
     if (!std::strcmp(name, "split_small")) { if (value < 0 || value > 8) return AESW_ERR_INVALID_ARG; ctx->split_small = (int)value; return AESW_OK; }
     if (!std::strcmp(name, "stream_check")) { if (value != 0 && value != 1) return AESW_ERR_INVALID_ARG; ctx->stream_check = (int)value; return AESW_OK; }
     if (!std::strcmp(name, "stream_poison")) { if (value < 0) return AESW_ERR_INVALID_ARG; ctx->stream_poison = value; return AESW_OK; }
@@ -611,7 +615,7 @@ int aesw_get_option(const aesw_ctx *ctx, const char *name, int64_t *value) {
     if (!std::strcmp(name, "batch_streams")) { *value = ctx->batch_streams; return AESW_OK; }
     if (!std::strcmp(name, "copy_threads")) { *value = ctx->copy_threads; return AESW_OK; }
     if (!std::strcmp(name, "effective_copy_threads")) { *value = auto_copy_threads(ctx); return AESW_OK; }
-    if (!std::strcmp(name, "key_slots")) { *value = ctx->key_ring; return AESW_OK; }
+    if (!std::strcmp(name, "key_slots")) { *value = ctx->keys.ring_size(); return AESW_OK; }
     if (!std::strcmp(name, "split_small")) { *value = ctx->split_small; return AESW_OK; }
     if (!std::strcmp(name, "stream_check")) { *value = ctx->stream_check; return AESW_OK; }
     if (!std::strcmp(name, "stream_poison")) { *value = ctx->stream_poison; return AESW_OK; }
@@ -625,15 +629,10 @@ int aesw_get_option(const aesw_ctx *ctx, const char *name, int64_t *value) {
         *value = (int64_t)b;
         return AESW_OK;
     }
-    if (!std::strcmp(name, "key_reader_waits")) { *value = (int64_t)ctx->key_waits; return AESW_OK; }  // read-only statistics
-    if (!std::strcmp(name, "key_writer_waits")) { *value = (int64_t)ctx->key_writer_waits; return AESW_OK; }
-    if (!std::strcmp(name, "key_slots_allocated")) { *value = (int64_t)ctx->key_slots.size(); return AESW_OK; }
-    if (!std::strcmp(name, "key_slots_pinned")) {
-        int64_t n = 0;
-        for (const auto &sl : ctx->key_slots) n += sl.pinned ? 1 : 0;
-        *value = n;
-        return AESW_OK;
-    }
+    if (!std::strcmp(name, "key_reader_waits")) { *value = (int64_t)ctx->keys.key_reader_waits(); return AESW_OK; }  // read-only statistics
+    if (!std::strcmp(name, "key_writer_waits")) { *value = (int64_t)ctx->keys.key_writer_waits(); return AESW_OK; }
+    if (!std::strcmp(name, "key_slots_allocated")) { *value = ctx->keys.key_slots_allocated(); return AESW_OK; }
+    if (!std::strcmp(name, "key_slots_pinned")) { *value = ctx->keys.key_slots_pinned(); return AESW_OK; }
     return AESW_ERR_INVALID_ARG;
 }
 
@@ -647,144 +646,23 @@ int aesw_schedule_key_device(aesw_ctx *ctx, const uint8_t *d_key, int layout, co
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool cap = stream_capturing(s);
-    int slot = -1;
-    // an eager schedule that fails before its key launch is issued leaves the slot as it was: keep its readers (still tracked)
-    // and step the ring back, so that the next schedule comes back to the slot with them intact
-    auto unwind = [&](hipError_t e, const char *what) {
-        if (!cap) ctx->key_pos = (ctx->key_pos + (int)ctx->key_ring_slots.size() - 1) % (int)ctx->key_ring_slots.size();
-        return fail_hip(ctx, e, what);
-    };
-    if (cap) {
-        // a captured schedule writes its slot on every replay of the graph, whenever that is: a slot of its own, never reused
-        const int rc = key_new_slot(ctx, &slot);
-        if (rc != AESW_OK) return rc;
-        ctx->key_slots[slot].pinned = true;
-    } else {
-        const int rc = key_next_ring_slot(ctx, &slot);
-        if (rc != AESW_OK) return rc;
-        // write-after-read: every launch that may still read this slot's previous key, on whatever stream, comes first
-        aesw_ctx::KeySlot &sl = ctx->key_slots[slot];
-        for (auto &r : sl.readers) {
-            const hipError_t e = hipStreamWaitEvent(s, r.e, 0);
-            if (e != hipSuccess) return unwind(e, "hipStreamWaitEvent(key readers)");
-            ++ctx->key_waits;
-        }
-        // write-after-write: the key launch that wrote the slot last may still be queued on its own stream; run behind it, or it
-        // lands on top of this key and its older key becomes the current one
-        if (sl.written && sl.writer != s) {
-            const hipError_t e = hipStreamWaitEvent(s, sl.ready, 0);
-            if (e != hipSuccess) return unwind(e, "hipStreamWaitEvent(key writer)");
-            ++ctx->key_writer_waits;
-        }
-    }
-    aesw_ctx::KeySlot &sl = ctx->key_slots[slot];
-    KeyParams kp{d_key, ctx->d_tables, ko, sl.d, 1, 0, 0};
-    const hipError_t le = launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, s);
-    if (le != hipSuccess) return unwind(le, "launch_key");
-    sl.written = true;
-    if (!cap) {
-        // the new key is issued behind every earlier reader: their events are free again
-        for (auto &r : sl.readers) ctx->event_pool.push_back(r.e);
-        sl.readers.clear();
-        // a later encrypt on ANOTHER stream (the host-pointer entry points use the context's own) waits for these round keys
-        HIP_TRY(ctx, hipEventRecord(sl.ready, s));
-    }
-    sl.writer = s;
-    ctx->key_cur = slot;
-    ctx->have_key = true;
-    return AESW_OK;
+    KeyRing::Access w;
+    const int rc = ctx->keys.begin_write(ctx, s, &w);
+    if (rc != AESW_OK) return rc;
+    KeyParams kp{d_key, ctx->d_tables, ko, w.d, 1, 0, 0};
+    return ctx->keys.end_write(ctx, w, launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, s));
 }
 
 int aesw_encrypt_witness_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys,
                                 uint64_t n, int layout, uint8_t *d_x, uint8_t *d_y, uint8_t *d_z, uint8_t *d_ct,
                                 const aesw_key_slab *ks, void *stream) {
     if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_encrypt_witness_device");
-    if (!ctx || !valid_layout(layout)) return AESW_ERR_INVALID_ARG;
-    if (!d_keys) {
-        if (per_block_keys) return AESW_ERR_INVALID_ARG;
-        if (!ctx->have_key) return AESW_ERR_NO_KEY;  // "Keys should be scheduled", src/aes128.rs:170
-    }
-    if (n == 0) return AESW_OK;
-    const bool has_x = aesw_column_stride(layout, 0) != 0;  // AESW_LAYOUT_VALUES has no x column: d_x is ignored
-    if (!d_pt || (has_x && !d_x) || !d_y || !d_z) return AESW_ERR_INVALID_ARG;
-    if ((has_x && !aligned16(d_x)) || !aligned16(d_y) || !aligned16(d_z) || !aligned4(d_pt) || (d_keys && !aligned4(d_keys)) ||
-        (d_ct && !aligned4(d_ct)))
-        return AESW_ERR_INVALID_ARG;
-    KeyOut ko;
-    if (!key_out_of(ks, &ko)) return AESW_ERR_INVALID_ARG;
-    const bool kemit = ko.w || ko.kx || ko.ky || ko.kz;
-    if (!d_keys && kemit) return AESW_ERR_INVALID_ARG;  // the key slab of a scheduled key comes from aesw_schedule_key*
-    if (ctx->split_small > 1 && !ctx->in_split && !per_block_keys && !kemit && n >= ((uint64_t)1 << 15) && n <= ((uint64_t)1 << 17)) {
-        // "split_small": the lone small batch as 2-3 sub-launches on the internal streams (fork / join as in the batch entry
-        // point).  Sub-ranges are multiples of 48 blocks -- whole 3-wave groups, and 48 x 1360 / 1056 / 608 are multiples of the
-        // 128-byte line, so no two sub-launches share a line of any column.
-        const uint32_t parts = (uint32_t)ctx->split_small;
-        const uint64_t per = ((n + parts - 1) / parts + 47) / 48 * 48;
-        aesw_batch b[8];
-        uint32_t cnt = 0;
-        const uint64_t sx = aesw_column_stride(layout, 0), sy = aesw_column_stride(layout, 1), sz = aesw_column_stride(layout, 2);
-        for (uint64_t lo = 0; lo < n && cnt < 8; lo += per, ++cnt) {
-            const uint64_t m = n - lo < per ? n - lo : per;
-            b[cnt] = aesw_batch{d_pt + lo * 16, d_keys, m, d_x ? d_x + lo * sx : nullptr, d_y + lo * sy, d_z + lo * sz,
-                                d_ct ? d_ct + lo * 16 : nullptr, nullptr};
-        }
-        const int keep = ctx->batch_streams;
-        ctx->batch_streams = (int)cnt;
-        ctx->in_split = true;
-        const int rc = aesw_encrypt_witness_batches_device(ctx, b, cnt, 0, layout, stream);
-        ctx->in_split = false;
-        ctx->batch_streams = keep;
-        return rc;
-    }
+    EncLaunch L;
+    int rc;
+    if (!validate_encrypt(ctx, d_pt, d_keys, per_block_keys, n, layout, d_x, d_y, d_z, d_ct, ks, &L, &rc)) return rc;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!per_block_keys && kemit) {
-        // shared key: its schedule witness is one key slab
-        KeyParams kp{d_keys, ctx->d_tables, ko, nullptr, 1, 0, 0};
-        HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, s));
-    }
-    const int km = per_block_keys ? 0 : (d_keys ? 1 : 2);
-    const bool cap = km == 2 && stream_capturing(s);
-    if (km == 2 && s != ctx->key_slots[ctx->key_cur].writer) {
-        // the round keys were written on another stream: order this launch behind them
-        aesw_ctx::KeySlot &sl = ctx->key_slots[ctx->key_cur];
-        if (cap && same_capture(s, sl.writer)) {
-            // `s` was forked (with an event) from the capture on the key's own stream -- the internal streams of the batch entry
-            // point and of "split_small" are: whatever ordered the key in front of that capture orders it in front of `s` too.
-            // (Asking the key's event would be an error here: its stream is the one being captured.)
-        } else if (cap) {
-            // a captured launch cannot take a dependency on work outside its graph.  If the key launch has already finished,
-            // there is nothing to depend on; otherwise refuse instead of dropping the wait silently
-            RelaxedCapture relaxed;
-            const bool done = !sl.pinned && hipEventQuery(sl.ready) == hipSuccess;
-            (void)hipGetLastError();
-            if (!done) {
-                ctx->last_error = "scheduled-key encrypt captured on a stream other than the one aesw_schedule_key_device ran on, "
-                                  "and the key launch has not finished (or was itself captured): synchronise first, or capture both on one stream";
-                return AESW_ERR_INVALID_ARG;
-            }
-        } else if (!sl.pinned) {
-            HIP_TRY(ctx, hipStreamWaitEvent(s, sl.ready, 0));
-        }  // (a slot written by a captured schedule has no event: the caller orders its graph launches, include/aesw.h)
-    }
-    EncParams p{d_pt, d_keys, km == 2 ? reinterpret_cast<const uint32_t *>(ctx->key_slots[ctx->key_cur].d) : nullptr, ctx->d_tables, ctx->d_ftab[layout], d_x, d_y, d_z, d_ct,
-                per_block_keys ? ko : KeyOut{nullptr, nullptr, nullptr, nullptr}, n, 0, 0};
-#ifdef AESW_TRACE
-    p.trace = ctx->trace;
-#endif
-    HIP_TRY(ctx, launch_encrypt(p, layout, ctx->xt, km, per_block_keys && kemit, auto_waves(ctx, layout, per_block_keys != 0),
-                                ctx->nt, (uint32_t)ctx->grid_cap, ctx->xcd_remap, (uint32_t)ctx->lds_pad, s));
-    if (km == 2) {  // this launch reads the current slot: nothing may overwrite the slot under it
-        aesw_ctx::KeySlot &sl = ctx->key_slots[ctx->key_cur];
-        if (cap) sl.pinned = true;  // read on every replay of the graph, whenever that is: the ring never reuses the slot
-        else {
-            const int rc = key_track_reader(ctx, sl, s);
-            if (rc != AESW_OK) return rc;
-        }
-    }
-    return AESW_OK;
+    return encrypt_lone(ctx, L, reinterpret_cast<hipStream_t>(stream));
 }
 
 int aesw_encrypt_witness_batches_device(aesw_ctx *ctx, const aesw_batch *batches, uint32_t count, int per_block_keys, int layout,
@@ -794,40 +672,25 @@ int aesw_encrypt_witness_batches_device(aesw_ctx *ctx, const aesw_batch *batches
     if (count == 0) return AESW_OK;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // a batch is checked when its turn comes: the batches in front of a refused one have been issued (and are joined)
+    auto issue = [&](uint32_t i, hipStream_t si, bool lone) {
+        const aesw_batch &b = batches[i];
+        EncLaunch L;
+        int rc;
+        if (!validate_encrypt(ctx, b.d_pt, b.d_keys, per_block_keys, b.n, layout, b.d_x, b.d_y, b.d_z, b.d_ct, b.d_key_slab, &L, &rc)) return rc;
+        return lone ? encrypt_lone(ctx, L, si) : enqueue_encrypt(ctx, L, si);
+    };
     const uint32_t ns = (uint32_t)ctx->batch_streams < count ? (uint32_t)ctx->batch_streams : count;
-    if (ns <= 1) {  // nothing to overlap: plain launches on the caller's stream
+    if (ns <= 1) {  // nothing to overlap: plain launches on the caller's stream, each of them a lone launch ("split_small" applies)
         for (uint32_t i = 0; i < count; ++i) {
-            const aesw_batch &b = batches[i];
-            const int rc = aesw_encrypt_witness_device(ctx, b.d_pt, b.d_keys, per_block_keys, b.n, layout, b.d_x, b.d_y, b.d_z, b.d_ct, b.d_key_slab, stream);
+            const int rc = issue(i, s, true);
             if (rc != AESW_OK) return rc;
         }
         return AESW_OK;
     }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!ctx->ev_fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    for (uint32_t j = 0; j < ns; ++j) {
-        if (!ctx->s_batch[j]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->s_batch[j], hipStreamNonBlocking));
-        if (!ctx->ev_join[j]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join[j], hipEventDisableTiming));
-    }
-    // fork: the internal streams start behind what the caller's stream holds
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
-    for (uint32_t j = 0; j < ns; ++j) HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_batch[j], ctx->ev_fork, 0));
-    int rc = AESW_OK;
-    const bool outer = !ctx->in_split;
-    ctx->in_split = true;  // the launches below already sit on the internal streams: "split_small" must not deal them out again
-    for (uint32_t i = 0; i < count && rc == AESW_OK; ++i) {
-        const aesw_batch &b = batches[i];
-        rc = aesw_encrypt_witness_device(ctx, b.d_pt, b.d_keys, per_block_keys, b.n, layout, b.d_x, b.d_y, b.d_z, b.d_ct, b.d_key_slab,
-                                         ctx->s_batch[i % ns]);
-    }
-    if (outer) ctx->in_split = false;
-    // join, also after a failed launch: what was issued must be ordered before whatever the caller does next on `stream`
-    for (uint32_t j = 0; j < ns; ++j) {
-        const hipError_t e1 = hipEventRecord(ctx->ev_join[j], ctx->s_batch[j]);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, ctx->ev_join[j], 0) : e1;
-        if (e2 != hipSuccess && rc == AESW_OK) rc = fail_hip(ctx, e2, "join of the batch streams");
-    }
-    return rc;
+    // batches dealt onto the internal streams are never split again
+    return fork_join(ctx, s, ns, count, [&](uint32_t i, hipStream_t si) { return issue(i, si, false); });
 }
 
 int aesw_key_schedule_witness_device(aesw_ctx *ctx, const uint8_t *d_keys, uint64_t n, int layout, uint8_t *d_w,

@@ -1,7 +1,8 @@
 // aesw_ctx.h -- the opaque context of include/aesw.h and the small helpers every translation unit of the C ABI uses
-// (aesw_api.cpp: context, options and the device-pointer entry points; aesw_hostpath.cpp: the host-pointer entry points and their
-// two-stage pipeline; aesw_arena.cpp: the probed column arena; aesw_group.cpp: device groups; aesw_circuits.cpp: many circuits per
-// launch), and the few internal functions one of them takes from another.  Not part of the public ABI.
+// (aesw_api.cpp: context, options and the device-pointer entry points; aesw_keyring.cpp: the scheduled key's round-key slots;
+// aesw_hostpath.cpp: the host-pointer entry points and their two-stage pipeline; aesw_arena.cpp: the probed column arena;
+// aesw_group.cpp: device groups; aesw_circuits.cpp: many circuits per launch), and the few internal functions one of them takes from
+// another.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/aesw.h"
+#include "aesw_keyring.h"
 
 struct aesw_ctx {
     int device = -1;
@@ -17,34 +19,7 @@ struct aesw_ctx {
     uint8_t *d_fr_lut = nullptr;  // 256 x 32 B
     uint32_t *d_ftab[3] = {nullptr, nullptr, nullptr};  // flush descriptors per layout (aesw_layout.h "scheduled flush")
     uint32_t *d_chktab[2] = {nullptr, nullptr};         // check tables of the DENSE / PACKED layout (aesw_check.h), uploaded by aesw_create
-    // The scheduled key (FixedAes128Config::schedule_key, src/aes128.rs:143-152: `self.keys = Some(..)` replaces the key between
-    // encrypt calls).  Round keys live in SLOTS of 256 B (176 used); every aesw_schedule_key_device takes the next slot of a small
-    // ring and every scheduled-key launch bakes the pointer of the slot that is current when it is ENQUEUED, so a launch never sees
-    // a later key.  A slot is rewritten only behind every launch that reads it: one event per distinct reader stream (re-recorded
-    // by that stream's later launches, which are ordered behind its earlier ones), all of them waited on by the schedule that
-    // reuses the slot.  That schedule is also ordered behind the key launch that wrote the slot last, when it ran on another
-    // stream (its `ready` event).  Slots a hipGraph capture has touched (a captured schedule writes one, a captured launch reads one
-    // on every replay) are PINNED: the ring never hands them out again.
-    struct KeyReader { hipStream_t s; hipEvent_t e; };
-    struct KeySlot {
-        uint8_t *d = nullptr;
-        bool pinned = false;
-        bool written = false;        // a key launch has been issued into the slot (`writer` may be the null stream: no marker)
-        hipEvent_t ready = nullptr;  // recorded behind the key launch that wrote the slot: launches on other streams wait on it
-        hipStream_t writer = nullptr;
-        std::vector<KeyReader> readers;  // launches that may still be reading the slot
-    };
-    std::vector<KeySlot> key_slots;
-    std::vector<uint8_t *> key_chunks;   // hipMalloc'ed backing of the slots (KEY_CHUNK_SLOTS each)
-    std::vector<hipEvent_t> event_pool;  // reader events not in use
-    std::vector<int> key_ring_slots;     // the ring: indices into key_slots, at most key_ring of them
-    std::vector<int> key_spare;          // slots taken out of the ring when "key_slots" shrank (their readers are still tracked)
-    int key_pos = 0;        // ring position of the slot the last eager schedule wrote
-    int key_cur = -1;       // slot of the current key (-1: none scheduled)
-    int key_ring = 4;       // option "key_slots": un-pinned slots the ring cycles through (1 = every schedule waits for all readers)
-    uint64_t key_waits = 0;  // statistics: reader events a schedule had to wait on (option "key_reader_waits", read-only)
-    uint64_t key_writer_waits = 0;  // statistics: schedules ordered behind another stream's writer of their slot ("key_writer_waits", read-only)
-    bool have_key = false;
+    KeyRing keys;  // the scheduled key: its round-key slots and their ordering (aesw_keyring.h)
     bool xt = false;
     int waves_shared = 0;  // waves per group, shared-key kernels (0 = auto)
     int waves_pbk = 0;     // per-block-key and key kernels (0 = auto)
@@ -97,7 +72,6 @@ struct aesw_ctx {
     hipStream_t s_compute = nullptr, s_copy = nullptr;
     int split_small = 0;    // experiment of round 4 (profiles/r04_study/split_small.md): a LONE shared / scheduled-key launch of 2^15 .. 2^17 blocks
                             // dealt as this many line-aligned sub-ranges onto the internal streams (0 / 1 = off)
-    bool in_split = false;  // re-entrancy guard of the above
     int batch_streams = 3;  // aesw_encrypt_witness_batches_device: internal streams the batches are dealt onto
     hipStream_t s_batch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -163,10 +137,8 @@ void aesw_arena_cache_trim(aesw_ctx *ctx, uint64_t keep_bytes);  // aesw_arena.c
 
 inline bool aesw_valid_layout(int l) { return l == AESW_LAYOUT_DENSE || l == AESW_LAYOUT_PACKED || l == AESW_LAYOUT_VALUES; }
 
-// What aesw_hostpath.cpp takes from aesw_api.cpp, and the one thing aesw_get_option takes back.  Internal: not in the dynamic symbol table.
-#define AESW_INTERNAL __attribute__((visibility("hidden")))
+// What aesw_hostpath.cpp takes from aesw_api.cpp, and the one thing aesw_get_option takes back (AESW_INTERNAL: aesw_keyring.h).
 namespace aesw { struct AssembleParams; }
-AESW_INTERNAL int key_track_reader(aesw_ctx *ctx, aesw_ctx::KeySlot &sl, hipStream_t s);  // a launch on `s` reads round-key slot `sl`
 // the argument checks of the assemble entry points and the launch parameters of all 3 n_sets + 1 columns
 AESW_INTERNAL int fill_assemble_params(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_blocks, int layout, const uint8_t *d_x,
                                        const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *ks, aesw::AssembleParams *p);

@@ -302,7 +302,7 @@ int aesw_encrypt_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, 
     if (n == 0) return AESW_OK;
     if (!pt) return AESW_ERR_INVALID_ARG;  // x / y / z: a null column is computed but not copied back
     if (!keys && (per_block_keys || (ks && (ks->w || ks->kx || ks->ky || ks->kz)))) return AESW_ERR_INVALID_ARG;
-    if (!keys && !ctx->have_key) return AESW_ERR_NO_KEY;
+    if (!keys && !ctx->keys.has_key()) return AESW_ERR_NO_KEY;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     int rc = ensure_streams(ctx);
@@ -381,7 +381,7 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
     if (!ctx || !aesw_valid_layout(layout) || !consume) return AESW_ERR_INVALID_ARG;
     if (n == 0) return AESW_OK;
     if (!pt || (!keys && per_block_keys)) return AESW_ERR_INVALID_ARG;
-    if (!keys && !ctx->have_key) return AESW_ERR_NO_KEY;
+    if (!keys && !ctx->keys.has_key()) return AESW_ERR_NO_KEY;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     int rc = ensure_streams(ctx);
@@ -420,17 +420,16 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
     if (keys) HIP_TRY(ctx, hipMemcpyAsync(d + o_keys, keys, pbk ? n * 16 : 16, hipMemcpyHostToDevice, ctx->s_compute));
     auto slab_of = [&](int s) { return aesw_key_slab{d + ks_off[s][0], d + ks_off[s][1], d + ks_off[s][2], d + ks_off[s][3]}; };
     const uint8_t *d_key16 = nullptr;  // the 16 key bytes of a shared / scheduled key on the device (the literal rows of words_column)
+    KeyRing::Access key_read;          // of a scheduled key, read by the key-slab launch below and by every chunk's check
     if (checking && !pbk) {
         // a scheduled key's bytes are the first round key of its slot (rk[0] = the key, src/key_schedule.rs:107-114)
-        d_key16 = keys ? d + o_keys : ctx->key_slots[ctx->key_cur].d;
-        if (!keys) {
-            aesw_ctx::KeySlot &sl = ctx->key_slots[ctx->key_cur];
-            if (!sl.pinned && sl.writer != ctx->s_compute) HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_compute, sl.ready, 0));
-        }
+        // (the context's own stream is never captured: an eager read, one wait for a key written on another stream)
+        if (!keys && (rc = ctx->keys.begin_read(ctx, ctx->s_compute, &key_read)) != AESW_OK) return rc;
+        d_key16 = keys ? d + o_keys : key_read.d;
         const aesw_key_slab one = slab_of(0);
         KeyParams kp{d_key16, ctx->d_tables, KeyOut{one.w, one.kx, one.ky, one.kz}, nullptr, 1, 0, 0};
         HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, ctx->s_compute));
-        if (!keys) { const int r = key_track_reader(ctx, ctx->key_slots[ctx->key_cur], ctx->s_compute); if (r != AESW_OK) return r; }
+        if (!keys && (rc = ctx->keys.end_read(ctx, key_read)) != AESW_OK) return rc;
     }
     rc = pl.create_events(true);  // timed: aesw_last_stream_stats reports where the time went
     if (rc != AESW_OK) return rc;
@@ -452,7 +451,7 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
                                d + col_off[s][1], d + col_off[s][2], nullptr, &stage_slab,
                                reinterpret_cast<aesw_check_report *>(d + o_rep) + b0 / chunk, ctx->s_compute, !pbk && b0 != 0);
         if (r != AESW_OK || keys) return r;
-        return key_track_reader(ctx, ctx->key_slots[ctx->key_cur], ctx->s_compute);
+        return ctx->keys.end_read(ctx, key_read);  // the check read the slot, on the stream key_read was begun on
     };
     auto copies = [&](int s, uint64_t, uint64_t m, std::vector<CopyJob> &d2h, std::vector<CopyJob> &) {
         for (int c = 0; c < 3; ++c)
