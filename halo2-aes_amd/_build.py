@@ -5,6 +5,8 @@
                                   no device code, linked against libaesw.so -- it only calls the C ABI
   halo2-aes_amd/libaesw_circ.so   the many-circuit witness checker of include/aesw_circ.h: one more gfx950 kernel and its
                                   entry point (hipcc), linked against libaesw.so, whose context it takes
+  halo2-aes_amd/libaesw_cols.so   the checker of the assembled advice columns, bytes or Fr cells (include/aesw_cols.h): built and
+                                  linked like libaesw_circ.so
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -23,6 +25,7 @@ CSRC = PKG / "csrc"
 LIB = PKG / "libaesw.so"
 HOST_LIB = PKG / "libaesw_host.so"
 CIRC_LIB = PKG / "libaesw_circ.so"
+COLS_LIB = PKG / "libaesw_cols.so"
 
 
 def _newer(target: Path, sources) -> bool:
@@ -103,6 +106,31 @@ def build_circ(force: bool = False) -> Path:
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
     return CIRC_LIB
+
+
+COLS_SOURCES = [CSRC / "cols" / "aesw_cols_check.hip"]
+COLS_HEADERS = CIRC_HEADERS[:-1] + [ROOT / "include" / "aesw_cols.h"]
+
+
+def build_cols(force: bool = False) -> Path:
+    """libaesw_cols.so: the checker of the assembled advice columns and its entry point (hipcc, gfx950), NEEDED libaesw.so found
+    next to it ($ORIGIN).  A library of its own, like libaesw_circ.so: the kernel sets of the other two stay what they are."""
+    deps = COLS_SOURCES + COLS_HEADERS + [LIB]
+    if not force and _newer(COLS_LIB, deps):
+        return COLS_LIB
+    import fcntl
+    with open(PKG / ".build.lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if not force and _newer(COLS_LIB, deps):
+                return COLS_LIB
+            tmp = COLS_LIB.with_suffix(".so.tmp%d" % os.getpid())
+            _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-o", str(tmp)] +
+                 [str(s) for s in COLS_SOURCES] + ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"])
+            os.replace(tmp, COLS_LIB)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return COLS_LIB
 
 
 def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_sources=()) -> Path:

@@ -19,6 +19,7 @@ from . import constants as K
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libaesw.so"            # HIP kernels + the C ABI of include/aesw.h
 HOST_LIB_PATH = _PKG / "libaesw_host.so"  # C++ mirror of the reference's host interface (include/aesw_host.h), above the C ABI
+COLS_LIB_PATH = _PKG / "libaesw_cols.so"  # the checker of the assembled advice columns (include/aesw_cols.h), next to libaesw.so
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -171,9 +172,40 @@ CIRC_SYMBOLS = {
     "aesw_circ_circuit_of_block": (_U32, [_P, _U32, _U64]),
 }
 
+# include/aesw_cols.h
+COLS_SYMBOLS = {
+    "aesw_cols_check_device": (_I, [_P, _U32, _U32, _U32, _P, _U64, _P, _P, _P, _I, _P, _P, _P]),
+    "aesw_cols_cell_index": (_U64, [_U32, _U32, _U32, _U32, _U64]),
+    "aesw_cols_fr_table": (None, [_P]),
+    "aesw_cols_hash_search": (_I, [_P, C.POINTER(_U32), C.POINTER(_U32), _P]),
+    "aesw_cols_hash_invert": (_I, [_P, _U32, _U32, _P, _P]),
+}
+
 _lib = None
 _host_lib = None
 _circ_lib = None
+_cols_lib = None
+
+
+def load_cols_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_cols.so (in-tree): the checker of the assembled advice columns.  It links against libaesw.so, whose contexts
+    it takes; a missing library is an error, there is no other implementation of Context.check_columns."""
+    global _cols_lib
+    if _cols_lib is not None and path is None:
+        return _cols_lib
+    load_library()  # libaesw.so first: the NEEDED entry resolves to the copy already mapped
+    p = Path(path) if path else COLS_LIB_PATH
+    if not p.exists():
+        raise FileNotFoundError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                "(hipcc --offload-arch=gfx950). There is no fallback implementation." % p)
+    lib = C.CDLL(str(p))
+    for name, (res, args) in COLS_SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if path is None:
+        _cols_lib = lib
+    return lib
 
 
 def load_circ_library(path: Path | None = None) -> C.CDLL:
@@ -418,6 +450,16 @@ def circ_report_dict(rep) -> dict:
     first = None if v[6] == 0xFFFFFFFFFFFFFFFF else (v[6] >> 20, bool((v[6] >> 19) & 1), (v[6] >> 16) & 7, v[6] & 0xFFFF)
     return {"blocks": v[0], "keys": v[1], "lookup_failures": v[2], "copy_failures": v[3], "gate_failures": v[4], "input_failures": v[5],
             "first": first, "offset_failures": v[7], "satisfied": not any(v[2:6]) and v[7] == 0}
+
+
+def cols_report_dict(rep) -> dict:
+    """The uint64[12] report tensor of Context.check_columns(sync=False), read back, as the dict sync=True returns."""
+    v = [int(x) & 0xFFFFFFFFFFFFFFFF for x in rep.cpu().tolist()]
+    out = circ_report_dict(rep[:8])
+    out.update(cell_failures=v[8], unassigned_failures=v[9], first_cell=None if v[10] == 0xFFFFFFFFFFFFFFFF else v[10], cells=v[11])
+    out["satisfied"] = out["satisfied"] and v[8] == 0 and v[9] == 0
+    return out
+
 
 Witness = namedtuple("Witness", "x y z ct key")
 KeyWitness = namedtuple("KeyWitness", "w kx ky kz rk")
@@ -846,6 +888,47 @@ class Context:
         torch.cuda.current_stream().synchronize()
         return circ_report_dict(rep)
 
+    def check_columns(self, k: int, n_sets: int, pt, keys, advice, counts, ct=None, sync: bool = True, _offsets=None):
+        """MockProver::assert_satisfied over the ASSEMBLED advice columns of C FixedAes128Config<k, n_sets> circuits in one launch
+        (aesw_cols_check_device, libaesw_cols.so).  advice: what assemble_advice_circuits returns, [C, 3*n_sets+1, 2^k] bytes or
+        [C, 3*n_sets+1, 2^k, 32] Fr cells (for C = 1 also assemble_advice's [3*n_sets+1, 2^k] / [..., 32]); pt uint8[n,16], keys
+        uint8[C,16] or None, ct uint8[n,16] or None, counts / _offsets as for check_circuits.  Returns the dict of check_circuits
+        plus cell_failures, unassigned_failures, first_cell (None or the absolute cell index) and cells; `satisfied` needs every
+        failure count to be 0.  With sync=False the uint64[12] device tensor the report was written to."""
+        lib = load_cols_library()
+        torch = self._torch()
+        pt = self._u8(pt, "pt")
+        n = int(pt.shape[0])
+        nc = len(counts)
+        advice = self._u8(advice, "advice")
+        ncol, rows = 3 * n_sets + 1, 1 << k
+        shape = tuple(advice.shape)
+        if shape in ((nc, ncol, rows), (nc, ncol, rows, 32)):
+            as_fr = len(shape) == 4
+        elif nc == 1 and shape in ((ncol, rows), (ncol, rows, 32)):
+            as_fr = len(shape) == 3
+        else:
+            raise ValueError("advice must be [C, 3*n_sets+1, 2^k] bytes or [C, 3*n_sets+1, 2^k, 32] Fr cells")
+        if _offsets is None:
+            d_offs = self._offsets_tensor(circuit_offsets(k, n_sets, counts, n))
+        else:
+            d_offs = _offsets
+            if int(d_offs.numel()) != nc + 1:
+                raise ValueError("_offsets must hold len(counts) + 1 entries")
+        if keys is not None and tuple(self._u8(keys, "keys").shape) != (nc, 16):
+            raise ValueError("keys must be [C,16] for C = len(counts)")
+        if ct is not None and tuple(self._u8(ct, "ct").shape) != (n, 16):
+            raise ValueError("ct must be [n,16]")
+        rep = torch.empty(12, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_cols_check_device(
+            self._h, k, n_sets, nc, d_offs.data_ptr(), n, pt.data_ptr() if n else None, keys.data_ptr() if keys is not None else None,
+            ct.data_ptr() if ct is not None and n else None, 1 if as_fr else 0, advice.data_ptr(), rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_cols_check_device")
+        if not sync:
+            return rep
+        torch.cuda.current_stream().synchronize()
+        return cols_report_dict(rep)
+
     def circuits(self, k: int, n_sets: int, keys, pt, counts, as_fr: bool = True):
         """C FixedAes128Config<k, n_sets> circuits on torch's current stream: the key schedule of keys (uint8[C,16]), the
         witness of pt (uint8[n,16]; circuit c takes the next counts[c] blocks) with each block under its circuit's key, and
@@ -1059,7 +1142,7 @@ class Group(Context):
 # the device-tensor methods of Context (the C ABI refuses them on a group as well)
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
-              "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits"):
+              "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
