@@ -49,26 +49,33 @@ def hipcc_path() -> str:
     raise RuntimeError("hipcc not found")
 
 
+def _build(target: Path, deps, command, force: bool) -> Path:
+    """`target` from `deps`, unless it is newer than all of them and not forced.  `command(tmp)` is the argument list that writes
+    the library to `tmp`.  Several ranks may get here at once (torchrun): serialise on a lock file, look again (another process
+    may have built it while we waited), build under a private name, publish with an atomic rename."""
+    if not force and _newer(target, deps):
+        return target
+    import fcntl
+    with open(PKG / ".build.lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if not force and _newer(target, deps):
+                return target
+            tmp = target.with_suffix(".so.tmp%d" % os.getpid())
+            _run(command(tmp))
+            os.replace(tmp, target)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return target
+
+
 def build_host(force: bool = False) -> Path:
     """libaesw_host.so: host code only (g++), NEEDED libaesw.so found next to it ($ORIGIN)."""
     host = PKG / "host"
     srcs = [host / "host_capi.cpp"]
     deps = srcs + [ROOT / "include" / "aesw.h", ROOT / "include" / "aesw_host.h", host / "halo2_lite.hpp", host / "aes_gadget.hpp", LIB]
-    if not force and _newer(HOST_LIB, deps):
-        return HOST_LIB
-    import fcntl
-    with open(PKG / ".build.lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and _newer(HOST_LIB, deps):
-                return HOST_LIB
-            tmp = HOST_LIB.with_suffix(".so.tmp%d" % os.getpid())
-            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", str(tmp)] + [str(s) for s in srcs] +
-                 ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"])
-            os.replace(tmp, HOST_LIB)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return HOST_LIB
+    return _build(HOST_LIB, deps, lambda tmp: ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", str(tmp)] + [str(s) for s in srcs] +
+                  ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"], force)
 
 
 # The one list of what libaesw.so is made of: tools that build a private variant of the library (tools/trace.py, parts.py,
@@ -87,25 +94,16 @@ CIRC_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_circ_search.h", "ae
     [ROOT / "include" / "aesw.h", ROOT / "include" / "aesw_circ.h"]
 
 
+def _checker_command(sources):
+    """libaesw_circ.so and libaesw_cols.so are built and linked alike."""
+    return lambda tmp: [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-o", str(tmp)] + \
+        [str(s) for s in sources] + ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]
+
+
 def build_circ(force: bool = False) -> Path:
     """libaesw_circ.so: the many-circuit checker kernel and its entry point (hipcc, gfx950), NEEDED libaesw.so found next to it
     ($ORIGIN).  A library of its own: the set of kernels inside libaesw.so stays what it is."""
-    deps = CIRC_SOURCES + CIRC_HEADERS + [LIB]
-    if not force and _newer(CIRC_LIB, deps):
-        return CIRC_LIB
-    import fcntl
-    with open(PKG / ".build.lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and _newer(CIRC_LIB, deps):
-                return CIRC_LIB
-            tmp = CIRC_LIB.with_suffix(".so.tmp%d" % os.getpid())
-            _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-o", str(tmp)] +
-                 [str(s) for s in CIRC_SOURCES] + ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"])
-            os.replace(tmp, CIRC_LIB)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return CIRC_LIB
+    return _build(CIRC_LIB, CIRC_SOURCES + CIRC_HEADERS + [LIB], _checker_command(CIRC_SOURCES), force)
 
 
 COLS_SOURCES = [CSRC / "cols" / "aesw_cols_check.hip"]
@@ -115,43 +113,12 @@ COLS_HEADERS = CIRC_HEADERS[:-1] + [ROOT / "include" / "aesw_cols.h"]
 def build_cols(force: bool = False) -> Path:
     """libaesw_cols.so: the checker of the assembled advice columns and its entry point (hipcc, gfx950), NEEDED libaesw.so found
     next to it ($ORIGIN).  A library of its own, like libaesw_circ.so: the kernel sets of the other two stay what they are."""
-    deps = COLS_SOURCES + COLS_HEADERS + [LIB]
-    if not force and _newer(COLS_LIB, deps):
-        return COLS_LIB
-    import fcntl
-    with open(PKG / ".build.lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and _newer(COLS_LIB, deps):
-                return COLS_LIB
-            tmp = COLS_LIB.with_suffix(".so.tmp%d" % os.getpid())
-            _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-o", str(tmp)] +
-                 [str(s) for s in COLS_SOURCES] + ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"])
-            os.replace(tmp, COLS_LIB)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return COLS_LIB
+    return _build(COLS_LIB, COLS_SOURCES + COLS_HEADERS + [LIB], _checker_command(COLS_SOURCES), force)
 
 
 def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_sources=()) -> Path:
     """libaesw.so, or with `extra_flags` / `extra_sources` and another `out` a diagnostic variant of it (-DAESW_TRACE, ...)."""
-    out = Path(out)
     srcs = PRODUCT_SOURCES + [Path(s) for s in extra_sources]
-    deps = srcs + PRODUCT_HEADERS
-    if not force and _newer(out, deps):
-        return out
-    # several ranks may get here at once (torchrun): serialise on a lock file, build under a
-    # private name, publish with an atomic rename
-    import fcntl
-    with open(PKG / ".build.lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and _newer(out, deps):
-                return out  # another process built it while we waited
-            tmp = out.with_suffix(".so.tmp%d" % os.getpid())
-            _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread"] + list(extra_flags) +
-                 ["-o", str(tmp)] + [str(s) for s in srcs])
-            os.replace(tmp, out)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return out
+    return _build(Path(out), srcs + PRODUCT_HEADERS,
+                  lambda tmp: [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread"] + list(extra_flags) +
+                  ["-o", str(tmp)] + [str(s) for s in srcs], force)

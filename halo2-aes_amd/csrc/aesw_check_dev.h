@@ -1,7 +1,12 @@
-// aesw_check_dev.h -- the device building blocks of the witness checker (aesw_check.h holds the checks themselves): the wave's
-// LDS synchronisation, the register staging of a unit's column ranges, the fast path's form of the check table and its
-// branch-free walk.  One source for every checker kernel: check_kernel (aesw_kernels.hip, libaesw.so) and circ_check_kernel
-// (circ/aesw_circ_check.hip, libaesw_circ.so).  Device code only: include from a HIP translation unit.
+// aesw_check_dev.h -- the wave-level core of the device witness checker, one source for all three checker kernels: check_kernel
+// (aesw_kernels.hip, libaesw.so), circ_check_kernel (circ/aesw_circ_check.hip, libaesw_circ.so) and cols_check_kernel
+// (cols/aesw_cols_check.hip, libaesw_cols.so).  aesw_check.h holds the checks themselves (the exact walk the CPU model runs);
+// this header holds what decides on the device whether a staged unit passes: the wave's LDS synchronisation, the register
+// staging of a unit's column ranges, the fast path's form of the check table and its branch-free walk, the verdict of a staged
+// block and of a staged key unit (block_unit_check, key_unit_check), the validation of circuit offsets (offsets_bad) and the
+// flush of a lane's counts into the report (flush_acc).  A kernel adds its prologue and its staging loop: how a unit and its
+// literal bytes get into the image and into registers.  The launch geometry the three launchers share is host code and lives
+// in aesw_internal.h.  Device code only: include from a HIP translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,6 +21,11 @@ namespace aesw {
 constexpr int LANES = 64;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// a value every lane of the wave holds alike, said so to the compiler: what is derived from it stays in scalar registers
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+    return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32 | __builtin_amdgcn_readfirstlane((uint32_t)v);
+}
 
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -67,6 +77,13 @@ __device__ __forceinline__ void load_fast_table(uint32_t *tab, const uint32_t *t
     for (uint32_t i = threadIdx.x; i < (uint32_t)BLOCK_COPIES; i += blockDim.x) tab[CHK_EDGES + i] = t[CHK_EDGES + i];
     for (uint32_t i = threadIdx.x; i < (uint32_t)(KEY_COPIES + WORDS_ROWS); i += blockDim.x) tab[CHK_KEDGES + i] = t[CHK_KEDGES + i];
 }
+// Table words whose low half is the image offset of a literal row a lane compares in the fast path (lanes 0..15, i = lane & 15;
+// the other lanes read a valid entry they never use).  Ciphertext: z of the block's last sixteen rows, AES_ROWS - 16 + i, which
+// sits in the second word of the row entry: tab[CHK_CT_LITERALS + 2 * i].  Key bytes: words_column rows 0..15, the low half of
+// their gate entries: tab[CHK_KEY_LITERALS + i].  Constants, not helpers: a function around the index or the load compiles
+// check_kernel differently (profiles/checker_core/README.md).
+constexpr int CHK_CT_LITERALS = CHK_ROWS + 2 * (AES_ROWS - 16) + 1, CHK_KEY_LITERALS = CHK_GATES;
+
 // one lookup row, branch-free: 1 if the enabled lookup has no table row
 __device__ __forceinline__ uint32_t fast_row_bad(const uint8_t *img, const uint8_t *t768, uint32_t w0, uint32_t w1) {
     const uint32_t x = img[w0 & 0xffffu], y = img[w0 >> 16], z = img[w1 & 0xffffu], tag = (w1 >> 16) & 7u;
@@ -91,10 +108,60 @@ __device__ __forceinline__ uint32_t fast_unit_bad(const uint8_t *img, const uint
     return bad;
 }
 
-// Fast path per block: every lane evaluates its slice branch-free out of registers ("is anything wrong with this unit?"); only a
+// Fast path per unit: every lane evaluates its slice branch-free out of registers ("is anything wrong with this unit?"); only a
 // unit where some lane says yes is walked again by the exact code of aesw_check.h (the code the CPU model runs), which counts
 // and names the failures.  A satisfied witness -- the normal case -- never takes the second walk.
 // Pipeline per wave: the loads of block b + stride are issued (into registers) before block b is checked out of LDS.
+// img: the wave's image with the unit staged and wave_lds_sync() passed; tab / t768: the fast table and tab768 in LDS;
+// table: the check table in global memory, which the exact walk reads; lit_b: plaintext | ciphertext << 8 and klit: the key byte
+// of lanes 0..15, fetched with the unit; ct_off / w_off: the offsets out of tab[CHK_CT_LITERALS + 2 * i] / tab[CHK_KEY_LITERALS + i].
+__device__ __forceinline__ void block_unit_check(const uint8_t *img, const uint32_t *tab, const uint8_t *t768, const uint32_t *table,
+                                                 const uint8_t *pt, const uint8_t *ct, uint32_t lit_b, uint32_t ct_off, uint64_t b,
+                                                 uint32_t lane, CheckAcc &acc) {
+    uint32_t bad = fast_unit_bad<CHK_ROWS, AES_ROWS, CHK_EDGES, BLOCK_COPIES>(img, t768, tab, lane);
+    if (lane < 16) {
+        bad |= img[lane] != (lit_b & 0xffu);
+        if (ct) bad |= img[ct_off] != (lit_b >> 8);
+    }
+    if (__ballot(bad != 0) != 0) check_block(img, table, t768, pt + b * 16, ct ? ct + b * 16 : nullptr, b, lane, LANES, acc);
+}
+__device__ __forceinline__ void key_unit_check(const uint8_t *img, const uint32_t *tab, const uint8_t *t768, const uint32_t *table,
+                                               const uint8_t *keys, uint32_t klit, uint32_t w_off, uint64_t unit, uint32_t lane,
+                                               CheckAcc &acc) {
+    uint32_t kbad = fast_unit_bad<CHK_KROWS, KEY_ROWS, CHK_KEDGES, KEY_COPIES>(img, t768, tab, lane);
+    for (uint32_t r = lane; r < (uint32_t)WORDS_ROWS; r += LANES) {
+        const uint32_t gte = tab[CHK_GATES + r];
+        kbad |= ((gte >> 24) != 0) & (img[gte & 0xffffu] != ((gte >> 16) & 0xffu));
+    }
+    if (lane < 16 && keys) kbad |= img[w_off] != klit;
+    if (__ballot(kbad != 0) != 0) check_key(img, table, t768, keys ? keys + unit * 16 : nullptr, unit, lane, LANES, acc);
+}
+// One lane's finding into a word of the report.  Failures are the rare case: a lane that found any adds them itself.
+__device__ __forceinline__ void report_add(uint64_t *word, uint64_t count) {
+    if (count) atomicAdd(reinterpret_cast<unsigned long long *>(word), (unsigned long long)count);
+}
+__device__ __forceinline__ void report_min(uint64_t *word, uint64_t first) {
+    if (first != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(word), (unsigned long long)first);
+}
+// report words 2..6 (lookup, copy, gate, input, first); a kernel whose report has more words adds them next to the call
+__device__ __forceinline__ void flush_acc(uint64_t *report, const CheckAcc &acc) {
+    report_add(report + 2, acc.lookup); report_add(report + 3, acc.copy); report_add(report + 4, acc.gate); report_add(report + 5, acc.input);
+    report_min(report + 6, acc.first);
+}
+// The circuit offsets of a many-circuit batch (C + 1 values: 0 first, n last, ascending, at most `cap` blocks per circuit),
+// validated by the lanes of the grid, one circuit per lane, once: what this lane counted.
+__device__ __forceinline__ uint32_t offsets_bad(const uint64_t *offsets, uint64_t nc, uint64_t n, uint64_t cap, uint64_t gwave,
+                                                uint64_t nwaves, uint32_t lane) {
+    uint32_t off_bad = 0;
+    for (uint64_t c = gwave * LANES + lane; c < nc; c += nwaves * LANES) {
+        const uint64_t o0 = offsets[c], o1 = offsets[c + 1];
+        off_bad += (o1 < o0 || o1 - o0 > cap) ? 1u : 0u;
+        if (c == 0 && o0 != 0) ++off_bad;
+        if (c + 1 == nc && o1 != n) ++off_bad;
+    }
+    return off_bad;
+}
+
 template <int LAYOUT>
 struct ChkLayout {
     static constexpr int SX = AES_ROWS, SY = LAYOUT == DENSE ? AES_ROWS : Geo<PACKED>::YS, SZ = LAYOUT == DENSE ? AES_ROWS : Geo<PACKED>::ZS;

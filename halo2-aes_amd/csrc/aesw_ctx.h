@@ -135,6 +135,7 @@ struct DeviceGuard {
 
 void aesw_arena_cache_trim(aesw_ctx *ctx, uint64_t keep_bytes);  // aesw_arena.cpp: release cached arenas, oldest first, until keep_bytes stay
 
+inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }  // a: a power of two
 inline bool aesw_valid_layout(int l) { return l == AESW_LAYOUT_DENSE || l == AESW_LAYOUT_PACKED || l == AESW_LAYOUT_VALUES; }
 
 // What aesw_hostpath.cpp takes from aesw_api.cpp, and the one thing aesw_get_option takes back (AESW_INTERNAL: aesw_keyring.h).

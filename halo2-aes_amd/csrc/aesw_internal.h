@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aesw_check.h"
+
 namespace aesw {
 
 struct KeyOut {
@@ -87,6 +89,17 @@ struct CheckParams {
     uint32_t sx, sy, sz, kxs, kys, kzs, bi, img;  // strides, block image bytes, bytes of one wave's image region
 };
 hipError_t launch_check(const CheckParams &p, hipStream_t s);
+// The launch geometry of the three checker kernels (check_kernel, circ_check_kernel, cols_check_kernel): four waves per
+// workgroup, one unit per wave at a time, and at most three workgroups (twelve waves) for each of the 256 CUs -- every wave
+// strides over its share of the units.
+constexpr uint32_t CHECK_WAVES = 4;
+inline uint64_t check_groups(uint64_t units) {
+    const uint64_t groups = (units + CHECK_WAVES - 1) / CHECK_WAVES;
+    return groups < 256 * 3 ? groups : 256 * 3;
+}
+// Dynamic LDS of the part every checker kernel lays out first: fast table | tab768 | one image of `img` bytes per wave
+// (ChkLayout<LAYOUT>::IMG).  What a kernel keeps behind it is its launcher's to add.
+inline size_t check_lds_bytes(size_t img) { return (size_t)CHK_WORDS * 4 + 768 + CHECK_WAVES * img; }
 hipError_t launch_expand_fr(const uint8_t *cells, uint64_t n_cells, const void *fr_lut, void *out, int store_mode, int geometry, hipStream_t s);
 
 }  // namespace aesw

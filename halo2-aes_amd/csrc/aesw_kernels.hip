@@ -934,7 +934,8 @@ hipError_t launch_probe(const ProbeParams &p0, bool fill, hipStream_t s) {
 // check_kernel: MockProver::assert_satisfied over slabs (aesw_check.h).  One wave = one block at a time: its three column
 // ranges (and, with per-block keys, its key slab) are copied into the wave's LDS image with coalesced dword loads, then the
 // 64 lanes walk the row, edge and gate entries of the layout's check table (LDS, loaded once per workgroup).  Read-bound:
-// 3 992 B per block with per-block keys.  Waves stride over the blocks; nothing is written but the report.
+// 3 992 B per block with per-block keys.  Waves stride over the blocks; nothing is written but the report.  What decides
+// whether a staged unit passes is aesw_check_dev.h's (shared with libaesw_circ.so and libaesw_cols.so); here is the staging.
 // ---------------------------------------------------------------------------
 template <int LAYOUT, bool PBK>
 __global__ void __launch_bounds__(256) check_kernel(const CheckParams a) {
@@ -951,8 +952,7 @@ __global__ void __launch_bounds__(256) check_kernel(const CheckParams a) {
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x / LANES), gwave = (uint64_t)blockIdx.x * (blockDim.x / LANES) + wave;
     CheckAcc acc;
     if (gwave == 0 && lane == 0) { a.report[0] = a.n; a.report[1] = PBK ? a.n : (a.skip_shared_key ? 0 : 1); }
-    const uint32_t ct_off = tab[CHK_ROWS + 2 * (AES_ROWS - 16 + (lane & 15)) + 1] & 0xffffu;  // lanes 0..15: z of rows 1344 + lane
-    const uint32_t w_off = tab[CHK_GATES + (lane & 15)] & 0xffffu;                              // lanes 0..15: words_column row `lane`
+    const uint32_t ct_off = tab[CHK_CT_LITERALS + 2 * (lane & 15)] & 0xffffu, w_off = tab[CHK_KEY_LITERALS + (lane & 15)] & 0xffffu;  // lanes 0..15
     if (!PBK) {  // one key slab for the whole batch: every wave keeps a copy; the first wave of the grid checks it
         StagedKey<LAYOUT> sk;
         sk.load(a, 0, lane);
@@ -979,29 +979,11 @@ __global__ void __launch_bounds__(256) check_kernel(const CheckParams a) {
         const uint32_t lit_b = lit, klit_b = klit;
         wave_lds_sync();
         if (b + nwaves < a.n) fetch(b + nwaves);  // in flight while this block is checked
-        uint32_t bad = fast_unit_bad<CHK_ROWS, AES_ROWS, CHK_EDGES, BLOCK_COPIES>(img, t768, tab, lane);
-        if (lane < 16) {
-            bad |= img[lane] != (lit_b & 0xffu);
-            if (a.ct) bad |= img[ct_off] != (lit_b >> 8);
-        }
-        if (__ballot(bad != 0) != 0) check_block(img, a.table, t768, a.pt + b * 16, a.ct ? a.ct + b * 16 : nullptr, b, lane, LANES, acc);
-        if (PBK) {
-            uint32_t kbad = fast_unit_bad<CHK_KROWS, KEY_ROWS, CHK_KEDGES, KEY_COPIES>(img, t768, tab, lane);
-            for (uint32_t r = lane; r < (uint32_t)WORDS_ROWS; r += LANES) {
-                const uint32_t gte = tab[CHK_GATES + r];
-                kbad |= ((gte >> 24) != 0) & (img[gte & 0xffffu] != ((gte >> 16) & 0xffu));
-            }
-            if (lane < 16 && a.keys) kbad |= img[w_off] != klit_b;
-            if (__ballot(kbad != 0) != 0) check_key(img, a.table, t768, a.keys ? a.keys + b * 16 : nullptr, b, lane, LANES, acc);
-        }
+        block_unit_check(img, tab, t768, a.table, a.pt, a.ct, lit_b, ct_off, b, lane, acc);
+        if (PBK) key_unit_check(img, tab, t768, a.table, a.keys, klit_b, w_off, b, lane, acc);
         wave_lds_sync();  // the next block overwrites the image
     }
-    // failures are the rare case: a lane that found any adds them itself
-    if (acc.lookup) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 2), (unsigned long long)acc.lookup);
-    if (acc.copy) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 3), (unsigned long long)acc.copy);
-    if (acc.gate) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 4), (unsigned long long)acc.gate);
-    if (acc.input) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 5), (unsigned long long)acc.input);
-    if (acc.first != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(a.report + 6), (unsigned long long)acc.first);
+    flush_acc(a.report, acc);
 }
 
 hipError_t launch_check(const CheckParams &p, hipStream_t s) {
@@ -1009,12 +991,9 @@ hipError_t launch_check(const CheckParams &p, hipStream_t s) {
     hipError_t e = hipMemsetAsync(p.report, 0, 6 * sizeof(uint64_t), s);
     if (e == hipSuccess) e = hipMemsetAsync(p.report + 6, 0xff, sizeof(uint64_t), s);
     if (e != hipSuccess || p.n == 0) return e;
-    const uint32_t waves = 4;
     const bool dense = p.sy == (uint32_t)AES_ROWS;
-    const size_t lds = (size_t)CHK_WORDS * 4 + 768 + (size_t)waves * (dense ? ChkLayout<DENSE>::IMG : ChkLayout<PACKED>::IMG);  // 41 / 46 KiB
-    uint64_t groups = (p.n + waves - 1) / waves;
-    if (groups > 256 * 3) groups = 256 * 3;  // three workgroups (twelve waves) per CU, every wave strides over its share of the blocks
-    const dim3 grid((unsigned)groups), block(waves * LANES);
+    const size_t lds = check_lds_bytes(dense ? ChkLayout<DENSE>::IMG : ChkLayout<PACKED>::IMG);  // 41 / 46 KiB
+    const dim3 grid((unsigned)check_groups(p.n)), block(CHECK_WAVES * LANES);
     if (dense) {
         if (p.per_block_keys) hipLaunchKernelGGL((check_kernel<DENSE, true>), grid, block, lds, s, p);
         else hipLaunchKernelGGL((check_kernel<DENSE, false>), grid, block, lds, s, p);

@@ -1,6 +1,7 @@
 // circ/aesw_circ_check.hip -- libaesw_circ.so (include/aesw_circ.h): MockProver::assert_satisfied over a many-circuit batch in
-// one launch.  (A directory of its own, as it is a library of its own: csrc/ itself holds the sources of libaesw.so.)  The checks are aesw_check.h's, the wave's machinery aesw_check_dev.h's -- the sources check_kernel (libaesw.so) is
-// made of -- and the kernel is shaped on check_kernel's per-block-key form: four-wave workgroups, one unit per wave at a time,
+// one launch.  (A directory of its own, as it is a library of its own: csrc/ itself holds the sources of libaesw.so.)  The checks are aesw_check.h's; the wave's machinery, the verdict of a staged
+// unit, the offset validation and the report flush are aesw_check_dev.h's, and the launch geometry aesw_internal.h's -- the
+// sources check_kernel (libaesw.so) is made of.  What is here is the staging, shaped on check_kernel's per-block-key form: four-wave workgroups, one unit per wave at a time,
 // the next block's loads issued into registers before the current one is checked out of LDS, a branch-free fast path, and the
 // exact second walk (check_block / check_key) only for a unit some lane objects to.  What differs:
 //   * block b is held against key slab circuit(b) (aesw_circ_search.h: a wave-uniform binary search over the offsets, scalar
@@ -44,17 +45,8 @@ __global__ void __launch_bounds__(256) circ_check_kernel(const CircCheckParams p
     const uint64_t nc = p.n_circuits;
     CheckAcc acc;
     if (gwave == 0 && lane == 0) { a.report[0] = a.n; a.report[1] = nc; }
-    const uint32_t ct_off = tab[CHK_ROWS + 2 * (AES_ROWS - 16 + (lane & 15)) + 1] & 0xffffu;  // lanes 0..15: z of rows 1344 + lane
-    const uint32_t w_off = tab[CHK_GATES + (lane & 15)] & 0xffffu;                              // lanes 0..15: words_column row `lane`
-
-    // the offsets: one circuit per lane, once
-    uint32_t off_bad = 0;
-    for (uint64_t c = gwave * LANES + lane; c < nc; c += nwaves * LANES) {
-        const uint64_t o0 = p.offsets[c], o1 = p.offsets[c + 1];
-        off_bad += (o1 < o0 || o1 - o0 > p.cap) ? 1u : 0u;
-        if (c == 0 && o0 != 0) ++off_bad;
-        if (c + 1 == nc && o1 != a.n) ++off_bad;
-    }
+    const uint32_t ct_off = tab[CHK_CT_LITERALS + 2 * (lane & 15)] & 0xffffu, w_off = tab[CHK_KEY_LITERALS + (lane & 15)] & 0xffffu;  // lanes 0..15
+    const uint32_t off_bad = offsets_bad(p.offsets, nc, a.n, p.cap, gwave, nwaves, lane);
 
     // the key slabs: unit c, also for a circuit that holds no block
     for (uint64_t c = gwave; c < nc; c += nwaves) {
@@ -64,13 +56,7 @@ __global__ void __launch_bounds__(256) circ_check_kernel(const CircCheckParams p
         if (lane < 16 && a.keys) klit = a.keys[c * 16 + lane];
         sk.store(kimg, lane);
         wave_lds_sync();
-        uint32_t kbad = fast_unit_bad<CHK_KROWS, KEY_ROWS, CHK_KEDGES, KEY_COPIES>(img, t768, tab, lane);
-        for (uint32_t r = lane; r < (uint32_t)WORDS_ROWS; r += LANES) {
-            const uint32_t gte = tab[CHK_GATES + r];
-            kbad |= ((gte >> 24) != 0) & (img[gte & 0xffffu] != ((gte >> 16) & 0xffu));
-        }
-        if (lane < 16 && a.keys) kbad |= img[w_off] != klit;
-        if (__ballot(kbad != 0) != 0) check_key(img, a.table, t768, a.keys ? a.keys + c * 16 : nullptr, c, lane, LANES, acc);
+        key_unit_check(img, tab, t768, a.table, a.keys, klit, w_off, c, lane, acc);
         wave_lds_sync();  // the next unit overwrites the key image
     }
 
@@ -81,8 +67,7 @@ __global__ void __launch_bounds__(256) circ_check_kernel(const CircCheckParams p
     typedef const uint64_t __attribute__((address_space(4))) *ConstOffsets;  // read-only for the whole launch: scalar loads
     const ConstOffsets offs = (ConstOffsets)p.offsets;
     auto fetch = [&](uint64_t b) {
-        const uint64_t bu = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32 | __builtin_amdgcn_readfirstlane((uint32_t)b);
-        const uint32_t c = circuit_of_block(offs, p.n_circuits, bu);
+        const uint32_t c = circuit_of_block(offs, p.n_circuits, uni64(b));
         sx.load(a.x + b * G::SX, lane); sy.load(a.y + b * G::SY, lane); sz.load(a.z + b * G::SZ, lane);
         skey.load(a, c, lane);
         if (lane < 16) {
@@ -97,21 +82,11 @@ __global__ void __launch_bounds__(256) circ_check_kernel(const CircCheckParams p
         const uint32_t lit_b = lit;
         wave_lds_sync();
         if (b + nwaves < a.n) fetch(b + nwaves);  // in flight while this block is checked
-        uint32_t bad = fast_unit_bad<CHK_ROWS, AES_ROWS, CHK_EDGES, BLOCK_COPIES>(img, t768, tab, lane);
-        if (lane < 16) {
-            bad |= img[lane] != (lit_b & 0xffu);
-            if (a.ct) bad |= img[ct_off] != (lit_b >> 8);
-        }
-        if (__ballot(bad != 0) != 0) check_block(img, a.table, t768, a.pt + b * 16, a.ct ? a.ct + b * 16 : nullptr, b, lane, LANES, acc);
+        block_unit_check(img, tab, t768, a.table, a.pt, a.ct, lit_b, ct_off, b, lane, acc);
         wave_lds_sync();  // the next block overwrites the image
     }
-    // failures are the rare case: a lane that found any adds them itself
-    if (acc.lookup) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 2), (unsigned long long)acc.lookup);
-    if (acc.copy) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 3), (unsigned long long)acc.copy);
-    if (acc.gate) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 4), (unsigned long long)acc.gate);
-    if (acc.input) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 5), (unsigned long long)acc.input);
-    if (acc.first != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(a.report + 6), (unsigned long long)acc.first);
-    if (off_bad) atomicAdd(reinterpret_cast<unsigned long long *>(a.report + 7), (unsigned long long)off_bad);
+    flush_acc(a.report, acc);
+    report_add(a.report + 7, off_bad);
 }
 
 // The report starts as (0 blocks, 0 keys, no failures, first = none, no offset failures): one eight-lane launch in front of the
@@ -125,22 +100,15 @@ static hipError_t launch_circ_check(const CircCheckParams &p, bool dense, hipStr
     hipLaunchKernelGGL(circ_report_init_kernel, dim3(1), dim3(64), 0, s, p.c.report);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const uint32_t waves = 4;
-    const size_t lds = (size_t)CHK_WORDS * 4 + 768 + (size_t)waves * (dense ? ChkLayout<DENSE>::IMG : ChkLayout<PACKED>::IMG);  // 41 / 46 KiB
+    const size_t lds = check_lds_bytes(dense ? ChkLayout<DENSE>::IMG : ChkLayout<PACKED>::IMG);  // 41 / 46 KiB
     const uint64_t units = p.c.n > p.n_circuits ? p.c.n : p.n_circuits;  // n_circuits >= 1: there is always a key slab to check
-    uint64_t groups = (units + waves - 1) / waves;
-    if (groups > 256 * 3) groups = 256 * 3;  // three workgroups (twelve waves) per CU, every wave strides over its share of the units
-    const dim3 grid((unsigned)groups), block(waves * LANES);
+    const dim3 grid((unsigned)check_groups(units)), block(CHECK_WAVES * LANES);
     if (dense) hipLaunchKernelGGL((circ_check_kernel<DENSE>), grid, block, lds, s, p);
     else hipLaunchKernelGGL((circ_check_kernel<PACKED>), grid, block, lds, s, p);
     return hipGetLastError();
 }
 
 }  // namespace aesw_circ
-
-namespace {
-bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-}  // namespace
 
 extern "C" {
 

@@ -1,6 +1,7 @@
 // cols/aesw_cols_check.hip -- libaesw_cols.so (include/aesw_cols.h): MockProver::assert_satisfied over the ASSEMBLED advice
 // columns of a many-circuit batch, bytes or bn256::Fr cells, in one launch.  The checks are aesw_check.h's and the wave's
-// machinery aesw_check_dev.h's, unmodified (check_block, check_key, the fast table and its branch-free walk); only the staging
+// machinery aesw_check_dev.h's, called, not copied (check_block, check_key, the fast table and its branch-free walk, the verdict
+// of a staged unit, the offset validation, the report flush; the launch geometry is aesw_internal.h's); only the staging
 // is new: a unit's DENSE image  x | y | z | kx | ky | kz | words  is gathered from the columns instead of from slabs.
 //   * a block's three ranges are 1 360 contiguous cells of three neighbouring columns, starting on a 16-byte boundary
 //     (rows 400 + 1360 j in set 0, 1360 j elsewhere); in byte form they travel like a DENSE slab, the next block's loads
@@ -50,10 +51,6 @@ struct CellAcc {
     uint64_t cell = 0, unassigned = 0, first = ~0ull;
 };
 
-// a value every lane of the wave holds alike, said so to the compiler: what is derived from it stays in scalar registers
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-    return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32 | __builtin_amdgcn_readfirstlane((uint32_t)v);
-}
 __device__ __forceinline__ bool any4(u32x4 v) { return (v.x | v.y | v.z | v.w) != 0; }
 
 // Byte form: the staged registers of one column range against its mask (bytes 0xff where nothing is assigned).
@@ -153,20 +150,11 @@ __global__ void __launch_bounds__(256) cols_check_kernel(const ColsParams p) {
     CheckAcc acc;
     CellAcc ca;
     if (gwave == 0 && lane == 0) { p.report[0] = p.n; p.report[1] = nc; p.report[11] = (nc * ncols) << p.k; }
-    const uint32_t ct_off = tab[CHK_ROWS + 2 * (AES_ROWS - 16 + (lane & 15)) + 1] & 0xffffu;
-    const uint32_t w_off = tab[CHK_GATES + (lane & 15)] & 0xffffu;
+    const uint32_t ct_off = tab[CHK_CT_LITERALS + 2 * (lane & 15)] & 0xffffu, w_off = tab[CHK_KEY_LITERALS + (lane & 15)] & 0xffffu;  // lanes 0..15
     typedef const uint64_t __attribute__((address_space(4))) *ConstOffsets;  // read-only for the whole launch: scalar loads
     const ConstOffsets offs = (ConstOffsets)p.offsets;
     auto cell_of = [&](uint64_t c, uint32_t col, uint64_t row) { return ((c * ncols + col) << p.k) + row; };
-
-    // the offsets: one circuit per lane, once
-    uint32_t off_bad = 0;
-    for (uint64_t c = gwave * LANES + lane; c < nc; c += nwaves * LANES) {
-        const uint64_t o0 = p.offsets[c], o1 = p.offsets[c + 1];
-        off_bad += (o1 < o0 || o1 - o0 > p.cap) ? 1u : 0u;
-        if (c == 0 && o0 != 0) ++off_bad;
-        if (c + 1 == nc && o1 != p.n) ++off_bad;
-    }
+    const uint32_t off_bad = offsets_bad(p.offsets, nc, p.n, p.cap, gwave, nwaves, lane);
 
     // the key rows of circuit c into the key image; COUNT: with their cell tests (the key unit), else bytes only (a block's run)
     auto stage_key = [&](uint64_t c, bool count) {
@@ -204,13 +192,7 @@ __global__ void __launch_bounds__(256) cols_check_kernel(const ColsParams p) {
         if (lane < 16 && p.keys) klit = p.keys[c * 16 + lane];
         stage_key(c, true);
         wave_lds_sync();
-        uint32_t kbad = fast_unit_bad<CHK_KROWS, KEY_ROWS, CHK_KEDGES, KEY_COPIES>(img, t768, tab, lane);
-        for (uint32_t r = lane; r < (uint32_t)WORDS_ROWS; r += LANES) {
-            const uint32_t gte = tab[CHK_GATES + r];
-            kbad |= ((gte >> 24) != 0) & (img[gte & 0xffffu] != ((gte >> 16) & 0xffu));
-        }
-        if (lane < 16 && p.keys) kbad |= img[w_off] != klit;
-        if (__ballot(kbad != 0) != 0) check_key(img, p.table, t768, p.keys ? p.keys + c * 16 : nullptr, c, lane, LANES, acc);
+        key_unit_check(img, tab, t768, p.table, p.keys, klit, w_off, c, lane, acc);
         wave_lds_sync();  // the next unit overwrites the key image
     }
 
@@ -270,12 +252,7 @@ __global__ void __launch_bounds__(256) cols_check_kernel(const ColsParams p) {
                     if (!AS_FR && __ballot(stray != 0) != 0)
                         for (uint32_t col = 0; col < 3; ++col)
                             count_stray(img + col * AES_ROWS, mask + col * AES_ROWS, AES_ROWS, cell0 + ((uint64_t)col << p.k), lane, ca);
-                    uint32_t bad = fast_unit_bad<CHK_ROWS, AES_ROWS, CHK_EDGES, BLOCK_COPIES>(img, t768, tab, lane);
-                    if (lane < 16) {
-                        bad |= img[lane] != (lit_b & 0xffu);
-                        if (p.ct) bad |= img[ct_off] != (lit_b >> 8);
-                    }
-                    if (__ballot(bad != 0) != 0) check_block(img, p.table, t768, p.pt + b * 16, p.ct ? p.ct + b * 16 : nullptr, b, lane, LANES, acc);
+                    block_unit_check(img, tab, t768, p.table, p.pt, p.ct, lit_b, ct_off, b, lane, acc);
                 }
                 wave_lds_sync();  // the next block overwrites the image
             }
@@ -344,17 +321,9 @@ __global__ void __launch_bounds__(256) cols_check_kernel(const ColsParams p) {
         }
     }
 
-    // failures are the rare case: a lane that found any adds them itself
-    typedef unsigned long long ull;
-    if (acc.lookup) atomicAdd(reinterpret_cast<ull *>(p.report + 2), (ull)acc.lookup);
-    if (acc.copy) atomicAdd(reinterpret_cast<ull *>(p.report + 3), (ull)acc.copy);
-    if (acc.gate) atomicAdd(reinterpret_cast<ull *>(p.report + 4), (ull)acc.gate);
-    if (acc.input) atomicAdd(reinterpret_cast<ull *>(p.report + 5), (ull)acc.input);
-    if (acc.first != ~0ull) atomicMin(reinterpret_cast<ull *>(p.report + 6), (ull)acc.first);
-    if (off_bad) atomicAdd(reinterpret_cast<ull *>(p.report + 7), (ull)off_bad);
-    if (ca.cell) atomicAdd(reinterpret_cast<ull *>(p.report + 8), (ull)ca.cell);
-    if (ca.unassigned) atomicAdd(reinterpret_cast<ull *>(p.report + 9), (ull)ca.unassigned);
-    if (ca.first != ~0ull) atomicMin(reinterpret_cast<ull *>(p.report + 10), (ull)ca.first);
+    flush_acc(p.report, acc);
+    report_add(p.report + 7, off_bad); report_add(p.report + 8, ca.cell); report_add(p.report + 9, ca.unassigned);
+    report_min(p.report + 10, ca.first);
 }
 
 // The report starts as (0 units, no failures, first = first_cell = none, 0 cells): a kernel node, not a memset node, so a
@@ -367,17 +336,14 @@ static hipError_t launch_cols_check(ColsParams &p, bool as_fr, hipStream_t s) {
     hipLaunchKernelGGL(cols_report_init_kernel, dim3(1), dim3(64), 0, s, p.report);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const uint32_t waves = 4;
-    const size_t lds = (size_t)CHK_WORDS * 4 + 768 + MASK_BYTES + (size_t)waves * G::IMG + (as_fr ? (size_t)1 << p.hbits : 0);  // 51 ... 55 KiB
+    const size_t lds = check_lds_bytes(G::IMG) + MASK_BYTES + (as_fr ? (size_t)1 << p.hbits : 0);  // 51 ... 55 KiB
     const uint32_t cs = p.k < SWEEP_LOG ? p.k : SWEEP_LOG;
     const uint64_t sweep = ((uint64_t)p.n_circuits * (3 * p.n_sets + 1)) << (p.k - cs);
     const uint64_t units = p.n > sweep ? p.n : sweep;  // sweep >= C: there is always something to check
-    uint64_t groups = (units + waves - 1) / waves;
-    if (groups > 256 * 3) groups = 256 * 3;  // three workgroups (twelve waves) per CU, every wave strides over its share of the units
-    const uint64_t nwaves = groups * waves;
+    const uint64_t groups = check_groups(units), nwaves = groups * CHECK_WAVES;
     p.run = (p.n + nwaves - 1) / nwaves;
     if (p.run == 0) p.run = 1;
-    const dim3 grid((unsigned)groups), block(waves * LANES);
+    const dim3 grid((unsigned)groups), block(CHECK_WAVES * LANES);
     if (as_fr) hipLaunchKernelGGL((cols_check_kernel<true>), grid, block, lds, s, p);
     else hipLaunchKernelGGL((cols_check_kernel<false>), grid, block, lds, s, p);
     return hipGetLastError();
@@ -472,10 +438,6 @@ static const LibHash &lib_hash() {  // searched once, when the library is loaded
 __attribute__((used)) static const int hash_at_load = lib_hash().rc;
 
 }  // namespace aesw_cols
-
-namespace {
-bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-}  // namespace
 
 extern "C" {
 

@@ -12,23 +12,17 @@
 import json
 import os
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
 import pytest
-import yaml
 
 import circ_check_cases as ccc
+from isa_extract import extract, needs_llvm, short as _short
 from test_circuits_coverage import all_kernels
 
 ROOT = Path(__file__).resolve().parent.parent
-LLVM = Path("/opt/rocm/lib/llvm/bin")
 TABLE = ROOT / "profiles" / "isa_resources_circ.json"
-TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-
-needs_llvm = pytest.mark.skipif(not (LLVM / "llvm-objdump").exists() or shutil.which("objcopy") is None or shutil.which("c++filt") is None,
-                                reason="needs the ROCm LLVM tools, objcopy and c++filt")
 
 
 def _declared():
@@ -73,30 +67,9 @@ def test_every_kernel_of_the_library_is_swept_and_the_list_names_nothing_else(pk
 
 @pytest.fixture(scope="module")
 def code_object(pkg, tmp_path_factory):
-    d = tmp_path_factory.mktemp("isa_circ")
-    fat, co = d / "fat.bin", d / "k.co"
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", str(pkg.api.CIRC_LIB_PATH), str(fat)], check=True)
-    subprocess.run([str(LLVM / "clang-offload-bundler"), "--type=o", "--targets=" + TARGET, "--input=" + str(fat),
-                    "--output=" + str(co), "--unbundle"], check=True)
-    asm = subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    meta = yaml.safe_load(notes[notes.index("---"):notes.index("...", notes.index("---"))])
-    assert meta["amdhsa.target"].endswith("gfx950"), meta["amdhsa.target"]
-    names = [k[".name"] for k in meta["amdhsa.kernels"]]
-    dem = subprocess.run(["c++filt"] + names, stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()
-    funcs, cur = {}, None
-    for line in asm.splitlines():
-        m = re.match(r"^[0-9a-f]+ <([^>]+)>:$", line)
-        if m:
-            cur = funcs.setdefault(m.group(1), [])
-            continue
-        if cur is not None and line.startswith("\t"):
-            cur.append(line.split("//")[0].strip())
-    return {"meta": {k[".name"]: k for k in meta["amdhsa.kernels"]}, "demangled": dict(zip(names, dem)), "funcs": funcs}
-
-
-def _short(demangled):
-    return re.sub(r"\(.*\)$", "", demangled.replace("void ", "")).replace(", ", ",")
+    co = extract(pkg.api.CIRC_LIB_PATH, tmp_path_factory.mktemp("isa_circ"))
+    assert co["target"].endswith("gfx950"), co["target"]
+    return co
 
 
 @needs_llvm

@@ -15,11 +15,11 @@ import subprocess
 from pathlib import Path
 
 import cols_check_cases as ccs
-from test_circ_check_library import LLVM, TARGET, _nm, _short, needs_llvm
+from isa_extract import extract, needs_llvm, short as _short
+from test_circ_check_library import _nm
 from test_circuits_coverage import all_kernels
 
 import pytest
-import yaml
 
 ROOT = Path(__file__).resolve().parent.parent
 TABLE = ROOT / "profiles" / "isa_resources_cols.json"
@@ -73,26 +73,9 @@ def test_every_kernel_of_the_library_is_swept_and_the_list_names_nothing_else(pk
 
 @pytest.fixture(scope="module")
 def code_object(pkg, tmp_path_factory):
-    d = tmp_path_factory.mktemp("isa_cols")
-    fat, co = d / "fat.bin", d / "k.co"
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", str(pkg.api.COLS_LIB_PATH), str(fat)], check=True)
-    subprocess.run([str(LLVM / "clang-offload-bundler"), "--type=o", "--targets=" + TARGET, "--input=" + str(fat),
-                    "--output=" + str(co), "--unbundle"], check=True)
-    asm = subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    meta = yaml.safe_load(notes[notes.index("---"):notes.index("...", notes.index("---"))])
-    assert meta["amdhsa.target"].endswith("gfx950"), meta["amdhsa.target"]
-    names = [k[".name"] for k in meta["amdhsa.kernels"]]
-    dem = subprocess.run(["c++filt"] + names, stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()
-    funcs, cur = {}, None
-    for line in asm.splitlines():
-        m = re.match(r"^[0-9a-f]+ <([^>]+)>:$", line)
-        if m:
-            cur = funcs.setdefault(m.group(1), [])
-            continue
-        if cur is not None and line.startswith("\t"):
-            cur.append(line.split("//")[0].strip())
-    return {"meta": {k[".name"]: k for k in meta["amdhsa.kernels"]}, "demangled": dict(zip(names, dem)), "funcs": funcs}
+    co = extract(pkg.api.COLS_LIB_PATH, tmp_path_factory.mktemp("isa_cols"))
+    assert co["target"].endswith("gfx950"), co["target"]
+    return co
 
 
 @needs_llvm

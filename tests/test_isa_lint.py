@@ -16,52 +16,25 @@ diff a reviewer sees.  Regenerate the table on purpose with  AESW_UPDATE_ISA_JSO
 import json
 import os
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import pytest
-import yaml
+
+from isa_extract import extract, needs_llvm, short
 
 ROOT = Path(__file__).resolve().parent.parent
-LLVM = Path("/opt/rocm/lib/llvm/bin")
 TABLE = ROOT / "profiles" / "isa_resources.json"
-TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-
-needs_llvm = pytest.mark.skipif(not (LLVM / "llvm-objdump").exists() or shutil.which("objcopy") is None or shutil.which("c++filt") is None,
-                                reason="needs the ROCm LLVM tools, objcopy and c++filt")
 
 
 @pytest.fixture(scope="module")
 def code_object(pkg, tmp_path_factory):
     """The gfx950 code object of the built library, its disassembly and its kernel metadata."""
-    lib = ROOT / "halo2-aes_amd" / "libaesw.so"
-    d = tmp_path_factory.mktemp("isa")
-    fat, co = d / "fat.bin", d / "k.co"
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", str(lib), str(fat)], check=True)
-    subprocess.run([str(LLVM / "clang-offload-bundler"), "--type=o", "--targets=" + TARGET, "--input=" + str(fat),
-                    "--output=" + str(co), "--unbundle"], check=True)
-    asm = subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    meta = yaml.safe_load(notes[notes.index("---"):notes.index("...", notes.index("---"))])
-    names = [k[".name"] for k in meta["amdhsa.kernels"]]
-    dem = subprocess.run(["c++filt"] + names, stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()
-    # per-function instruction lists: "<mangled>:" labels, then "\tmnemonic operands // addr: encoding"
-    funcs, cur = {}, None
-    for line in asm.splitlines():
-        m = re.match(r"^[0-9a-f]+ <([^>]+)>:$", line)
-        if m:
-            cur = funcs.setdefault(m.group(1), [])
-            continue
-        if cur is not None and line.startswith("\t"):
-            cur.append(line.split("//")[0].strip())
-    return {"meta": {k[".name"]: k for k in meta["amdhsa.kernels"]}, "demangled": dict(zip(names, dem)), "funcs": funcs}
+    return extract(ROOT / "halo2-aes_amd" / "libaesw.so", tmp_path_factory.mktemp("isa"))
 
 
 def _short(demangled):
     """aesw::encrypt_kernel<1, true, 0, true, 2>(aesw::EncParams) -> encrypt_kernel<1,true,0,true,2>"""
-    s = re.sub(r"\(.*\)$", "", demangled.replace("void ", "").replace("aesw::", ""))
-    return s.replace(", ", ",")
+    return short(demangled, drop="aesw::")
 
 
 @needs_llvm
