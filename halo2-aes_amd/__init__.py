@@ -6,7 +6,7 @@ through ``__graft_entry__.load_package()`` / ``tests/conftest.py``, which
 register it as the module ``halo2_aes_amd``.
 
 Layout:
-  csrc/        HIP kernels (gfx950) + the C ABI of include/aesw.h; the many-circuit checker of include/aesw_circ.h
+  csrc/        HIP kernels (gfx950) + the C ABI of include/aesw.h; the checkers of include/aesw_circ.h, aesw_cols.h and aesw_vals.h
   host/        C++ mirror of the reference's interface (FixedAes128Config, chips,
                Aes128KeyScheduleConfig, load_enc_full_table, MockProver) above the C ABI
   api.py       ctypes binding of the C ABI, tensor plumbing (torch); Group: one process over several GPUs

@@ -7,6 +7,7 @@
                                   entry point (hipcc), linked against libaesw.so, whose context it takes
   halo2-aes_amd/libaesw_cols.so   the checker of the assembled advice columns, bytes or Fr cells (include/aesw_cols.h): built and
                                   linked like libaesw_circ.so
+  halo2-aes_amd/libaesw_vals.so   the checker of a VALUES witness (include/aesw_vals.h): built and linked like libaesw_circ.so
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -26,6 +27,7 @@ LIB = PKG / "libaesw.so"
 HOST_LIB = PKG / "libaesw_host.so"
 CIRC_LIB = PKG / "libaesw_circ.so"
 COLS_LIB = PKG / "libaesw_cols.so"
+VALS_LIB = PKG / "libaesw_vals.so"
 
 
 def _newer(target: Path, sources) -> bool:
@@ -95,7 +97,7 @@ CIRC_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_circ_search.h", "ae
 
 
 def _checker_command(sources):
-    """libaesw_circ.so and libaesw_cols.so are built and linked alike."""
+    """libaesw_circ.so, libaesw_cols.so and libaesw_vals.so are built and linked alike."""
     return lambda tmp: [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-o", str(tmp)] + \
         [str(s) for s in sources] + ["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]
 
@@ -114,6 +116,16 @@ def build_cols(force: bool = False) -> Path:
     """libaesw_cols.so: the checker of the assembled advice columns and its entry point (hipcc, gfx950), NEEDED libaesw.so found
     next to it ($ORIGIN).  A library of its own, like libaesw_circ.so: the kernel sets of the other two stay what they are."""
     return _build(COLS_LIB, COLS_SOURCES + COLS_HEADERS + [LIB], _checker_command(COLS_SOURCES), force)
+
+
+VALS_SOURCES = [CSRC / "vals" / "aesw_vals_check.hip"]
+VALS_HEADERS = [h for h in CIRC_HEADERS[:-1] if h.name != "aesw_circ_search.h"] + [CSRC / "aesw_vals_check.h", ROOT / "include" / "aesw_vals.h"]
+
+
+def build_vals(force: bool = False) -> Path:
+    """libaesw_vals.so: the checker of a VALUES witness and its entry point (hipcc, gfx950), NEEDED libaesw.so found next to it
+    ($ORIGIN).  A library of its own, like libaesw_circ.so and libaesw_cols.so: the kernel sets of the other three stay what they are."""
+    return _build(VALS_LIB, VALS_SOURCES + VALS_HEADERS + [LIB], _checker_command(VALS_SOURCES), force)
 
 
 def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_sources=()) -> Path:

@@ -20,6 +20,7 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libaesw.so"            # HIP kernels + the C ABI of include/aesw.h
 HOST_LIB_PATH = _PKG / "libaesw_host.so"  # C++ mirror of the reference's host interface (include/aesw_host.h), above the C ABI
 COLS_LIB_PATH = _PKG / "libaesw_cols.so"  # the checker of the assembled advice columns (include/aesw_cols.h), next to libaesw.so
+VALS_LIB_PATH = _PKG / "libaesw_vals.so"  # the checker of a VALUES witness (include/aesw_vals.h), next to libaesw.so
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -181,10 +182,61 @@ COLS_SYMBOLS = {
     "aesw_cols_hash_invert": (_I, [_P, _U32, _U32, _P, _P]),
 }
 
+# include/aesw_vals.h
+VALS_SYMBOLS = {
+    "aesw_vals_check_device": (_I, [_P, _P, _P, _I, _U64, _P, _P, _P, C.POINTER(KeySlab), _P, _P]),
+    "aesw_vals_prepare": (_I, [_P]),
+    "aesw_vals_check_rows": (_U32, []),
+    "aesw_vals_check_table": (_I, [_P, _P]),
+    "aesw_vals_image_bytes": (_U32, []),
+}
+
 _lib = None
 _host_lib = None
 _circ_lib = None
 _cols_lib = None
+_vals_lib = None
+
+
+def load_vals_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_vals.so (in-tree): the checker of a VALUES witness.  It links against libaesw.so, whose contexts it takes; a
+    missing library is an error, there is no other implementation of Context.check_values."""
+    global _vals_lib
+    if _vals_lib is not None and path is None:
+        return _vals_lib
+    load_library()  # libaesw.so first: the NEEDED entry resolves to the copy already mapped
+    p = Path(path) if path else VALS_LIB_PATH
+    if not p.exists():
+        raise FileNotFoundError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                "(hipcc --offload-arch=gfx950). There is no fallback implementation." % p)
+    lib = C.CDLL(str(p))
+    for name, (res, args) in VALS_SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if path is None:
+        _vals_lib = lib
+    return lib
+
+
+def vals_check_table():
+    """aesw_vals_check_table: (words uint32[1056, 2], rows uint16[1056]) -- the resolved lookups of a VALUES block; the image
+    order and the offset encoding are in include/aesw_vals.h."""
+    lib = load_vals_library()
+    n = int(lib.aesw_vals_check_rows())
+    words, rows = np.zeros((n, 2), np.uint32), np.zeros(n, np.uint16)
+    rc = lib.aesw_vals_check_table(_np_ptr(words), _np_ptr(rows))
+    if rc:
+        raise AeswError(rc, "aesw_vals_check_table")
+    return words, rows
+
+
+def check_report_dict(rep) -> dict:
+    """The uint64[7] report tensor of Context.check_witness / check_values (sync=False), read back, as the dict sync=True returns."""
+    v = [int(x) & 0xFFFFFFFFFFFFFFFF for x in rep.cpu().tolist()]
+    first = None if v[6] == 0xFFFFFFFFFFFFFFFF else (v[6] >> 20, bool((v[6] >> 19) & 1), (v[6] >> 16) & 7, v[6] & 0xFFFF)
+    return {"blocks": v[0], "keys": v[1], "lookup_failures": v[2], "copy_failures": v[3], "gate_failures": v[4], "input_failures": v[5],
+            "first": first, "satisfied": not any(v[2:6])}
 
 
 def load_cols_library(path: Path | None = None) -> C.CDLL:
@@ -771,6 +823,30 @@ class Context:
         return {"blocks": v[0], "keys": v[1], "lookup_failures": v[2], "copy_failures": v[3], "gate_failures": v[4], "input_failures": v[5],
                 "first": first, "satisfied": not any(v[2:6])}
 
+    def check_values(self, pt, keys, witness: Witness, key_witness: KeyWitness, ct=None, sync: bool = True):
+        """MockProver::assert_satisfied over a VALUES witness on the device (aesw_vals_check_device, libaesw_vals.so): the 1 056
+        enabled lookups of every block, each x (and the y of an xor row) resolved through the copy graph to the VALUES cell, plaintext
+        byte or round-key cell it copies from, and the packed key slab(s) as check_witness checks them.  witness: the y / z of
+        encrypt_witness(layout=LAYOUT_VALUES) (x is ignored); keys: None, uint8[16] or uint8[n,16] (per-block keys: key_witness
+        then holds n key slabs).  Returns the dict of check_witness after synchronising the stream; with sync=False the uint64[7]
+        device tensor the report was written to."""
+        lib = load_vals_library()
+        torch = self._torch()
+        pt = self._u8(pt, "pt")
+        n = int(pt.shape[0])
+        pbk = keys is not None and self._u8(keys, "keys").numel() != 16
+        ks = KeySlab(*[t.data_ptr() for t in key_witness[:4]]) if key_witness is not None else None
+        rep = torch.empty(7, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_vals_check_device(
+            self._h, pt.data_ptr() if n else None, keys.data_ptr() if keys is not None else None, 1 if pbk else 0, n,
+            witness.y.data_ptr() if witness.y is not None else None, witness.z.data_ptr() if witness.z is not None else None,
+            ct.data_ptr() if ct is not None and n else None, C.byref(ks) if ks is not None else None, rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_vals_check_device")
+        if not sync:
+            return rep
+        torch.cuda.current_stream().synchronize()
+        return check_report_dict(rep)
+
     def last_stream_check(self):
         """aesw_last_stream_check: what option "stream_check" found over the chunks of the last encrypt_witness_stream call."""
         rep = CheckReport()
@@ -1142,7 +1218,7 @@ class Group(Context):
 # the device-tensor methods of Context (the C ABI refuses them on a group as well)
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
-              "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns"):
+              "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
