@@ -191,32 +191,73 @@ VALS_SYMBOLS = {
     "aesw_vals_image_bytes": (_U32, []),
 }
 
-_lib = None
-_host_lib = None
-_circ_lib = None
-_cols_lib = None
-_vals_lib = None
+_BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
+_NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
+# the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT)
+_LIBRARIES = {
+    "aesw": (LIB_PATH, SYMBOLS, _NO_FALLBACK),
+    "host": (HOST_LIB_PATH, HOST_SYMBOLS, ""),
+    "circ": (CIRC_LIB_PATH, CIRC_SYMBOLS, _NO_FALLBACK),
+    "cols": (COLS_LIB_PATH, COLS_SYMBOLS, _NO_FALLBACK),
+    "vals": (VALS_LIB_PATH, VALS_SYMBOLS, _NO_FALLBACK),
+}
+_loaded = {}  # name -> the CDLL of the default path
 
 
-def load_vals_library(path: Path | None = None) -> C.CDLL:
-    """Load libaesw_vals.so (in-tree): the checker of a VALUES witness.  It links against libaesw.so, whose contexts it takes; a
-    missing library is an error, there is no other implementation of Context.check_values."""
-    global _vals_lib
-    if _vals_lib is not None and path is None:
-        return _vals_lib
-    load_library()  # libaesw.so first: the NEEDED entry resolves to the copy already mapped
-    p = Path(path) if path else VALS_LIB_PATH
+def _load(name: str, path) -> C.CDLL:
+    """The library `name` with every declared symbol bound (AttributeError if its ABI is incomplete).  The default path is
+    loaded once; an explicit path is loaded anew and never cached.  A missing library is an error: there is no fallback."""
+    if path is None and name in _loaded:
+        return _loaded[name]
+    default, symbols, hint = _LIBRARIES[name]
+    if name == "aesw":
+        # torch ships its own libamdhip64.so.7 and dlopen()s it by path.  Import it
+        # FIRST so libaesw.so's NEEDED libamdhip64.so.7 binds to that copy: two HIP
+        # runtimes in one process do not share the device (hipGetDeviceCount fails
+        # in the second one).  A host without torch (the Rust caller) uses /opt/rocm's.
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+    else:
+        _load("aesw", None)  # libaesw.so first: the NEEDED entry resolves to the copy already mapped
+    p = Path(path) if path else default
     if not p.exists():
-        raise FileNotFoundError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                "(hipcc --offload-arch=gfx950). There is no fallback implementation." % p)
-    lib = C.CDLL(str(p))
-    for name, (res, args) in VALS_SYMBOLS.items():
-        fn = getattr(lib, name)
+        raise FileNotFoundError((_BUILD_IT + hint) % p)
+    lib = C.CDLL(str(p))  # RTLD_LOCAL: two builds of a library can sit in one process (tools/ab_lib.py)
+    for sym, (res, args) in symbols.items():
+        fn = getattr(lib, sym)
         fn.restype = res
         fn.argtypes = args
     if path is None:
-        _vals_lib = lib
+        _loaded[name] = lib
     return lib
+
+
+def load_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw.so (in-tree).  Raises if it has not been built."""
+    return _load("aesw", path)
+
+
+def load_host_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_host.so (in-tree): the host-side mirror.  It links against libaesw.so and holds no device code."""
+    return _load("host", path)
+
+
+def load_circ_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_circ.so (in-tree): the many-circuit checker behind Context.check_circuits.  It links against libaesw.so,
+    whose contexts it takes."""
+    return _load("circ", path)
+
+
+def load_cols_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_cols.so (in-tree): the checker of the assembled advice columns behind Context.check_columns."""
+    return _load("cols", path)
+
+
+def load_vals_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_vals.so (in-tree): the checker of a VALUES witness behind Context.check_values."""
+    return _load("vals", path)
 
 
 def vals_check_table():
@@ -231,101 +272,54 @@ def vals_check_table():
     return words, rows
 
 
-def check_report_dict(rep) -> dict:
-    """The uint64[7] report tensor of Context.check_witness / check_values (sync=False), read back, as the dict sync=True returns."""
-    v = [int(x) & 0xFFFFFFFFFFFFFFFF for x in rep.cpu().tolist()]
-    first = None if v[6] == 0xFFFFFFFFFFFFFFFF else (v[6] >> 20, bool((v[6] >> 19) & 1), (v[6] >> 16) & 7, v[6] & 0xFFFF)
+_NONE = 0xFFFFFFFFFFFFFFFF  # `first` / `first_cell` of a report that found nothing (-1 as int64)
+
+
+def _words(rep) -> list:
+    """A report tensor (int64 on any device) read back as unsigned 64-bit words."""
+    return [int(x) & _NONE for x in rep.cpu().tolist()]
+
+
+def _decode(v) -> dict:
+    """The seven words every report starts with (the fields of CheckReport, in order) as the dict of Context.check_witness."""
+    first = None if v[6] == _NONE else (v[6] >> 20, bool((v[6] >> 19) & 1), (v[6] >> 16) & 7, v[6] & 0xFFFF)
     return {"blocks": v[0], "keys": v[1], "lookup_failures": v[2], "copy_failures": v[3], "gate_failures": v[4], "input_failures": v[5],
             "first": first, "satisfied": not any(v[2:6])}
 
 
-def load_cols_library(path: Path | None = None) -> C.CDLL:
-    """Load libaesw_cols.so (in-tree): the checker of the assembled advice columns.  It links against libaesw.so, whose contexts
-    it takes; a missing library is an error, there is no other implementation of Context.check_columns."""
-    global _cols_lib
-    if _cols_lib is not None and path is None:
-        return _cols_lib
-    load_library()  # libaesw.so first: the NEEDED entry resolves to the copy already mapped
-    p = Path(path) if path else COLS_LIB_PATH
-    if not p.exists():
-        raise FileNotFoundError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                "(hipcc --offload-arch=gfx950). There is no fallback implementation." % p)
-    lib = C.CDLL(str(p))
-    for name, (res, args) in COLS_SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _cols_lib = lib
-    return lib
+def _decode_struct(rep: CheckReport) -> dict:
+    return _decode([int(getattr(rep, f)) for f, _ in CheckReport._fields_])
 
 
-def load_circ_library(path: Path | None = None) -> C.CDLL:
-    """Load libaesw_circ.so (in-tree): the many-circuit checker.  It links against libaesw.so, whose contexts it takes; a missing
-    library is an error, there is no other implementation of Context.check_circuits."""
-    global _circ_lib
-    if _circ_lib is not None and path is None:
-        return _circ_lib
-    load_library()  # libaesw.so first: the NEEDED entry resolves to the copy already mapped
-    p = Path(path) if path else CIRC_LIB_PATH
-    if not p.exists():
-        raise FileNotFoundError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                "(hipcc --offload-arch=gfx950). There is no fallback implementation." % p)
-    lib = C.CDLL(str(p))
-    for name, (res, args) in CIRC_SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _circ_lib = lib
-    return lib
+def check_report_dict(rep) -> dict:
+    """The uint64[7] report tensor of Context.check_witness / check_values (sync=False), read back, as the dict sync=True returns."""
+    return _decode(_words(rep))
 
 
-def load_host_library(path: Path | None = None) -> C.CDLL:
-    """Load libaesw_host.so (in-tree): the host-side mirror.  It links against libaesw.so and holds no device code."""
-    global _host_lib
-    if _host_lib is not None and path is None:
-        return _host_lib
-    load_library()  # libaesw.so first: the mirror's NEEDED entry resolves to the copy already mapped
-    p = Path(path) if path else HOST_LIB_PATH
-    if not p.exists():
-        raise FileNotFoundError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`" % p)
-    lib = C.CDLL(str(p))
-    for name, (res, args) in HOST_SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _host_lib = lib
-    return lib
+def circ_report_dict(rep) -> dict:
+    """The uint64[8] report tensor of Context.check_circuits(sync=False), read back, as the dict sync=True returns."""
+    v = _words(rep)
+    out = _decode(v)
+    out.update(offset_failures=v[7], satisfied=out["satisfied"] and v[7] == 0)
+    return out
 
 
-def load_library(path: Path | None = None) -> C.CDLL:
-    """Load libaesw.so (in-tree).  Raises if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = Path(path) if path else LIB_PATH
-    # torch ships its own libamdhip64.so.7 and dlopen()s it by path.  Import it
-    # FIRST so libaesw.so's NEEDED libamdhip64.so.7 binds to that copy: two HIP
-    # runtimes in one process do not share the device (hipGetDeviceCount fails
-    # in the second one).  A host without torch (the Rust caller) uses /opt/rocm's.
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not p.exists():
-        raise FileNotFoundError(
-            "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). There is no fallback implementation." % p)
-    lib = C.CDLL(str(p))  # RTLD_LOCAL: two builds of the library can sit in one process (tools/ab_lib.py)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _lib = lib
-    return lib
+def cols_report_dict(rep) -> dict:
+    """The uint64[12] report tensor of Context.check_columns(sync=False), read back, as the dict sync=True returns."""
+    v = _words(rep)
+    out = circ_report_dict(rep[:8])
+    out.update(cell_failures=v[8], unassigned_failures=v[9], first_cell=None if v[10] == _NONE else v[10], cells=v[11],
+               satisfied=out["satisfied"] and v[8] == 0 and v[9] == 0)
+    return out
+
+
+def _ptr(x):
+    """An optional argument as ctypes takes it: None, a reference to a structure, a numpy array's or a tensor's address."""
+    if x is None:
+        return None
+    if isinstance(x, C.Structure):
+        return C.byref(x)
+    return _np_ptr(x) if isinstance(x, np.ndarray) else x.data_ptr()
 
 
 def _strerror(status: int) -> str:
@@ -496,23 +490,6 @@ def host_free(arr: np.ndarray):
 _pinned = {}
 
 
-def circ_report_dict(rep) -> dict:
-    """The uint64[8] report tensor of Context.check_circuits(sync=False), read back, as the dict sync=True returns."""
-    v = [int(x) & 0xFFFFFFFFFFFFFFFF for x in rep.cpu().tolist()]
-    first = None if v[6] == 0xFFFFFFFFFFFFFFFF else (v[6] >> 20, bool((v[6] >> 19) & 1), (v[6] >> 16) & 7, v[6] & 0xFFFF)
-    return {"blocks": v[0], "keys": v[1], "lookup_failures": v[2], "copy_failures": v[3], "gate_failures": v[4], "input_failures": v[5],
-            "first": first, "offset_failures": v[7], "satisfied": not any(v[2:6]) and v[7] == 0}
-
-
-def cols_report_dict(rep) -> dict:
-    """The uint64[12] report tensor of Context.check_columns(sync=False), read back, as the dict sync=True returns."""
-    v = [int(x) & 0xFFFFFFFFFFFFFFFF for x in rep.cpu().tolist()]
-    out = circ_report_dict(rep[:8])
-    out.update(cell_failures=v[8], unassigned_failures=v[9], first_cell=None if v[10] == 0xFFFFFFFFFFFFFFFF else v[10], cells=v[11])
-    out["satisfied"] = out["satisfied"] and v[8] == 0 and v[9] == 0
-    return out
-
-
 Witness = namedtuple("Witness", "x y z ct key")
 KeyWitness = namedtuple("KeyWitness", "w kx ky kz rk")
 
@@ -671,7 +648,7 @@ class Context:
                              *[torch.empty(key_column_stride(layout, c), dtype=torch.uint8, device=dev) for c in range(3)],
                              None)
             ks = KeySlab(*[t.data_ptr() for t in out[:4]])
-        rc = self._lib.aesw_schedule_key_device(self._h, key.data_ptr(), layout, C.byref(ks) if ks is not None else None,
+        rc = self._lib.aesw_schedule_key_device(self._h, key.data_ptr(), layout, _ptr(ks),
                                                 self._stream())
         self._check(rc, "aesw_schedule_key_device")
         return out
@@ -711,12 +688,12 @@ class Context:
                 raise ValueError("column %s too small" % name)
         ks = None
         if out.key is not None:
-            ks = KeySlab(*[t.data_ptr() if t is not None else None for t in out.key[:4]])
+            ks = KeySlab(*[_ptr(t) for t in out.key[:4]])
         rc = self._lib.aesw_encrypt_witness_device(
-            self._h, pt.data_ptr(), keys.data_ptr() if keys is not None else None, pbk, n, layout,
+            self._h, pt.data_ptr(), _ptr(keys), pbk, n, layout,
             out.x.data_ptr() if out.x.numel() else None, out.y.data_ptr(),
-            out.z.data_ptr(), out.ct.data_ptr() if out.ct is not None else None,
-            C.byref(ks) if ks is not None else None, self._stream())
+            out.z.data_ptr(), _ptr(out.ct),
+            _ptr(ks), self._stream())
         self._check(rc, "aesw_encrypt_witness_device")
         return out
 
@@ -743,11 +720,11 @@ class Context:
                     raise ValueError("column %s of batch %d too small" % (name, i))
             ks = None
             if out.key is not None:
-                ks = KeySlab(*[t.data_ptr() if t is not None else None for t in out.key[:4]])
+                ks = KeySlab(*[_ptr(t) for t in out.key[:4]])
                 keep.append(ks)
-            arr[i] = Batch(pt.data_ptr(), keys.data_ptr() if keys is not None else None, n,
+            arr[i] = Batch(pt.data_ptr(), _ptr(keys), n,
                            out.x.data_ptr() if out.x.numel() else None, out.y.data_ptr(), out.z.data_ptr(),
-                           out.ct.data_ptr() if out.ct is not None else None, C.pointer(ks) if ks is not None else None)
+                           _ptr(out.ct), C.pointer(ks) if ks is not None else None)
             keep.append((pt, keys))
         rc = self._lib.aesw_encrypt_witness_batches_device(self._h, arr, len(batches), 1 if per_block_keys else 0, layout, self._stream())
         self._check(rc, "aesw_encrypt_witness_batches_device")
@@ -775,7 +752,7 @@ class Context:
         rk = torch.empty((n, 176), dtype=torch.uint8, device=dev) if want_rk else None
         rc = self._lib.aesw_key_schedule_witness_device(
             self._h, keys.data_ptr(), n, layout, w.data_ptr(), kx.data_ptr(), ky.data_ptr(), kz.data_ptr(),
-            rk.data_ptr() if rk is not None else None, self._stream())
+            _ptr(rk), self._stream())
         self._check(rc, "aesw_key_schedule_witness_device")
         return KeyWitness(w, kx, ky, kz, rk)
 
@@ -799,6 +776,13 @@ class Context:
         self._check(rc, "aesw_expand_fr_device")
         return out
 
+    def _report(self, rep, sync: bool, decode):
+        """The end of every check_*: the report tensor as it is, or synchronise the stream and decode it."""
+        if not sync:
+            return rep
+        self._torch().cuda.current_stream().synchronize()
+        return decode(rep)
+
     def check_witness(self, pt, keys, witness: Witness, key_witness: KeyWitness, layout: int = K.LAYOUT_PACKED, ct=None, sync: bool = True):
         """MockProver::assert_satisfied over a batch on the device (aesw_check_witness_device; src/aes128.rs:409-418): every
         enabled lookup, every copy_advice() pair, the round-constant gate and the literal rows of n blocks and their key slab(s).
@@ -812,16 +796,10 @@ class Context:
         ks = KeySlab(*[t.data_ptr() for t in key_witness[:4]])
         rep = torch.empty(7, dtype=torch.int64, device=self._dev())
         rc = self._lib.aesw_check_witness_device(
-            self._h, pt.data_ptr(), keys.data_ptr() if keys is not None else None, 1 if pbk else 0, n, layout, witness.x.data_ptr(),
-            witness.y.data_ptr(), witness.z.data_ptr(), ct.data_ptr() if ct is not None else None, C.byref(ks), rep.data_ptr(), self._stream())
+            self._h, pt.data_ptr(), _ptr(keys), 1 if pbk else 0, n, layout, witness.x.data_ptr(),
+            witness.y.data_ptr(), witness.z.data_ptr(), _ptr(ct), C.byref(ks), rep.data_ptr(), self._stream())
         self._check(rc, "aesw_check_witness_device")
-        if not sync:
-            return rep
-        torch.cuda.current_stream().synchronize()
-        v = [int(x) & 0xFFFFFFFFFFFFFFFF for x in rep.cpu().tolist()]
-        first = None if v[6] == 0xFFFFFFFFFFFFFFFF else (v[6] >> 20, bool((v[6] >> 19) & 1), (v[6] >> 16) & 7, v[6] & 0xFFFF)
-        return {"blocks": v[0], "keys": v[1], "lookup_failures": v[2], "copy_failures": v[3], "gate_failures": v[4], "input_failures": v[5],
-                "first": first, "satisfied": not any(v[2:6])}
+        return self._report(rep, sync, check_report_dict)
 
     def check_values(self, pt, keys, witness: Witness, key_witness: KeyWitness, ct=None, sync: bool = True):
         """MockProver::assert_satisfied over a VALUES witness on the device (aesw_vals_check_device, libaesw_vals.so): the 1 056
@@ -838,24 +816,16 @@ class Context:
         ks = KeySlab(*[t.data_ptr() for t in key_witness[:4]]) if key_witness is not None else None
         rep = torch.empty(7, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_vals_check_device(
-            self._h, pt.data_ptr() if n else None, keys.data_ptr() if keys is not None else None, 1 if pbk else 0, n,
-            witness.y.data_ptr() if witness.y is not None else None, witness.z.data_ptr() if witness.z is not None else None,
-            ct.data_ptr() if ct is not None and n else None, C.byref(ks) if ks is not None else None, rep.data_ptr(), self._stream())
+            self._h, pt.data_ptr() if n else None, _ptr(keys), 1 if pbk else 0, n, _ptr(witness.y), _ptr(witness.z),
+            ct.data_ptr() if ct is not None and n else None, _ptr(ks), rep.data_ptr(), self._stream())
         self._check(rc, "aesw_vals_check_device")
-        if not sync:
-            return rep
-        torch.cuda.current_stream().synchronize()
-        return check_report_dict(rep)
+        return self._report(rep, sync, check_report_dict)
 
     def last_stream_check(self):
         """aesw_last_stream_check: what option "stream_check" found over the chunks of the last encrypt_witness_stream call."""
         rep = CheckReport()
         self._check(self._lib.aesw_last_stream_check(self._h, C.byref(rep)), "aesw_last_stream_check")
-        f = int(rep.first)
-        out = {k_: int(getattr(rep, k_)) for k_ in ("blocks", "keys", "lookup_failures", "copy_failures", "gate_failures", "input_failures")}
-        out.update(first=None if f == 0xFFFFFFFFFFFFFFFF else (f >> 20, bool((f >> 19) & 1), (f >> 16) & 7, f & 0xFFFF),
-                   satisfied=not any(out[k_] for k_ in ("lookup_failures", "copy_failures", "gate_failures", "input_failures")))
-        return out
+        return _decode_struct(rep)
 
     def check_witness_host(self, pt, keys, cols, key_cols, layout: int = K.LAYOUT_PACKED, ct=None):
         """aesw_check_witness: the same check for a witness in HOST memory (numpy uint8 arrays: cols = (x, y, z), key_cols =
@@ -866,17 +836,12 @@ class Context:
         keys = None if keys is None else np.ascontiguousarray(keys, np.uint8)
         pbk = keys is not None and keys.size != 16
         keep = [np.ascontiguousarray(a, np.uint8) for a in (*cols, *key_cols)] + ([np.ascontiguousarray(ct, np.uint8)] if ct is not None else [])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         ks = KeySlab(*[a.ctypes.data for a in keep[3:7]])
         rep = CheckReport()
-        rc = self._lib.aesw_check_witness(self._h, p(pt), p(keys) if keys is not None else None, 1 if pbk else 0, n, layout, p(keep[0]), p(keep[1]),
-                                          p(keep[2]), p(keep[7]) if ct is not None else None, C.byref(ks), C.byref(rep))
+        rc = self._lib.aesw_check_witness(self._h, _np_ptr(pt), _ptr(keys), 1 if pbk else 0, n, layout, *[_np_ptr(a) for a in keep[:3]],
+                                          _np_ptr(keep[7]) if ct is not None else None, C.byref(ks), C.byref(rep))
         self._check(rc, "aesw_check_witness")
-        f = int(rep.first)
-        first = None if f == 0xFFFFFFFFFFFFFFFF else (f >> 20, bool((f >> 19) & 1), (f >> 16) & 7, f & 0xFFFF)
-        out = {k_: int(getattr(rep, k_)) for k_ in ("blocks", "keys", "lookup_failures", "copy_failures", "gate_failures", "input_failures")}
-        out.update(first=first, satisfied=not any(out[k_] for k_ in ("lookup_failures", "copy_failures", "gate_failures", "input_failures")))
-        return out
+        return _decode_struct(rep)
 
     def assemble_advice(self, k: int, n_sets: int, witness: Witness, key_witness: KeyWitness | None, n_blocks: int,
                         layout: int = K.LAYOUT_PACKED, as_fr: bool = False, out=None):
@@ -893,13 +858,31 @@ class Context:
         ks = KeySlab(*[t.data_ptr() for t in key_witness[:4]]) if key_witness is not None else None
         rc = self._lib.aesw_assemble_advice_device(
             self._h, k, n_sets, n_blocks, layout, witness.x.data_ptr(), witness.y.data_ptr(), witness.z.data_ptr(),
-            C.byref(ks) if ks is not None else None, 1 if as_fr else 0, out.data_ptr(), self._stream())
+            _ptr(ks), 1 if as_fr else 0, out.data_ptr(), self._stream())
         self._check(rc, "aesw_assemble_advice_device")
         return out
 
     # -- many circuits per launch
     def _offsets_tensor(self, offs: np.ndarray):
         return self._torch().from_numpy(offs.view(np.int64)).to(self._dev())
+
+    def _circuit_args(self, k: int, n_sets: int, n: int, counts, keys, _offsets=None):
+        """What the many-circuit entry points share: (C, the device int64[C+1] block offsets) of `counts` over n blocks,
+        validated on the host unless `_offsets` is handed in, and keys checked to be None or uint8[C,16]."""
+        nc = len(counts)
+        if _offsets is None:
+            _offsets = self._offsets_tensor(circuit_offsets(k, n_sets, counts, n))
+        elif int(_offsets.numel()) != nc + 1:
+            raise ValueError("_offsets must hold len(counts) + 1 entries")
+        if keys is not None and tuple(self._u8(keys, "keys").shape) != (nc, 16):
+            raise ValueError("keys must be [C,16] for C = len(counts)")
+        return nc, _offsets
+
+    def _key_slabs(self, key_witness, nc: int) -> KeySlab:
+        """The aesw_key_slab of a key_witness that holds (at least) nc key slabs."""
+        if key_witness is None or int(key_witness.w.numel()) < nc * K.WORDS_ROWS:
+            raise ValueError("key_witness must hold one key slab per circuit")
+        return KeySlab(*[self._u8(t, "key_witness").data_ptr() for t in key_witness[:4]])
 
     def assemble_advice_circuits(self, k: int, n_sets: int, witness: Witness, key_witness: KeyWitness, counts, as_fr: bool = False,
                                  layout: int = K.LAYOUT_PACKED, n_blocks: int | None = None, out=None, _offsets=None):
@@ -911,8 +894,7 @@ class Context:
             n_blocks = int(witness.y.numel()) // column_stride(layout, 1)
         offs = circuit_offsets(k, n_sets, counts, n_blocks)
         nc = len(offs) - 1
-        if key_witness is None or int(key_witness.w.numel()) < nc * K.WORDS_ROWS:
-            raise ValueError("key_witness must hold one key slab per circuit")
+        ks = self._key_slabs(key_witness, nc)
         torch = self._torch()
         shape = (nc, 3 * n_sets + 1, 1 << k) + ((32,) if as_fr else ())
         if out is None:
@@ -920,7 +902,6 @@ class Context:
         elif tuple(out.shape) != shape:
             raise ValueError("out must have shape %r" % (shape,))
         self._u8(out, "out")
-        ks = KeySlab(*[self._u8(t, "key_witness").data_ptr() for t in key_witness[:4]])
         d_offs = self._offsets_tensor(offs) if _offsets is None else _offsets
         rc = self._lib.aesw_assemble_advice_circuits_device(
             self._h, k, n_sets, nc, d_offs.data_ptr(), layout, witness.x.data_ptr(), witness.y.data_ptr(), witness.z.data_ptr(),
@@ -941,28 +922,15 @@ class Context:
         torch = self._torch()
         pt = self._u8(pt, "pt")
         n = int(pt.shape[0])
-        nc = len(counts)
-        if _offsets is None:
-            d_offs = self._offsets_tensor(circuit_offsets(k, n_sets, counts, n))
-        else:
-            d_offs = _offsets
-            if int(d_offs.numel()) != nc + 1:
-                raise ValueError("_offsets must hold len(counts) + 1 entries")
-        if keys is not None and tuple(self._u8(keys, "keys").shape) != (nc, 16):
-            raise ValueError("keys must be [C,16] for C = len(counts)")
-        if key_witness is None or int(key_witness.w.numel()) < nc * K.WORDS_ROWS:
-            raise ValueError("key_witness must hold one key slab per circuit")
-        ks = KeySlab(*[self._u8(t, "key_witness").data_ptr() for t in key_witness[:4]])
+        nc, d_offs = self._circuit_args(k, n_sets, n, counts, keys, _offsets)
+        ks = self._key_slabs(key_witness, nc)
         rep = torch.empty(8, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_circ_check_witness_device(
-            self._h, k, n_sets, nc, d_offs.data_ptr(), n, pt.data_ptr() if n else None, keys.data_ptr() if keys is not None else None, layout,
+            self._h, k, n_sets, nc, d_offs.data_ptr(), n, pt.data_ptr() if n else None, _ptr(keys), layout,
             witness.x.data_ptr() if n else None, witness.y.data_ptr() if n else None, witness.z.data_ptr() if n else None,
             ct.data_ptr() if ct is not None and n else None, C.byref(ks), rep.data_ptr(), self._stream())
         self._check(rc, "aesw_circ_check_witness_device")
-        if not sync:
-            return rep
-        torch.cuda.current_stream().synchronize()
-        return circ_report_dict(rep)
+        return self._report(rep, sync, circ_report_dict)
 
     def check_columns(self, k: int, n_sets: int, pt, keys, advice, counts, ct=None, sync: bool = True, _offsets=None):
         """MockProver::assert_satisfied over the ASSEMBLED advice columns of C FixedAes128Config<k, n_sets> circuits in one launch
@@ -985,41 +953,27 @@ class Context:
             as_fr = len(shape) == 3
         else:
             raise ValueError("advice must be [C, 3*n_sets+1, 2^k] bytes or [C, 3*n_sets+1, 2^k, 32] Fr cells")
-        if _offsets is None:
-            d_offs = self._offsets_tensor(circuit_offsets(k, n_sets, counts, n))
-        else:
-            d_offs = _offsets
-            if int(d_offs.numel()) != nc + 1:
-                raise ValueError("_offsets must hold len(counts) + 1 entries")
-        if keys is not None and tuple(self._u8(keys, "keys").shape) != (nc, 16):
-            raise ValueError("keys must be [C,16] for C = len(counts)")
+        nc, d_offs = self._circuit_args(k, n_sets, n, counts, keys, _offsets)
         if ct is not None and tuple(self._u8(ct, "ct").shape) != (n, 16):
             raise ValueError("ct must be [n,16]")
         rep = torch.empty(12, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_cols_check_device(
-            self._h, k, n_sets, nc, d_offs.data_ptr(), n, pt.data_ptr() if n else None, keys.data_ptr() if keys is not None else None,
+            self._h, k, n_sets, nc, d_offs.data_ptr(), n, pt.data_ptr() if n else None, _ptr(keys),
             ct.data_ptr() if ct is not None and n else None, 1 if as_fr else 0, advice.data_ptr(), rep.data_ptr(), self._stream())
         self._check(rc, "aesw_cols_check_device")
-        if not sync:
-            return rep
-        torch.cuda.current_stream().synchronize()
-        return cols_report_dict(rep)
+        return self._report(rep, sync, cols_report_dict)
 
     def circuits(self, k: int, n_sets: int, keys, pt, counts, as_fr: bool = True):
         """C FixedAes128Config<k, n_sets> circuits on torch's current stream: the key schedule of keys (uint8[C,16]), the
         witness of pt (uint8[n,16]; circuit c takes the next counts[c] blocks) with each block under its circuit's key, and
         the advice columns of every circuit in one launch.  Returns (witness, key_witness, advice): the PACKED block slabs and
         ciphertexts, the C key slabs and advice [C, 3*n_sets+1, 2^k] (bytes) or [..., 32] (Fr)."""
-        offs = circuit_offsets(k, n_sets, counts, int(pt.shape[0]))
-        keys = self._u8(keys, "keys")
-        if tuple(keys.shape) != (len(offs) - 1, 16):
-            raise ValueError("keys must be [C,16] for C = len(counts)")
+        n = int(pt.shape[0])
+        _nc, d_offs = self._circuit_args(k, n_sets, n, counts, keys)  # counts first, then keys (uint8[C,16])
         torch = self._torch()
-        d_offs = self._offsets_tensor(offs)
         kw = self.key_schedule_witness(keys, K.LAYOUT_PACKED, want_rk=False)
         # every block under its circuit's key: the per-block-key launch on the keys gathered by circuit (16 B per block)
         per_block = torch.repeat_interleave(keys, torch.as_tensor(counts, dtype=torch.int64, device=keys.device), dim=0)
-        n = int(pt.shape[0])
         wit = self.encrypt_witness(pt, per_block, K.LAYOUT_PACKED, want_ct=True) if n else \
             self.alloc_witness(1, K.LAYOUT_PACKED, want_ct=True)  # no block: key rows only (the slabs are never read)
         adv = self.assemble_advice_circuits(k, n_sets, wit, kw, counts, as_fr=as_fr, n_blocks=n, _offsets=d_offs)
@@ -1048,9 +1002,9 @@ class Context:
             key = KeyWitness(np.empty(m * K.WORDS_ROWS, np.uint8),
                              *[np.empty(m * key_column_stride(layout, c), np.uint8) for c in range(3)], None)
             ks = KeySlab(*[a.ctypes.data for a in key[:4]])
-        rc = self._lib.aesw_encrypt_witness(self._h, _np_ptr(pt), _np_ptr(keys) if keys is not None else None, pbk, n, layout,
+        rc = self._lib.aesw_encrypt_witness(self._h, _np_ptr(pt), _ptr(keys), pbk, n, layout,
                                             *[_np_ptr(c) for c in cols],
-                                            _np_ptr(ct) if ct is not None else None, C.byref(ks) if ks is not None else None)
+                                            _ptr(ct), _ptr(ks))
         self._check(rc, "aesw_encrypt_witness")
         return Witness(cols[0], cols[1], cols[2], ct, key)
 
@@ -1077,7 +1031,7 @@ class Context:
                 err.append(e)
                 return 1
 
-        rc = self._lib.aesw_encrypt_witness_stream(self._h, _np_ptr(pt), _np_ptr(keys) if keys is not None else None, pbk, n,
+        rc = self._lib.aesw_encrypt_witness_stream(self._h, _np_ptr(pt), _ptr(keys), pbk, n,
                                                    layout, C.cast(cb, C.c_void_p), None)
         if err:
             raise err[0]
@@ -1109,7 +1063,7 @@ class Context:
         ks = KeySlab(*[t.data_ptr() for t in key_witness[:4]]) if key_witness is not None else None
         rc = self._lib.aesw_assemble_advice_stream(
             self._h, k, n_sets, n_blocks, layout, witness.x.data_ptr(), witness.y.data_ptr(), witness.z.data_ptr(),
-            C.byref(ks) if ks is not None else None, 1 if as_fr else 0, C.cast(cb, C.c_void_p), None)
+            _ptr(ks), 1 if as_fr else 0, C.cast(cb, C.c_void_p), None)
         if err:
             raise err[0]
         self._check(rc, "aesw_assemble_advice_stream")
@@ -1125,7 +1079,7 @@ class Context:
         ks = KeySlab(*[t.data_ptr() for t in key_witness[:4]]) if key_witness is not None else None
         rc = self._lib.aesw_assemble_advice_host(
             self._h, k, n_sets, n_blocks, layout, witness.x.data_ptr(), witness.y.data_ptr(), witness.z.data_ptr(),
-            C.byref(ks) if ks is not None else None, 1 if as_fr else 0, _np_ptr(out))
+            _ptr(ks), 1 if as_fr else 0, _np_ptr(out))
         self._check(rc, "aesw_assemble_advice_host")
         return out
 
@@ -1150,7 +1104,7 @@ class Context:
         if key_slab:
             kw = KeyWitness(np.empty(K.WORDS_ROWS, np.uint8), *[np.empty(key_column_stride(layout, c), np.uint8) for c in range(3)], None)
             ks = KeySlab(*[a.ctypes.data for a in kw[:4]])
-        rc = self._lib.aesw_schedule_key(self._h, _np_ptr(key), layout, C.byref(ks) if ks is not None else None)
+        rc = self._lib.aesw_schedule_key(self._h, _np_ptr(key), layout, _ptr(ks))
         self._check(rc, "aesw_schedule_key")
         return kw
 
@@ -1191,7 +1145,7 @@ class Group(Context):
             if t.shape != (256,):
                 raise ValueError("tables must be three uint8[256] arrays")
         devs = None if devices is None else np.ascontiguousarray(list(devices), dtype=np.intc)
-        rc = self._lib.aesw_create_group(C.byref(self._h), _np_ptr(devs) if devs is not None else None,
+        rc = self._lib.aesw_create_group(C.byref(self._h), _ptr(devs),
                                          0 if devs is None else devs.size, *[_np_ptr(t) for t in self._tables])
         if rc:
             self._h = C.c_void_p()

@@ -147,7 +147,7 @@ int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys
     const CheckGeo cg = check_geo(layout);
     CheckParams p{};
     p.pt = d_pt; p.keys = d_keys; p.x = d_x; p.y = d_y; p.z = d_z; p.ct = d_ct;
-    if (ks) { p.kw = ks->w; p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
+    if (ks) set_key_slab(p, ks);
     p.table = ctx->d_chktab[li];
     p.tab768 = ctx->d_tables;
     p.report = reinterpret_cast<uint64_t *>(d_report);

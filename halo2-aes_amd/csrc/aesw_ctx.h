@@ -136,6 +136,10 @@ struct DeviceGuard {
 void aesw_arena_cache_trim(aesw_ctx *ctx, uint64_t keep_bytes);  // aesw_arena.cpp: release cached arenas, oldest first, until keep_bytes stay
 
 inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }  // a: a power of two
+// a key slab a checker library reads 16 bytes at a time: all four columns there and 16-byte aligned
+inline bool key_slab_ok(const aesw_key_slab *ks) {
+    return ks && ks->w && ks->kx && ks->ky && ks->kz && aligned_to(ks->w, 16) && aligned_to(ks->kx, 16) && aligned_to(ks->ky, 16) && aligned_to(ks->kz, 16);
+}
 inline bool aesw_valid_layout(int l) { return l == AESW_LAYOUT_DENSE || l == AESW_LAYOUT_PACKED || l == AESW_LAYOUT_VALUES; }
 
 // What aesw_hostpath.cpp takes from aesw_api.cpp, and the one thing aesw_get_option takes back (AESW_INTERNAL: aesw_keyring.h).

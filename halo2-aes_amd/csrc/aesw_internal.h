@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/aesw.h"
 #include "aesw_check.h"
 
 namespace aesw {
@@ -88,6 +89,7 @@ struct CheckParams {
     uint32_t skip_shared_key;   // one key slab for the batch: do not check it in this launch (a later chunk of a host-pointer call)
     uint32_t sx, sy, sz, kxs, kys, kzs, bi, img;  // strides, block image bytes, bytes of one wave's image region
 };
+inline void set_key_slab(CheckParams &p, const aesw_key_slab *ks) { p.kw = ks->w; p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
 hipError_t launch_check(const CheckParams &p, hipStream_t s);
 // The launch geometry of the three checker kernels (check_kernel, circ_check_kernel, cols_check_kernel): four waves per
 // workgroup, one unit per wave at a time, and at most three workgroups (twelve waves) for each of the 256 CUs -- every wave

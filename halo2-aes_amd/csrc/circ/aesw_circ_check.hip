@@ -122,9 +122,7 @@ int aesw_circ_check_witness_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, u
         n_circuits == 0 || !d_offsets || !aligned_to(d_offsets, 8) || !d_report || !aligned_to(d_report, 8))
         return AESW_ERR_INVALID_ARG;
     const aesw_key_slab *ks = d_key_slabs;
-    if (!ks || !ks->w || !ks->kx || !ks->ky || !ks->kz || !aligned_to(ks->w, 16) || !aligned_to(ks->kx, 16) || !aligned_to(ks->ky, 16) ||
-        !aligned_to(ks->kz, 16) || !aligned_to(d_keys, 4))
-        return AESW_ERR_INVALID_ARG;
+    if (!key_slab_ok(ks) || !aligned_to(d_keys, 4)) return AESW_ERR_INVALID_ARG;
     if (n && (!d_pt || !d_x || !d_y || !d_z || !aligned_to(d_pt, 4) || !aligned_to(d_ct, 4) || !aligned_to(d_x, 16) || !aligned_to(d_y, 16) ||
               !aligned_to(d_z, 16)))
         return AESW_ERR_INVALID_ARG;
@@ -134,7 +132,7 @@ int aesw_circ_check_witness_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, u
     const aesw::CheckGeo cg = aesw::check_geo(layout);
     aesw_circ::CircCheckParams p{};
     p.c.pt = d_pt; p.c.keys = d_keys; p.c.x = d_x; p.c.y = d_y; p.c.z = d_z; p.c.ct = d_ct;
-    p.c.kw = ks->w; p.c.kx = ks->kx; p.c.ky = ks->ky; p.c.kz = ks->kz;
+    aesw::set_key_slab(p.c, ks);
     p.c.table = ctx->d_chktab[li];
     p.c.tab768 = ctx->d_tables;
     p.c.report = reinterpret_cast<uint64_t *>(d_report);

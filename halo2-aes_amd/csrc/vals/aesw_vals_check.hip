@@ -155,9 +155,7 @@ int aesw_vals_check_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_
     if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_vals_check_device");
     if (!ctx || !d_report || !aligned_to(d_report, 8)) return AESW_ERR_INVALID_ARG;
     const aesw_key_slab *ks = d_key_slab;
-    if (!ks || !ks->w || !ks->kx || !ks->ky || !ks->kz || !aligned_to(ks->w, 16) || !aligned_to(ks->kx, 16) || !aligned_to(ks->ky, 16) ||
-        !aligned_to(ks->kz, 16) || !aligned_to(d_keys, 4))
-        return AESW_ERR_INVALID_ARG;
+    if (!key_slab_ok(ks) || !aligned_to(d_keys, 4)) return AESW_ERR_INVALID_ARG;
     if (per_block_keys && n && !d_keys) return AESW_ERR_INVALID_ARG;
     if (n && (!d_pt || !d_y || !d_z || !aligned_to(d_pt, 16) || !aligned_to(d_ct, 16) || !aligned_to(d_y, 16) || !aligned_to(d_z, 16)))
         return AESW_ERR_INVALID_ARG;
@@ -167,7 +165,7 @@ int aesw_vals_check_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_
     const int rc = aesw_vals::ensure_table(ctx, &p.table);
     if (rc != AESW_OK) return rc;
     p.pt = d_pt; p.keys = d_keys; p.y = d_y; p.z = d_z; p.ct = d_ct;  // x: a values witness has none
-    p.kw = ks->w; p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz;
+    aesw::set_key_slab(p, ks);
     p.tab768 = ctx->d_tables;
     p.report = reinterpret_cast<uint64_t *>(d_report);
     p.n = n;

@@ -1,5 +1,6 @@
 """The gfx950 code object inside one of the built libraries, for the CPU tests that look at the compiled kernels
-(test_isa_lint.py: libaesw.so, test_circ_check_library.py: libaesw_circ.so, test_cols_check_library.py: libaesw_cols.so):
+(test_isa_lint.py: libaesw.so; through check_library.py test_circ_check_library.py: libaesw_circ.so,
+test_cols_check_library.py: libaesw_cols.so and test_vals_check_library.py: libaesw_vals.so):
 objcopy takes the fat binary out of the library, clang-offload-bundler the gfx950 object out of that, llvm-objdump and
 llvm-readelf give its disassembly and kernel metadata.  Each test compares what it finds with its own tracked table."""
 import re

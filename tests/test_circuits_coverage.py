@@ -2,22 +2,13 @@
 
 tests/test_instantiation_coverage.py covers the aesw:: kernels through tests/kernel_cases.py; the many-circuit kernels of
 namespace aesw_circ are launched by tests/test_gpu_circuits.py, whose case list is tests/circuit_cases.py."""
-import re
-import subprocess
-
 import circuit_cases as cc
 import kernel_cases as kc
-
-_ANY_STUB = re.compile(r"([\w:]*?)__device_stub__(\w+)(<[^()]*>)?\(")
-
-
-def all_kernels(nm_text):
-    """(namespace, kernel name with template arguments, spaces removed) of every __global__ instantiation's host stub."""
-    return {(m.group(1).rstrip(":"), m.group(2) + (m.group(3) or "").replace(" ", "")) for m in _ANY_STUB.finditer(nm_text)}
+from check_library import all_kernels, nm
 
 
 def _nm(pkg):
-    return subprocess.run(["nm", "-C", str(pkg.api.LIB_PATH)], stdout=subprocess.PIPE, text=True, check=True).stdout
+    return nm(pkg.api.LIB_PATH, "-C")
 
 
 def test_all_kernels_parse():

@@ -14,12 +14,12 @@ and it compares every kernel's register / LDS / spill / store-instruction counts
 diff a reviewer sees.  Regenerate the table on purpose with  AESW_UPDATE_ISA_JSON=1 python -m pytest tests/test_isa_lint.py
 """
 import json
-import os
 import re
 from pathlib import Path
 
 import pytest
 
+from check_library import assert_tracked, resource_table
 from isa_extract import extract, needs_llvm, short
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -63,46 +63,21 @@ def test_every_inline_asm_store_is_padded(code_object):
 
 @needs_llvm
 def test_no_scratch_no_vgpr_spills_and_the_tracked_resource_table(code_object):
-    table, over = {}, []
-    for name, k in code_object["meta"].items():
-        ins = code_object["funcs"].get(name, [])
-        short = _short(code_object["demangled"][name])
-        assert k[".private_segment_fixed_size"] == 0, "%s uses %d B of scratch" % (short, k[".private_segment_fixed_size"])
-        assert k.get(".vgpr_spill_count", 0) == 0, "%s spills VGPRs" % short
-        # 256 unified registers = two waves per SIMD, what the 7 one-wave groups (packed) / two 3-wave groups per CU need.
-        # The DENSE instantiations (a demoted option: 35 % of what they write are zeros) are allowed the whole file: they
-        # run one wave per SIMD (two 2-wave groups per CU) and are launch-bounded accordingly in the source.
-        limit = 512 if short.startswith(("encrypt_kernel<0,", "key_kernel<0,")) else 256
-        if k[".vgpr_count"] > limit:
-            over.append((short, k[".vgpr_count"]))
-        table[short] = {
-            "vgpr": k[".vgpr_count"], "agpr": k.get(".agpr_count", 0), "sgpr": k[".sgpr_count"],
-            "sgpr_spill": k.get(".sgpr_spill_count", 0), "static_lds": k[".group_segment_fixed_size"],
-            "instructions": len(ins),
-            "stores_x4_sc1": sum(1 for t in ins if re.match(r"^global_store_dwordx4\b.*\bsc1\b", t)),
-            "stores_x4_other": sum(1 for t in ins if re.match(r"^global_store_dwordx4\b", t) and " sc1" not in t),
-            "ds_read_b128": sum(1 for t in ins if t.startswith("ds_read_b128")),
-            "v_perm_b32": sum(1 for t in ins if t.startswith("v_perm_b32")),
-            "readlane_writelane": sum(1 for t in ins if t.startswith(("v_readlane_b32", "v_writelane_b32"))),
-        }
+    table = resource_table(code_object, {
+        "stores_x4_sc1": lambda t: bool(re.match(r"^global_store_dwordx4\b.*\bsc1\b", t)),
+        "stores_x4_other": lambda t: bool(re.match(r"^global_store_dwordx4\b", t)) and " sc1" not in t,
+        "ds_read_b128": "ds_read_b128",
+        "v_perm_b32": "v_perm_b32",
+        "readlane_writelane": ("v_readlane_b32", "v_writelane_b32"),
+    }, drop="aesw::", max_unified=None)
     assert any(k.startswith("encrypt_kernel<1,true,0,true,2>") for k in table), sorted(table)[:5]
+    # 256 unified registers = two waves per SIMD, what the 7 one-wave groups (packed) / two 3-wave groups per CU need.
+    # The DENSE instantiations (a demoted option: 35 % of what they write are zeros) are allowed the whole file: they
+    # run one wave per SIMD (two 2-wave groups per CU) and are launch-bounded accordingly in the source.
+    over = [(k, row["vgpr"]) for k, row in table.items()
+            if row["vgpr"] > (512 if k.startswith(("encrypt_kernel<0,", "key_kernel<0,")) else 256)]
     assert not over, "more unified registers than the launch geometry allows: %r" % over
-    table = dict(sorted(table.items()))
-    if os.environ.get("AESW_UPDATE_ISA_JSON"):
-        TABLE.write_text(json.dumps(table, indent=1) + "\n")
-    assert TABLE.exists(), "profiles/isa_resources.json is missing: run with AESW_UPDATE_ISA_JSON=1 and commit it"
-    tracked = json.loads(TABLE.read_text())
-    drift = []
-    for name in sorted(set(table) | set(tracked)):
-        a, b = tracked.get(name), table.get(name)
-        if a != b:
-            if a and b:
-                what = ", ".join("%s %s -> %s" % (f, a.get(f), b.get(f)) for f in b if a.get(f) != b.get(f))
-            else:
-                what = "only in the %s" % ("tracked table" if a else "built library")
-            drift.append("%s: %s" % (name, what))
-    assert not drift, ("the built kernels differ from profiles/isa_resources.json (regenerate it with AESW_UPDATE_ISA_JSON=1 "
-                       "and commit the diff if the change is intended):\n" + "\n".join(drift[:30]))
+    assert_tracked(table, TABLE)
 
 
 @needs_llvm

@@ -20,7 +20,7 @@ lib_path = b.build_product(extra_flags=["-DAESW_TRACE"], out=ROOT / "tools" / "l
                            extra_sources=[ROOT / "halo2-aes_amd" / "host" / "host_capi.cpp"])
 if len(sys.argv) > 1 and sys.argv[1] == "build":
     sys.exit(0)
-pkg.api._lib = pkg.api.load_library(lib_path)
+pkg.api._loaded["aesw"] = pkg.api.load_library(lib_path)
 
 log2n = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 n = 1 << log2n
