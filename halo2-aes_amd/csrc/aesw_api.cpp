@@ -92,8 +92,8 @@ static int auto_waves(const aesw_ctx *ctx, int layout, bool pbk) {
     int w;
     // per-block keys: one-wave groups (7 resident per CU instead of two 3-wave groups) measured +1.3 ... +2.4 % at 2^20
     // blocks on two boxes and -0.6 % on a third (tools/sweep.py 20 c2 packed waves); shared key: 3-wave groups
-    if (pbk) w = ctx->waves_pbk ? ctx->waves_pbk : 1;
-    else w = ctx->waves_shared ? ctx->waves_shared : (layout == AESW_LAYOUT_DENSE ? 2 : 3);
+    if (pbk) w = ctx->opt.waves_pbk ? ctx->opt.waves_pbk : 1;
+    else w = ctx->opt.waves_shared ? ctx->opt.waves_shared : (layout == AESW_LAYOUT_DENSE ? 2 : 3);
     return w > max_waves ? max_waves : w;
 }
 
@@ -102,7 +102,7 @@ static int auto_waves_key(const aesw_ctx *ctx, int layout, bool want_rk) {
     // packed, witness only (no round-key output: no 2.8 KB round-key staging per wave since round 4): three 3-wave groups fit a CU
     // (45.7 KB each) and run 143.7 us against 146.3 for 4-wave groups and 148.0 / 154.9 for 2 / 1 (tools/keyarena.py,
     // profiles/r04_study/key_kernel_kz.md); with round keys a 3-wave group is 54 KB (two per CU): 4-wave groups as before
-    if (ctx->waves_pbk) return ctx->waves_pbk;
+    if (ctx->opt.waves_pbk) return ctx->opt.waves_pbk;
     if (layout == AESW_LAYOUT_DENSE) return 2;
     return want_rk ? 4 : 3;
 }
@@ -127,7 +127,7 @@ int fill_assemble_params(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_
     p->sx = aesw_column_stride(layout, 0); p->sy = aesw_column_stride(layout, 1); p->sz = aesw_column_stride(layout, 2);
     p->kxs = aesw_key_column_stride(layout, 0); p->kys = aesw_key_column_stride(layout, 1); p->kzs = aesw_key_column_stride(layout, 2);
     p->packed = layout == AESW_LAYOUT_PACKED;
-    p->geometry = ctx->asm_geo;
+    p->geometry = ctx->opt.asm_geo;
     return AESW_OK;
 }
 
@@ -206,7 +206,7 @@ int enqueue_encrypt(aesw_ctx *ctx, const EncLaunch &L, hipStream_t s) {
     if (!L.per_block_keys && L.kemit) {
         // shared key: its schedule witness is one key slab
         KeyParams kp{L.d_keys, ctx->d_tables, L.ko, nullptr, 1, 0, 0};
-        HIP_TRY(ctx, launch_key(kp, L.layout, ctx->xt, 1, ctx->key_nt, 0u, s));
+        HIP_TRY(ctx, launch_key(kp, L.layout, ctx->xt, 1, ctx->opt.key_nt, 0u, s));
     }
     const int km = L.per_block_keys ? 0 : (L.d_keys ? 1 : 2);
     KeyRing::Access rd;
@@ -220,7 +220,7 @@ int enqueue_encrypt(aesw_ctx *ctx, const EncLaunch &L, hipStream_t s) {
     p.trace = ctx->trace;
 #endif
     HIP_TRY(ctx, launch_encrypt(p, L.layout, ctx->xt, km, L.per_block_keys && L.kemit, auto_waves(ctx, L.layout, L.per_block_keys != 0),
-                                ctx->nt, (uint32_t)ctx->grid_cap, ctx->xcd_remap, (uint32_t)ctx->lds_pad, s));
+                                ctx->opt.nt, (uint32_t)ctx->opt.grid_cap, ctx->opt.xcd_remap, (uint32_t)ctx->opt.lds_pad, s));
     return km == 2 ? ctx->keys.end_read(ctx, rd) : AESW_OK;  // this launch reads the current slot: nothing may overwrite the slot under it
 }
 
@@ -249,11 +249,11 @@ int fork_join(aesw_ctx *ctx, hipStream_t s, uint32_t ns, uint32_t count, Issue &
 // A LONE launch on the caller's stream: aesw_encrypt_witness_device (the chunks of the host-pointer paths come through it), and the
 // batches of the batch entry point when it has one stream or one batch.  Only here does "split_small" apply.
 int encrypt_lone(aesw_ctx *ctx, const EncLaunch &L, hipStream_t s) {
-    if (ctx->split_small <= 1 || L.per_block_keys || L.kemit || L.n < ((uint64_t)1 << 15) || L.n > ((uint64_t)1 << 17)) return enqueue_encrypt(ctx, L, s);
+    if (ctx->opt.split_small <= 1 || L.per_block_keys || L.kemit || L.n < ((uint64_t)1 << 15) || L.n > ((uint64_t)1 << 17)) return enqueue_encrypt(ctx, L, s);
     // "split_small": the lone small batch as 2-3 sub-launches on the internal streams.  Sub-ranges are multiples of 48 blocks -- whole
     // 3-wave groups, and 48 x 1360 / 1056 / 608 are multiples of the 128-byte line, so no two sub-launches share a line of any column.
     // A split uses as many internal streams as it has parts (at most 8, at least 2 for these n), whatever "batch_streams" says.
-    const uint32_t parts = (uint32_t)ctx->split_small;
+    const uint32_t parts = (uint32_t)ctx->opt.split_small;
     const uint64_t per = ((L.n + parts - 1) / parts + 47) / 48 * 48;
     const uint32_t cnt = (uint32_t)((L.n + per - 1) / per);
     const uint64_t sx = aesw_column_stride(L.layout, 0), sy = aesw_column_stride(L.layout, 1), sz = aesw_column_stride(L.layout, 2);
@@ -535,105 +535,48 @@ int aesw_assemble_selectors(uint32_t k, uint32_t n_sets, uint64_t n_blocks, uint
 
 // ---- options --------------------------------------------------------------------
 
+// One row of AESW_OPTIONS (aesw_options.h) per name checks the value and stores it in ctx->opt; here is what a row cannot say.
 int aesw_set_option(aesw_ctx *ctx, const char *name, int64_t value) {
     if (aesw_is_group(ctx)) return aesw_group_set_option(ctx, name, value);
     if (!ctx || !name) return AESW_ERR_INVALID_ARG;
-    if (!std::strcmp(name, "waves_shared")) { if (value < 0 || value > 4) return AESW_ERR_INVALID_ARG; ctx->waves_shared = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "waves_pbk")) { if (value < 0 || value > 4) return AESW_ERR_INVALID_ARG; ctx->waves_pbk = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "nt_stores")) { ctx->nt = value != 0 ? 1 : 0; return AESW_OK; }
-    if (!std::strcmp(name, "store_mode")) {
-        // 3 = "leave the flush out" (output is garbage): exists only in -DAESW_DIAGNOSTIC builds of the library (tools/)
-#ifdef AESW_DIAGNOSTIC
-        const int max_mode = 5;
-#else
-        const int max_mode = 2;
-#endif
-        if (value < 0 || value > max_mode) return AESW_ERR_INVALID_ARG;
-        ctx->nt = (int)value;
-        return AESW_OK;
-    }
-    if (!std::strcmp(name, "key_store_mode")) { if (value < 0 || value > 2) return AESW_ERR_INVALID_ARG; ctx->key_nt = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "fr_geometry")) { if (value < 0 || value > 2) return AESW_ERR_INVALID_ARG; ctx->fr_geo = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "fr_store_mode")) { if (value < 0 || value > 2) return AESW_ERR_INVALID_ARG; ctx->fr_nt = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "assemble_geometry")) { if (value < 0 || value > 4) return AESW_ERR_INVALID_ARG; ctx->asm_geo = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "grid_cap")) { if (value < 0 || value > 0x7fffffff) return AESW_ERR_INVALID_ARG; ctx->grid_cap = value; return AESW_OK; }
-    if (!std::strcmp(name, "xcd_remap")) { if (value < 0 || value > (1 << 24)) return AESW_ERR_INVALID_ARG; ctx->xcd_remap = (uint32_t)value; return AESW_OK; }
-    if (!std::strcmp(name, "lds_pad")) { if (value < 0 || value > 120 * 1024) return AESW_ERR_INVALID_ARG; ctx->lds_pad = value; return AESW_OK; }
-    if (!std::strcmp(name, "arena_align_log2")) { if (value != 0 && (value < 7 || value > 32)) return AESW_ERR_INVALID_ARG; ctx->arena_align_log2 = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "arena_probe")) { if (value < -1 || value > 64) return AESW_ERR_INVALID_ARG; ctx->arena_probe = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "arena_unit")) { if (value < 0 || value > 2) return AESW_ERR_INVALID_ARG; ctx->arena_unit = (int)value; return AESW_OK; }
+    const OptionRow *r = aesw_find_option(name);
+    if (!r || !aesw_option_set(ctx->opt, *r, value)) return AESW_ERR_INVALID_ARG;
+    switch (r->extra) {
+    case OptExtra::ARENA_CACHE: if (!value) aesw_arena_cache_trim(ctx, 0); break;
+    case OptExtra::ARENA_CACHE_MAX_MB: aesw_arena_cache_trim(ctx, ctx->opt.arena_cache_max_bytes()); break;
+    case OptExtra::KEY_SLOTS: ctx->keys.set_ring_size((int)value); break;
+    case OptExtra::FORCE_TABLE_PATH: if (value) ctx->xt = false; break;
 #ifdef AESW_TRACE
-    if (!std::strcmp(name, "trace_ptr")) { ctx->trace = reinterpret_cast<uint64_t *>(value); return AESW_OK; }
+    case OptExtra::TRACE_PTR: ctx->trace = reinterpret_cast<uint64_t *>(value); break;
 #endif
-    if (!std::strcmp(name, "force_table_path")) { if (value) ctx->xt = false; return AESW_OK; }
-    if (!std::strcmp(name, "chunk_blocks")) { if (value < 64) return AESW_ERR_INVALID_ARG; ctx->chunk_blocks = value; return AESW_OK; }
-    if (!std::strcmp(name, "batch_streams")) { if (value < 1 || value > 8) return AESW_ERR_INVALID_ARG; ctx->batch_streams = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "copy_threads")) { if (value < -1 || value > 64) return AESW_ERR_INVALID_ARG; ctx->copy_threads = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "key_slots")) { if (value < 1 || value > 64) return AESW_ERR_INVALID_ARG; ctx->keys.set_ring_size((int)value); return AESW_OK; }
-    if (!std::strcmp(name, "split_small")) { if (value < 0 || value > 8) return AESW_ERR_INVALID_ARG; ctx->split_small = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "stream_check")) { if (value != 0 && value != 1) return AESW_ERR_INVALID_ARG; ctx->stream_check = (int)value; return AESW_OK; }
-    if (!std::strcmp(name, "stream_poison")) { if (value < 0) return AESW_ERR_INVALID_ARG; ctx->stream_poison = value; return AESW_OK; }
-    if (!std::strcmp(name, "arena_cache")) {  // 0 also releases what is cached now
-        if (value != 0 && value != 1) return AESW_ERR_INVALID_ARG;
-        ctx->arena_cache_on = (int)value;
-        if (!value) aesw_arena_cache_trim(ctx, 0);
-        return AESW_OK;
+    default: break;
     }
-    if (!std::strcmp(name, "arena_cache_max_mb")) {
-        if (value < 0 || value > ((int64_t)1 << 30)) return AESW_ERR_INVALID_ARG;
-        ctx->arena_cache_max_bytes = (uint64_t)value << 20;
-        aesw_arena_cache_trim(ctx, ctx->arena_cache_max_bytes);
-        return AESW_OK;
-    }
-    if (!std::strcmp(name, "arena_probe_budget_ms")) { if (value < 0 || value > 600000) return AESW_ERR_INVALID_ARG; ctx->arena_probe_budget_ms = value; return AESW_OK; }
-    return AESW_ERR_INVALID_ARG;
+    return AESW_OK;
 }
 
 int aesw_get_option(const aesw_ctx *ctx, const char *name, int64_t *value) {
     if (aesw_is_group(ctx)) return aesw_get_option(ctx->members[0], name, value);  // a group: member 0
     if (!ctx || !name || !value) return AESW_ERR_INVALID_ARG;
-    if (!std::strcmp(name, "waves_shared")) { *value = ctx->waves_shared; return AESW_OK; }
-    if (!std::strcmp(name, "waves_pbk")) { *value = ctx->waves_pbk; return AESW_OK; }
-    // what a launch really uses (0 = auto resolved, values above the layout's maximum clamped): packed layout
-    if (!std::strcmp(name, "effective_waves_shared")) { *value = auto_waves(ctx, AESW_LAYOUT_PACKED, false); return AESW_OK; }
-    if (!std::strcmp(name, "effective_waves_pbk")) { *value = auto_waves(ctx, AESW_LAYOUT_PACKED, true); return AESW_OK; }
-    if (!std::strcmp(name, "effective_waves_key")) { *value = auto_waves_key(ctx, AESW_LAYOUT_PACKED, false); return AESW_OK; }
-    if (!std::strcmp(name, "nt_stores")) { *value = ctx->nt == 1; return AESW_OK; }
-    if (!std::strcmp(name, "store_mode")) { *value = ctx->nt; return AESW_OK; }
-    if (!std::strcmp(name, "key_store_mode")) { *value = ctx->key_nt; return AESW_OK; }
-    if (!std::strcmp(name, "fr_store_mode")) { *value = ctx->fr_nt; return AESW_OK; }
-    if (!std::strcmp(name, "fr_geometry")) { *value = ctx->fr_geo; return AESW_OK; }
-    if (!std::strcmp(name, "assemble_geometry")) { *value = ctx->asm_geo; return AESW_OK; }
-    if (!std::strcmp(name, "grid_cap")) { *value = ctx->grid_cap; return AESW_OK; }
-    if (!std::strcmp(name, "xcd_remap")) { *value = ctx->xcd_remap; return AESW_OK; }
-    if (!std::strcmp(name, "lds_pad")) { *value = ctx->lds_pad; return AESW_OK; }
-    if (!std::strcmp(name, "arena_align_log2")) { *value = ctx->arena_align_log2; return AESW_OK; }
-    if (!std::strcmp(name, "arena_probe")) { *value = ctx->arena_probe; return AESW_OK; }
-    if (!std::strcmp(name, "arena_unit")) { *value = ctx->arena_unit; return AESW_OK; }
-    if (!std::strcmp(name, "force_table_path")) { *value = ctx->xt ? 0 : 1; return AESW_OK; }
-    if (!std::strcmp(name, "chunk_blocks")) { *value = ctx->chunk_blocks; return AESW_OK; }
-    if (!std::strcmp(name, "batch_streams")) { *value = ctx->batch_streams; return AESW_OK; }
-    if (!std::strcmp(name, "copy_threads")) { *value = ctx->copy_threads; return AESW_OK; }
-    if (!std::strcmp(name, "effective_copy_threads")) { *value = auto_copy_threads(ctx); return AESW_OK; }
-    if (!std::strcmp(name, "key_slots")) { *value = ctx->keys.ring_size(); return AESW_OK; }
-    if (!std::strcmp(name, "split_small")) { *value = ctx->split_small; return AESW_OK; }
-    if (!std::strcmp(name, "stream_check")) { *value = ctx->stream_check; return AESW_OK; }
-    if (!std::strcmp(name, "stream_poison")) { *value = ctx->stream_poison; return AESW_OK; }
-    if (!std::strcmp(name, "arena_cache")) { *value = ctx->arena_cache_on; return AESW_OK; }
-    if (!std::strcmp(name, "arena_cache_max_mb")) { *value = (int64_t)(ctx->arena_cache_max_bytes >> 20); return AESW_OK; }
-    if (!std::strcmp(name, "arena_probe_budget_ms")) { *value = ctx->arena_probe_budget_ms; return AESW_OK; }
-    if (!std::strcmp(name, "arena_cache_hits")) { *value = (int64_t)ctx->arena_cache_hits; return AESW_OK; }  // read-only statistics
-    if (!std::strcmp(name, "arena_cached_bytes")) {
-        uint64_t b = 0;
-        for (const auto &c : ctx->arena_cache) b += c.cols.bytes;
-        *value = (int64_t)b;
-        return AESW_OK;
+    const OptionRow *r = aesw_find_option(name);
+    if (!r || !(r->access & OPT_GET)) return AESW_ERR_INVALID_ARG;
+    if (aesw_option_get(ctx->opt, *r, value)) return AESW_OK;
+    switch (r->extra) {
+    case OptExtra::KEY_SLOTS: *value = ctx->keys.ring_size(); break;
+    case OptExtra::FORCE_TABLE_PATH: *value = ctx->xt ? 0 : 1; break;
+    case OptExtra::EFFECTIVE_WAVES_SHARED: *value = auto_waves(ctx, AESW_LAYOUT_PACKED, false); break;
+    case OptExtra::EFFECTIVE_WAVES_PBK: *value = auto_waves(ctx, AESW_LAYOUT_PACKED, true); break;
+    case OptExtra::EFFECTIVE_WAVES_KEY: *value = auto_waves_key(ctx, AESW_LAYOUT_PACKED, false); break;
+    case OptExtra::EFFECTIVE_COPY_THREADS: *value = auto_copy_threads(ctx); break;
+    case OptExtra::ARENA_CACHE_HITS: *value = (int64_t)ctx->arena_cache_hits; break;
+    case OptExtra::ARENA_CACHED_BYTES: *value = 0; for (const auto &c : ctx->arena_cache) *value += (int64_t)c.cols.bytes; break;
+    case OptExtra::KEY_READER_WAITS: *value = (int64_t)ctx->keys.key_reader_waits(); break;
+    case OptExtra::KEY_WRITER_WAITS: *value = (int64_t)ctx->keys.key_writer_waits(); break;
+    case OptExtra::KEY_SLOTS_ALLOCATED: *value = ctx->keys.key_slots_allocated(); break;
+    case OptExtra::KEY_SLOTS_PINNED: *value = ctx->keys.key_slots_pinned(); break;
+    // no default: -Wswitch names an OptExtra that has no case here (a readable row has a field or a case above)
+    case OptExtra::NONE: case OptExtra::ARENA_CACHE: case OptExtra::ARENA_CACHE_MAX_MB: case OptExtra::TRACE_PTR: return AESW_ERR_INVALID_ARG;
     }
-    if (!std::strcmp(name, "key_reader_waits")) { *value = (int64_t)ctx->keys.key_reader_waits(); return AESW_OK; }  // read-only statistics
-    if (!std::strcmp(name, "key_writer_waits")) { *value = (int64_t)ctx->keys.key_writer_waits(); return AESW_OK; }
-    if (!std::strcmp(name, "key_slots_allocated")) { *value = ctx->keys.key_slots_allocated(); return AESW_OK; }
-    if (!std::strcmp(name, "key_slots_pinned")) { *value = ctx->keys.key_slots_pinned(); return AESW_OK; }
-    return AESW_ERR_INVALID_ARG;
+    return AESW_OK;
 }
 
 // ---- device-pointer entry points ------------------------------------------------
@@ -650,7 +593,7 @@ int aesw_schedule_key_device(aesw_ctx *ctx, const uint8_t *d_key, int layout, co
     const int rc = ctx->keys.begin_write(ctx, s, &w);
     if (rc != AESW_OK) return rc;
     KeyParams kp{d_key, ctx->d_tables, ko, w.d, 1, 0, 0};
-    return ctx->keys.end_write(ctx, w, launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, s));
+    return ctx->keys.end_write(ctx, w, launch_key(kp, layout, ctx->xt, 1, ctx->opt.key_nt, 0u, s));
 }
 
 int aesw_encrypt_witness_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys, int per_block_keys,
@@ -681,7 +624,7 @@ int aesw_encrypt_witness_batches_device(aesw_ctx *ctx, const aesw_batch *batches
         if (!validate_encrypt(ctx, b.d_pt, b.d_keys, per_block_keys, b.n, layout, b.d_x, b.d_y, b.d_z, b.d_ct, b.d_key_slab, &L, &rc)) return rc;
         return lone ? encrypt_lone(ctx, L, si) : enqueue_encrypt(ctx, L, si);
     };
-    const uint32_t ns = (uint32_t)ctx->batch_streams < count ? (uint32_t)ctx->batch_streams : count;
+    const uint32_t ns = (uint32_t)ctx->opt.batch_streams < count ? (uint32_t)ctx->opt.batch_streams : count;
     if (ns <= 1) {  // nothing to overlap: plain launches on the caller's stream, each of them a lone launch ("split_small" applies)
         for (uint32_t i = 0; i < count; ++i) {
             const int rc = issue(i, s, true);
@@ -705,7 +648,7 @@ int aesw_key_schedule_witness_device(aesw_ctx *ctx, const uint8_t *d_keys, uint6
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     KeyParams kp{d_keys, ctx->d_tables, ko, d_rk, n, 0, 0};
-    HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, auto_waves_key(ctx, layout, d_rk != nullptr), ctx->key_nt, ctx->xcd_remap, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, auto_waves_key(ctx, layout, d_rk != nullptr), ctx->opt.key_nt, ctx->opt.xcd_remap, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;
 }
 
@@ -729,7 +672,7 @@ int aesw_assemble_advice_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     p.out = d_out;
-    HIP_TRY(ctx, launch_assemble(p, as_fr != 0, ctx->fr_nt, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(ctx, launch_assemble(p, as_fr != 0, ctx->opt.fr_nt, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;
 }
 
@@ -747,7 +690,7 @@ int aesw_expand_fr_device(aesw_ctx *ctx, const uint8_t *d_cells, uint64_t n_cell
     if (!d_cells || !d_fr || !aligned16(d_fr)) return AESW_ERR_INVALID_ARG;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
-    HIP_TRY(ctx, launch_expand_fr(d_cells, n_cells, ctx->d_fr_lut, d_fr, ctx->fr_nt, ctx->fr_geo, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(ctx, launch_expand_fr(d_cells, n_cells, ctx->d_fr_lut, d_fr, ctx->opt.fr_nt, ctx->opt.fr_geo, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;
 }
 

@@ -91,7 +91,7 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     const bool key_only = with_key_slab == 2;
     const uint64_t sx = key_only ? 0 : aesw_column_stride(layout, 0), sy = key_only ? 0 : aesw_column_stride(layout, 1),
                    sz = key_only ? 0 : aesw_column_stride(layout, 2);
-    const uint64_t align = ctx->arena_align_log2 ? (uint64_t)1 << ctx->arena_align_log2 : (uint64_t)2 << 20;
+    const uint64_t align = ctx->opt.arena_align_log2 ? (uint64_t)1 << ctx->opt.arena_align_log2 : (uint64_t)2 << 20;
     // sizes in the order the columns are laid out; a column of size 0 takes no room
     const uint64_t size[8] = {n * sx, n * sy, n * sz, with_ct ? n * 16 : 0,
                               with_key_slab ? n * WORDS_ROWS : 0, with_key_slab ? n * aesw_key_column_stride(layout, 0) : 0,
@@ -109,7 +109,7 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
         out->x = at(0); out->y = at(1); out->z = at(2); out->ct = at(3);
         out->key.w = at(4); out->key.kx = at(5); out->key.ky = at(6); out->key.kz = at(7);
     };
-    int probe = ctx->arena_probe < 0 ? (n >= ((uint64_t)1 << 16) ? 8 : 0) : ctx->arena_probe;
+    int probe = ctx->opt.arena_probe < 0 ? (n >= ((uint64_t)1 << 16) ? 8 : 0) : ctx->opt.arena_probe;
     if (probe == 0) {
         // hipMalloc returns memory aligned to the allocation granule only: over-allocate by one alignment unit
         uint8_t *raw = nullptr;
@@ -121,10 +121,10 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     }
     // Placement cache: this context has placed (and the caller has freed) an arena of exactly this shape: take it over.  The
     // backing is the one the earlier search chose, still mapped, so the pattern runs at the rate measured then.
-    if (ctx->arena_cache_on) {
+    if (ctx->opt.arena_cache_on) {
         for (size_t i = ctx->arena_cache.size(); i-- > 0;) {
             aesw_ctx::ArenaRec &c = ctx->arena_cache[i];
-            if (c.n == n && c.layout == layout && c.with_key_slab == with_key_slab && c.with_ct == (with_ct ? 1 : 0) && c.xcd == ctx->xcd_remap) {
+            if (c.n == n && c.layout == layout && c.with_key_slab == with_key_slab && c.with_ct == (with_ct ? 1 : 0) && c.xcd == ctx->opt.xcd_remap) {
                 *out = c.cols;
                 out->candidates = 0;  // nothing was built or timed for this call; probe_us / fill_us are the earlier search's
                 ctx->vmm_arenas.push_back(std::move(c));
@@ -140,8 +140,8 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     }
     const auto t_search = std::chrono::steady_clock::now();
     auto over_budget = [&]() {
-        if (ctx->arena_probe_budget_ms <= 0) return false;
-        return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_search).count() > ctx->arena_probe_budget_ms;
+        if (ctx->opt.arena_probe_budget_ms <= 0) return false;
+        return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_search).count() > ctx->opt.arena_probe_budget_ms;
     };
     // Search by measurement.  A UNIT is what one candidate backs: the whole set of columns in one range ("arena_unit" 0), or
     // one column ("arena_unit" 1: greedy, largest column first).  For every unit up to `probe` candidates are built -- a plain
@@ -191,7 +191,7 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     ProbeParams pp = {};
     for (int c = 0; c < 7; ++c) pp.stride[c] = strides7[c];
     pp.n = n;
-    pp.xcd_mode = ctx->xcd_remap;
+    pp.xcd_mode = ctx->opt.xcd_remap;
     // two timed passes of a 2^20-block set; proportionally more for smaller batches (short launches time noisily)
     const int passes = n >= ((uint64_t)1 << 20) ? 2 : (int)std::min<uint64_t>(32, (((uint64_t)1 << 21) + n - 1) / n);
     // "as fast as a linear fill": the two levels are 0.98 - 1.02 and >= 1.05 of the fill at 2^18 blocks and more; a shorter launch
@@ -298,9 +298,9 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     };
     // "arena_unit" 2 (default): whole-set candidates first; when none of them runs the pattern as fast as its fill, a second
     // search places the columns one at a time (the whole-set losers stay held meanwhile) and the better of the two is kept
-    Placement pl = search(ctx->arena_unit == 1 ? 1 : 0);
+    Placement pl = search(ctx->opt.arena_unit == 1 ? 1 : 0);
     if (pl.rc != AESW_OK) return pl.rc;
-    if (ctx->arena_unit == 2 && n >= ((uint64_t)1 << 18) && pl.probe_us > accept * pl.fill_us && !over_budget()) {
+    if (ctx->opt.arena_unit == 2 && n >= ((uint64_t)1 << 18) && pl.probe_us > accept * pl.fill_us && !over_budget()) {
         Placement alt = search(1);
         if (alt.rc == AESW_OK && alt.probe_us / alt.fill_us < pl.probe_us / pl.fill_us) std::swap(pl, alt);
         for (auto &r : alt.ranges) losers.push_back(r);  // the search that lost (or failed half-way: already handed over)
@@ -315,7 +315,7 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     out->probe_us = pl.probe_us;
     out->fill_us = pl.fill_us;
     rec.key = out->base;
-    rec.n = n; rec.layout = layout; rec.with_key_slab = with_key_slab; rec.with_ct = with_ct ? 1 : 0; rec.xcd = ctx->xcd_remap;
+    rec.n = n; rec.layout = layout; rec.with_key_slab = with_key_slab; rec.with_ct = with_ct ? 1 : 0; rec.xcd = ctx->opt.xcd_remap;
     rec.cols = *out;
     ctx->vmm_arenas.push_back(rec);
     done = true;
@@ -344,13 +344,13 @@ int aesw_columns_free(aesw_ctx *ctx, aesw_columns *cols) {
                 // what hipFree guarantees on the unprobed path: launches still queued into the arena finish first (a cached
                 // arena goes to the next caller of this shape at once, an uncached one is unmapped)
                 HIP_TRY(ctx, hipDeviceSynchronize());
-                if (ctx->arena_cache_on && ctx->vmm_arenas[i].cols.bytes <= ctx->arena_cache_max_bytes) {
+                if (ctx->opt.arena_cache_on && ctx->vmm_arenas[i].cols.bytes <= ctx->opt.arena_cache_max_bytes()) {
                     // keep the placement: the next arena of this shape takes it over (freed memory would be handed out again
                     // in some other combination, and the search would start over)
                     ctx->vmm_arenas[i].stamp = ++ctx->arena_stamp;
                     ctx->arena_cache.push_back(std::move(ctx->vmm_arenas[i]));
                     ctx->vmm_arenas.erase(ctx->vmm_arenas.begin() + (long)i);
-                    cache_trim(ctx, ctx->arena_cache_max_bytes);
+                    cache_trim(ctx, ctx->opt.arena_cache_max_bytes());
                 } else {
                     release_ranges(ctx->vmm_arenas[i].ranges);
                     ctx->vmm_arenas.erase(ctx->vmm_arenas.begin() + (long)i);

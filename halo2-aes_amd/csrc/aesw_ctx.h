@@ -7,11 +7,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <ctime>
 #include <string>
 #include <vector>
 
 #include "../../include/aesw.h"
 #include "aesw_keyring.h"
+#include "aesw_options.h"
 
 struct aesw_ctx {
     int device = -1;
@@ -21,27 +23,8 @@ struct aesw_ctx {
     uint32_t *d_chktab[2] = {nullptr, nullptr};         // check tables of the DENSE / PACKED layout (aesw_check.h), uploaded by aesw_create
     KeyRing keys;  // the scheduled key: its round-key slots and their ordering (aesw_keyring.h)
     bool xt = false;
-    int waves_shared = 0;  // waves per group, shared-key kernels (0 = auto)
-    int waves_pbk = 0;     // per-block-key and key kernels (0 = auto)
-    int nt = 1;  // store flavour: 0 plain, 1 nontemporal (default since round 3), 2 write-through (sc1).  With all three flavours compiled to the
-                 // same code (round 3: they used to differ by 60 VGPRs, i.e. in residency) nontemporal stores are 1-3 % ahead at 2^20 blocks on
-                 // well-placed columns and within +-2 % of sc1 elsewhere (profiles/r03_study/README.md)
-    int key_nt = 1;  // store flavour of key_kernel (one contiguous flush per column at the end): nontemporal 4-9 % ahead of sc1 (tools/keysweep.py)
-    int fr_geo = 1;  // geometry of expand_fr: 1 = one-shot 4 KiB workgroups, LUT gathered from global memory: 7.3 TB/s with nontemporal stores
-                     // against 5.2 for 0 = striding workgroups + LDS LUT and 5.9 for 2 = one-shot 16 KiB + LDS LUT (tools/frsweep.py)
-    int asm_geo = 4;  // geometry of the Fr form of assemble: 0 striding workgroups, 1 one-shot (chunk, segment, column) grid, 2 / 3 / 4 one-shot workgroups
-                      // on aligned output chunks: 256 threads x 1 piece, 256 x 2, 128 x 2 (4 = default: 6.9 TB/s for K = 20, N = 5 against 5.3 striding)
-                      // workgroups on a (chunk, segment, column) grid (round 3: byte-exact, 5.2 TB/s -- a piece is a chain of three dependent loads
-                      // (index table, slab byte, LUT) and a one-shot workgroup has nothing else in flight: latency x residency bounds it, not divisions)
-    int fr_nt = 1;  // store flavour of the Fr-expanding kernels: nontemporal measured 19 % ahead of plain and sc1 there (tools/frsweep.py)
-    int64_t grid_cap = 0;  // max workgroups per launch (0 = one per block group)
-    uint32_t xcd_remap = 1;  // xcd_group() mode: 0 dispatch order, 1 one contiguous eighth of the groups per XCD (+3-4 % at 2^20 blocks over 0, tools/sweep.py xcd), C >= 2 turns of C groups
-    int64_t lds_pad = 0;  // diagnostic (tools/occ.py): extra dynamic LDS per workgroup, lowers residency
-    int arena_align_log2 = 0;  // aesw_columns_alloc: column alignment (0 = auto: 2 MiB)
-    int arena_probe = -1;      // candidate backings aesw_columns_alloc measures per unit (-1 = auto, 0 = none: one hipMalloc)
+    AeswOptions opt;  // every knob aesw_set_option stores (aesw_options.h)
     double best_fill_us_per_gb = 0;  // fastest linear fill any arena search of this context has seen (us per 10^9 bytes): the probe's yardstick
-    int arena_unit = 2;        // what a candidate is: 0 = the whole set of columns in one range, 1 = one column (greedy, largest first),
-                               // 2 = whole sets first, columns if no set candidate runs the pattern as fast as its fill (default)
     struct ArenaRange { void *p; size_t bytes; bool vmm; };  // vmm: built with the virtual-memory API (freed by unmap), else hipMalloc
     // A probed arena: its ranges, and what it was placed for (the shape decides whether a later request may take it over)
     struct ArenaRec {
@@ -55,24 +38,16 @@ struct aesw_ctx {
     };
     std::vector<ArenaRec> vmm_arenas;  // arenas built with the virtual-memory API (one range per column; freed by unmap, not hipFree)
     // Placement cache: a probed arena that is freed keeps its backing (physical placement is what the search paid for); the next
-    // aesw_columns_alloc of the same shape takes it over without a search.  Bounded by arena_cache_max_bytes, oldest out first;
+    // aesw_columns_alloc of the same shape takes it over without a search.  Bounded by option "arena_cache_max_mb", oldest out first;
     // flushed when a search runs short of memory, by option "arena_cache" = 0 and by aesw_destroy.
     std::vector<ArenaRec> arena_cache;
-    int arena_cache_on = 1;
-    uint64_t arena_cache_max_bytes = (uint64_t)64 << 30;
     uint64_t arena_stamp = 0;
     uint64_t arena_cache_hits = 0;
-    int64_t arena_probe_budget_ms = 3000;  // a search stops building candidates once it has run this long (0 = no limit); it always keeps the best so far
 #ifdef AESW_TRACE
     uint64_t *trace = nullptr;
 #endif
-    int64_t chunk_blocks = 1 << 15;  // host-pointer path: blocks per pipeline stage
-    int copy_threads = -1;           // host threads that move a stage from the page-locked bounce buffer into a pageable destination (-1 = auto)
     std::string last_error;
     hipStream_t s_compute = nullptr, s_copy = nullptr;
-    int split_small = 0;    // experiment of round 4 (profiles/r04_study/split_small.md): a LONE shared / scheduled-key launch of 2^15 .. 2^17 blocks
-                            // dealt as this many line-aligned sub-ranges onto the internal streams (0 / 1 = off)
-    int batch_streams = 3;  // aesw_encrypt_witness_batches_device: internal streams the batches are dealt onto
     hipStream_t s_batch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint8_t *bounce[2] = {nullptr, nullptr};  // page-locked staging for pageable destinations
@@ -80,8 +55,6 @@ struct aesw_ctx {
     uint8_t *scratch = nullptr;  // device buffers of the host-pointer path (grow-only)
     size_t scratch_bytes = 0;
     aesw_stream_stats stats = {};  // of the last streaming call
-    int stream_check = 0;          // option: aesw_encrypt_witness_stream checks every chunk on the device before it travels (aesw_check.h)
-    int64_t stream_poison = 0;     // diagnostic (tests): block index + 1 whose y / z cells the stream overwrites before its chunk is checked and shipped
     aesw_check_report stream_report = {0, 0, 0, 0, 0, 0, ~0ull};  // of the last streaming call with "stream_check" on
     // Group context (aesw_create_group, aesw_group.cpp): one member context per listed device, nothing on a device of its own; the
     // host-pointer entry points split a batch into block shards over the members.  Empty for a plain context.
@@ -140,6 +113,24 @@ inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<ui
 inline bool key_slab_ok(const aesw_key_slab *ks) {
     return ks && ks->w && ks->kx && ks->ky && ks->kz && aligned_to(ks->w, 16) && aligned_to(ks->kx, 16) && aligned_to(ks->ky, 16) && aligned_to(ks->kz, 16);
 }
+inline uint64_t now_ns() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+}
+
+// Fold the report of one part of a batch (a pipeline stage, a group member's shard) into the batch-wide one.  Units of a part count
+// from its first block -- a block, or a per-block key slab; the one slab of a shared key is unit 0 of the batch as well.
+inline void merge_check_report(aesw_check_report &t, const aesw_check_report &r, uint64_t first_block, bool per_block_keys) {
+    t.blocks += r.blocks; t.keys += r.keys;
+    t.lookup_failures += r.lookup_failures; t.copy_failures += r.copy_failures;
+    t.gate_failures += r.gate_failures; t.input_failures += r.input_failures;
+    if (r.first == AESW_CHECK_NONE) return;
+    const uint64_t unit = AESW_CHECK_UNIT(r.first) + ((!per_block_keys && AESW_CHECK_IS_KEY_SLAB(r.first)) ? 0 : first_block);
+    const uint64_t f = unit << 20 | (r.first & 0xfffffu);
+    if (f < t.first) t.first = f;
+}
+
 inline bool aesw_valid_layout(int l) { return l == AESW_LAYOUT_DENSE || l == AESW_LAYOUT_PACKED || l == AESW_LAYOUT_VALUES; }
 
 // What aesw_hostpath.cpp takes from aesw_api.cpp, and the one thing aesw_get_option takes back (AESW_INTERNAL: aesw_keyring.h).

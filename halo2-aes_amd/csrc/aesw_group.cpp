@@ -7,7 +7,6 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
-#include <ctime>
 #include <deque>
 #include <functional>
 #include <mutex>
@@ -32,12 +31,6 @@ void shard_of(uint32_t members, uint64_t n, uint32_t i, uint64_t *first, uint64_
 
 template <class T>
 T *at(T *p, uint64_t off) { return p ? p + off : nullptr; }
-
-uint64_t now_ns() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
 
 uint32_t size_of(const aesw_ctx *g) { return (uint32_t)g->members.size(); }
 
@@ -76,18 +69,6 @@ int run_members(aesw_ctx *g, const std::function<int(uint32_t)> &fn) {
         if (inline_run[i]) status[i] = fn(i);
     for (std::thread &t : pool) t.join();
     return first_failure(g, status);
-}
-
-void add_report(aesw_check_report &t, const aesw_check_report &r, uint64_t offset, bool pbk) {
-    t.blocks += r.blocks; t.keys += r.keys;
-    t.lookup_failures += r.lookup_failures; t.copy_failures += r.copy_failures;
-    t.gate_failures += r.gate_failures; t.input_failures += r.input_failures;
-    if (r.first != AESW_CHECK_NONE) {
-        // batch-wide units: a block (or a per-block key slab) counts from the member's first block; a shared key slab is unit 0
-        const uint64_t unit = AESW_CHECK_UNIT(r.first) + ((!pbk && AESW_CHECK_IS_KEY_SLAB(r.first)) ? 0 : offset);
-        const uint64_t f = unit << 20 | (r.first & 0xfffffu);
-        if (f < t.first) t.first = f;
-    }
 }
 
 // aesw_encrypt_witness_stream: members hand their chunks to the calling thread, which runs `consume` one chunk at a time
@@ -249,7 +230,7 @@ int aesw_group_encrypt_witness_stream(aesw_ctx *g, const uint8_t *pt, const uint
         st.chunks += m->stats.chunks; st.bytes_to_host += m->stats.bytes_to_host;
         st.kernel_ns += m->stats.kernel_ns; st.d2h_ns += m->stats.d2h_ns;
         st.consumer_ns += m->stats.consumer_ns; st.wait_ns += m->stats.wait_ns;
-        add_report(rep, m->stream_report, first[i], pbk);
+        merge_check_report(rep, m->stream_report, first[i], pbk);
     }
     st.wall_ns = now_ns() - t_begin;
     g->stats = st;
@@ -300,7 +281,7 @@ int aesw_group_check_witness(aesw_ctx *g, const uint8_t *pt, const uint8_t *keys
     });
     if (rc != AESW_OK) return rc;
     for (uint32_t i = 0; i < G; ++i)
-        if (count[i]) add_report(*report, reps[i], first[i], pbk);
+        if (count[i]) merge_check_report(*report, reps[i], first[i], pbk);
     return AESW_OK;
 }
 

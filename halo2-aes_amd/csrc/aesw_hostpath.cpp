@@ -7,7 +7,6 @@
 
 #include <atomic>
 #include <cstring>
-#include <ctime>
 #include <thread>
 #include <vector>
 
@@ -24,7 +23,7 @@ using namespace aesw;
 // thread moves ~20 GB/s (less into memory it touches for the first time), the link delivers 55: the move is cut into 4 MiB
 // slices handed out to "copy_threads" threads (the caller is one of them).
 int auto_copy_threads(const aesw_ctx *ctx) {
-    if (ctx->copy_threads >= 0) return ctx->copy_threads < 1 ? 1 : ctx->copy_threads;
+    if (ctx->opt.copy_threads >= 0) return ctx->opt.copy_threads < 1 ? 1 : ctx->opt.copy_threads;
     cpu_set_t set;
     int usable = 1;
     if (sched_getaffinity(0, sizeof set, &set) == 0) usable = CPU_COUNT(&set);
@@ -59,12 +58,6 @@ void parallel_copy(const std::vector<CopyJob> &jobs, int threads) noexcept {
     }
     work();
     for (std::thread &t : pool) t.join();
-}
-
-uint64_t now_ns() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
 }
 
 struct DevBuf {
@@ -124,7 +117,7 @@ int ensure_carved(aesw_ctx *ctx, const Carve &dev, const Carve &host) {
 
 // Blocks per pipeline stage of a batch of n: "chunk_blocks", at most the batch, in whole 64-block units.
 uint64_t stage_blocks(const aesw_ctx *ctx, uint64_t n) {
-    const uint64_t chunk = (uint64_t)ctx->chunk_blocks < n ? (uint64_t)ctx->chunk_blocks : n;
+    const uint64_t chunk = (uint64_t)ctx->opt.chunk_blocks < n ? (uint64_t)ctx->opt.chunk_blocks : n;
     return (chunk + 63) / 64 * 64;
 }
 
@@ -279,18 +272,6 @@ int key_slab_to_device(aesw_ctx *ctx, const aesw_key_slab &dev, const aesw_key_s
     return copy_key_slab(ctx, host, first, dev, nk, layout, hipMemcpyHostToDevice, nullptr);
 }
 
-// Fold the report of one stage into the batch-wide one.  Units of a stage count from its first block; the shared key slab is
-// unit 0 of the batch as well.
-void merge_check_report(aesw_check_report &t, const aesw_check_report &r, uint64_t first_block, bool per_block_keys) {
-    t.blocks += r.blocks; t.keys += r.keys;
-    t.lookup_failures += r.lookup_failures; t.copy_failures += r.copy_failures;
-    t.gate_failures += r.gate_failures; t.input_failures += r.input_failures;
-    if (r.first == AESW_CHECK_NONE) return;
-    const uint64_t unit = (r.first >> 20) + ((!per_block_keys && ((r.first >> 19) & 1)) ? 0 : first_block);
-    const uint64_t f = unit << 20 | (r.first & 0xfffffu);
-    if (f < t.first) t.first = f;
-}
-
 }  // namespace
 
 extern "C" {
@@ -399,7 +380,7 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
     // "stream_check": every chunk is checked on the device behind its kernel (aesw_check.h).  Needs the key slab(s) the blocks' AddRoundKey
     // rows copy from -- one for a shared / scheduled key (made once, below), one per block with per-block keys (emitted by the chunk's
     // own launch into two more scratch sets) -- and one report per chunk, summed after the last one.
-    const bool checking = ctx->stream_check && layout != AESW_LAYOUT_VALUES;
+    const bool checking = ctx->opt.stream_check && layout != AESW_LAYOUT_VALUES;
     const uint64_t n_chunks = (n + chunk - 1) / chunk;
     size_t ks_off[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, o_rep = 0;
     if (checking) {
@@ -428,7 +409,7 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
         d_key16 = keys ? d + o_keys : key_read.d;
         const aesw_key_slab one = slab_of(0);
         KeyParams kp{d_key16, ctx->d_tables, KeyOut{one.w, one.kx, one.ky, one.kz}, nullptr, 1, 0, 0};
-        HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, 1, ctx->key_nt, 0u, ctx->s_compute));
+        HIP_TRY(ctx, launch_key(kp, layout, ctx->xt, 1, ctx->opt.key_nt, 0u, ctx->s_compute));
         if (!keys && (rc = ctx->keys.end_read(ctx, key_read)) != AESW_OK) return rc;
     }
     rc = pl.create_events(true);  // timed: aesw_last_stream_stats reports where the time went
@@ -439,10 +420,10 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
                                             layout, d + col_off[s][0], d + col_off[s][1], d + col_off[s][2], nullptr,
                                             checking && pbk ? &stage_slab : nullptr, ctx->s_compute);
         if (r != AESW_OK) return r;
-        if (ctx->stream_poison > 0 && (uint64_t)ctx->stream_poison - 1 >= b0 && (uint64_t)ctx->stream_poison - 1 < b0 + m) {
+        if (ctx->opt.stream_poison > 0 && (uint64_t)ctx->opt.stream_poison - 1 >= b0 && (uint64_t)ctx->opt.stream_poison - 1 < b0 + m) {
             // diagnostic: two cells of one block are overwritten between the kernel and the check (tests/test_gpu_round4.py shows the
             // stream check names that block, by its batch-wide index, in whatever chunk it lies)
-            const uint64_t pb = (uint64_t)ctx->stream_poison - 1 - b0;
+            const uint64_t pb = (uint64_t)ctx->opt.stream_poison - 1 - b0;
             HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][1] + pb * strides[1] + 5, 0x5A, 1, ctx->s_compute));
             HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][2] + pb * strides[2] + 7, 0xA5, 1, ctx->s_compute));
         }
@@ -517,7 +498,7 @@ static int assemble_columns(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t
         q.col_first = (uint32_t)col;
         q.col_count = 1;
         q.out = ctx->scratch + slot[s];
-        HIP_TRY(ctx, launch_assemble(q, as_fr != 0, ctx->fr_nt, ctx->s_compute));
+        HIP_TRY(ctx, launch_assemble(q, as_fr != 0, ctx->opt.fr_nt, ctx->s_compute));
         return AESW_OK;
     };
     auto copies = [&](int s, uint64_t col, uint64_t, std::vector<CopyJob> &d2h, std::vector<CopyJob> &move) {
@@ -599,7 +580,7 @@ int aesw_check_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, in
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     const CheckGeo cg = check_geo(layout);
-    const uint64_t chunk = (uint64_t)ctx->chunk_blocks < n ? (uint64_t)ctx->chunk_blocks : n;
+    const uint64_t chunk = (uint64_t)ctx->opt.chunk_blocks < n ? (uint64_t)ctx->opt.chunk_blocks : n;
     const uint64_t nk = per_block_keys ? chunk : 1;
     DevBuf dpt, dkeys, dx, dy, dz, dct, dw, dkx, dky, dkz, drep;
     HIP_TRY(ctx, dpt.alloc(chunk * 16));

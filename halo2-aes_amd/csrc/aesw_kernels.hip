@@ -1025,132 +1025,113 @@ static hipError_t allow_large_lds(const void *fn, size_t lds) {
     return e;
 }
 
-template <int L, bool XT, int KM, bool KEMIT, int NT>
-static hipError_t launch_enc(const EncParams &p0, int waves, uint32_t cap, uint32_t xr, uint32_t lds_pad, hipStream_t stream) {
+// ---- dispatch: runtime arguments -> one template instantiation ------------------------------------------------------
+// Which encrypt_kernel / key_kernel instantiations exist is said once, by the two visitors below: a handful of branches turn the
+// runtime tuple into a tag type for a functor.  Launching and warming are two functors over one visitor, so neither can name an
+// instantiation the other lacks (tests/kernel_cases.py restates the set for the sweep).
+template <int N> using Int = std::integral_constant<int, N>;
+#define AESW_V(c) decltype(c)::value  // the value of an Int<N> argument, as a constant expression
+// f(Int<v>{}) for v among the listed values; the last one also takes every other v
+template <int A, int... Rest, class F>
+static auto with_value(int v, F &&f) {
+    if constexpr (sizeof...(Rest) == 0) return f(Int<A>{});
+    else return v == A ? f(Int<A>{}) : with_value<Rest...>(v, f);
+}
+// the store flavour: 0 plain, 1 nontemporal, 2 write-through ("store_mode" / "key_store_mode" / "fr_store_mode")
+template <class F> static auto with_nt(int nt, F &&f) { return with_value<2, 1, 0>(nt, f); }
+#ifdef AESW_DIAGNOSTIC  // 3 ... 5: "leave the flush out" and its kin (tools/parts.py): launchable, never warmed
+#define AESW_ENC_FLAVOURS 5, 4, 3, 2, 1, 0
+#else
+#define AESW_ENC_FLAVOURS 2, 1, 0
+#endif
+template <int L_, bool XT_, int KM_, bool KEMIT_, int NT_> struct EncTag { static constexpr int L = L_, KM = KM_, NT = NT_; static constexpr bool XT = XT_, KEMIT = KEMIT_; };
+template <int L_, bool XT_, int NT_> struct KeyTag { static constexpr int L = L_, NT = NT_; static constexpr bool XT = XT_; };
+
+template <class F> static hipError_t with_encrypt_kernel(int layout, bool xt, int km, bool kemit, int nt, F &&f) {
+    // KM_PBK with KEMIT as a fourth key form, a value none of KM_PBK / KM_SHARED / KM_PRE has: a key slab is emitted by the
+    // per-block-key kernels only, so (KM_PRE, KEMIT) and (KM_SHARED, KEMIT) are never instantiated
+    constexpr int PBK_SLAB = 3;
+    return with_value<DENSE, VALUES, PACKED>(layout, [&](auto l) {
+        return with_value<1, 0>(xt, [&](auto x) {
+            return with_value<KM_PRE, KM_SHARED, PBK_SLAB, KM_PBK>(km == KM_PBK && kemit ? PBK_SLAB : km, [&](auto k) {
+                return with_value<AESW_ENC_FLAVOURS>(nt, [&](auto n) {
+                    constexpr bool KEMIT = AESW_V(k) == PBK_SLAB;
+                    return f(EncTag<AESW_V(l), AESW_V(x) != 0, KEMIT ? KM_PBK : AESW_V(k), KEMIT, AESW_V(n)>{});
+                });
+            });
+        });
+    });
+}
+
+template <class F> static hipError_t with_key_kernel(int layout, bool xt, int nt, F &&f) {  // VALUES key slabs are PACKED ones
+    return with_value<DENSE, PACKED>(layout, [&](auto l) { return with_value<1, 0>(xt, [&](auto x) { return with_nt(nt, [&](auto n) { return f(KeyTag<AESW_V(l), AESW_V(x) != 0, AESW_V(n)>{}); }); }); });
+}
+
+hipError_t launch_encrypt(const EncParams &p0, int layout, bool xt, int keymode, bool kemit, int waves, int nt,
+                          uint32_t cap /* max groups in flight */, uint32_t xcd_remap, uint32_t pad, hipStream_t s) {
+    if (waves < 1 || waves > 4 || keymode < 0 || keymode > 2) return hipErrorInvalidValue;
     const int bpg = waves * BPW;
     const uint64_t groups = (p0.n + bpg - 1) / bpg;
     if (groups == 0) return hipSuccess;
     if (groups > 0x7fffffffull) return hipErrorInvalidValue;
     EncParams p = p0;
     p.ngroups = (uint32_t)groups;
-    p.xcd_remap = xr;
-    const unsigned grid = cap && cap < groups ? cap : (unsigned)groups;
-    const size_t lds = TAB_BYTES + RKS_BYTES + (size_t)waves * enc_wave_lds<L>(KEMIT) + lds_pad;
-    // flush descriptors carry 16-bit LDS addresses: a group's staging must end below 64 KiB
-    if (TAB_BYTES + RKS_BYTES + (size_t)waves * enc_wave_lds<L>(KEMIT) > 65536 || !p0.ftab) return hipErrorInvalidValue;
-    {
-        hipError_t e = allow_large_lds(reinterpret_cast<const void *>(&encrypt_kernel<L, XT, KM, KEMIT, NT>), lds);
-        if (e != hipSuccess) return e;
-    }
-    // launched by name, not through a function-pointer variable: a host build with sanitizers silently drops the latter
-    hipLaunchKernelGGL((encrypt_kernel<L, XT, KM, KEMIT, NT>), dim3(grid), dim3(waves * LANES), lds, stream, p);
-    return hipGetLastError();
-}
-
-template <int L, bool XT, int KM, bool KEMIT>
-static hipError_t launch_enc_nt(const EncParams &p, int waves, int nt, uint32_t cap, uint32_t xr, uint32_t pad, hipStream_t s) {
-#ifdef AESW_DIAGNOSTIC
-    if (nt == 3) return launch_enc<L, XT, KM, KEMIT, 3>(p, waves, cap, xr, pad, s);
-    if (nt == 4) return launch_enc<L, XT, KM, KEMIT, 4>(p, waves, cap, xr, pad, s);
-    if (nt == 5) return launch_enc<L, XT, KM, KEMIT, 5>(p, waves, cap, xr, pad, s);
-#endif
-    return nt == 2 ? launch_enc<L, XT, KM, KEMIT, 2>(p, waves, cap, xr, pad, s)
-         : nt == 1 ? launch_enc<L, XT, KM, KEMIT, 1>(p, waves, cap, xr, pad, s)
-                   : launch_enc<L, XT, KM, KEMIT, 0>(p, waves, cap, xr, pad, s);
-}
-
-template <int L, bool XT>
-static hipError_t launch_enc_mode(const EncParams &p, int km, bool kemit, int waves, int nt, uint32_t cap, uint32_t xr, uint32_t pad, hipStream_t s) {
-    if (km == KM_PRE) return launch_enc_nt<L, XT, KM_PRE, false>(p, waves, nt, cap, xr, pad, s);
-    if (km == KM_SHARED) return launch_enc_nt<L, XT, KM_SHARED, false>(p, waves, nt, cap, xr, pad, s);
-    return kemit ? launch_enc_nt<L, XT, KM_PBK, true>(p, waves, nt, cap, xr, pad, s) : launch_enc_nt<L, XT, KM_PBK, false>(p, waves, nt, cap, xr, pad, s);
-}
-
-hipError_t launch_encrypt(const EncParams &p, int layout, bool xt, int keymode, bool kemit, int waves, int nt,
-                          uint32_t max_groups_in_flight, uint32_t xcd_remap, uint32_t pad, hipStream_t s) {
-    if (waves < 1 || waves > 4 || keymode < 0 || keymode > 2) return hipErrorInvalidValue;
-    const uint32_t cap = max_groups_in_flight;
     // a striding workgroup keeps its XCD class (id % 8) only when the stride is a multiple of 8
-    const uint32_t xr = (cap == 0 || cap % 8 == 0) ? xcd_remap : 0u;
-    if (layout == DENSE)
-        return xt ? launch_enc_mode<DENSE, true>(p, keymode, kemit, waves, nt, cap, xr, pad, s)
-                  : launch_enc_mode<DENSE, false>(p, keymode, kemit, waves, nt, cap, xr, pad, s);
-    if (layout == VALUES)
-        return xt ? launch_enc_mode<VALUES, true>(p, keymode, kemit, waves, nt, cap, xr, pad, s)
-                  : launch_enc_mode<VALUES, false>(p, keymode, kemit, waves, nt, cap, xr, pad, s);
-    return xt ? launch_enc_mode<PACKED, true>(p, keymode, kemit, waves, nt, cap, xr, pad, s)
-              : launch_enc_mode<PACKED, false>(p, keymode, kemit, waves, nt, cap, xr, pad, s);
+    p.xcd_remap = (cap == 0 || cap % 8 == 0) ? xcd_remap : 0u;
+    const unsigned grid = cap && cap < groups ? cap : (unsigned)groups;
+    return with_encrypt_kernel(layout, xt, keymode, kemit, nt, [&](auto tag) -> hipError_t {
+        using T = decltype(tag);
+        // flush descriptors carry 16-bit LDS addresses: a group's staging must end below 64 KiB
+        const size_t staging = TAB_BYTES + RKS_BYTES + (size_t)waves * enc_wave_lds<T::L>(T::KEMIT);
+        if (staging > 65536 || !p.ftab) return hipErrorInvalidValue;
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(&encrypt_kernel<T::L, T::XT, T::KM, T::KEMIT, T::NT>), staging + pad)) return e;
+        // launched by name, not through a function-pointer variable: a host build with sanitizers silently drops the latter
+        hipLaunchKernelGGL((encrypt_kernel<T::L, T::XT, T::KM, T::KEMIT, T::NT>), dim3(grid), dim3(waves * LANES), staging + pad, s, p);
+        return hipGetLastError();
+    });
 }
 
-template <int L, bool XT, int NT>
-static hipError_t launch_key_t(const KeyParams &p0, int waves, uint32_t xr, hipStream_t stream) {
+hipError_t launch_key(const KeyParams &p0, int layout, bool xt, int waves, int nt, uint32_t xcd_remap, hipStream_t s) {
+    if (waves < 1 || waves > 4) return hipErrorInvalidValue;
     const int bpg = waves * BPW;
     const uint64_t groups = (p0.n + bpg - 1) / bpg;
     if (groups == 0) return hipSuccess;
     if (groups > 0x7fffffffull) return hipErrorInvalidValue;
     KeyParams p = p0;
     p.ngroups = (uint32_t)groups;
-    p.xcd_remap = xr;
-    const size_t lds = TAB_BYTES + (size_t)waves * (Stage<L>::KEY_BYTES + (p.rk ? Stage<L>::RK_BYTES_W : 0));
-    {
-        hipError_t e = allow_large_lds(reinterpret_cast<const void *>(&key_kernel<L, XT, NT>), lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((key_kernel<L, XT, NT>), dim3((unsigned)groups), dim3(waves * LANES), lds, stream, p);
-    return hipGetLastError();
-}
-
-template <int L, bool XT>
-static hipError_t launch_key_nt(const KeyParams &p, int waves, int nt, uint32_t xr, hipStream_t s) {
-    return nt == 2 ? launch_key_t<L, XT, 2>(p, waves, xr, s) : nt == 1 ? launch_key_t<L, XT, 1>(p, waves, xr, s) : launch_key_t<L, XT, 0>(p, waves, xr, s);
-}
-
-hipError_t launch_key(const KeyParams &p, int layout, bool xt, int waves, int nt, uint32_t xcd_remap, hipStream_t s) {
-    if (waves < 1 || waves > 4) return hipErrorInvalidValue;
-    if (layout == DENSE) return xt ? launch_key_nt<DENSE, true>(p, waves, nt, xcd_remap, s) : launch_key_nt<DENSE, false>(p, waves, nt, xcd_remap, s);
-    return xt ? launch_key_nt<PACKED, true>(p, waves, nt, xcd_remap, s) : launch_key_nt<PACKED, false>(p, waves, nt, xcd_remap, s);
+    p.xcd_remap = xcd_remap;
+    return with_key_kernel(layout, xt, nt, [&](auto tag) -> hipError_t {
+        using T = decltype(tag);
+        const size_t lds = TAB_BYTES + (size_t)waves * (Stage<T::L>::KEY_BYTES + (p.rk ? Stage<T::L>::RK_BYTES_W : 0));
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(&key_kernel<T::L, T::XT, T::NT>), lds)) return e;
+        hipLaunchKernelGGL((key_kernel<T::L, T::XT, T::NT>), dim3((unsigned)groups), dim3(waves * LANES), lds, s, p);
+        return hipGetLastError();
+    });
 }
 
 // Dynamic LDS above 48 KiB needs hipFuncSetAttribute once per (kernel, device).  aesw_create() does it here for every
 // instantiation a context can launch, so that no launch ever changes a function attribute later -- in particular not
-// while the caller's stream is being captured into a hipGraph (tests/test_gpu_graph_capture.py).
-template <int L, bool XT, int KM, bool KEMIT>
-static hipError_t warm_enc_nt() {
-    const size_t lds = TAB_BYTES + RKS_BYTES + 4 * (size_t)enc_wave_lds<L>(KEMIT);  // the largest group any option can ask for
-    const size_t cap = lds > 65536 ? 65536 : lds;
-    hipError_t e = allow_large_lds(reinterpret_cast<const void *>(&encrypt_kernel<L, XT, KM, KEMIT, 0>), cap);
-    if (e == hipSuccess) e = allow_large_lds(reinterpret_cast<const void *>(&encrypt_kernel<L, XT, KM, KEMIT, 1>), cap);
-    if (e == hipSuccess) e = allow_large_lds(reinterpret_cast<const void *>(&encrypt_kernel<L, XT, KM, KEMIT, 2>), cap);
-    return e;
-}
-template <int L, bool XT>
-static hipError_t warm_layout() {
-    hipError_t e = warm_enc_nt<L, XT, KM_PRE, false>();
-    if (e == hipSuccess) e = warm_enc_nt<L, XT, KM_SHARED, false>();
-    if (e == hipSuccess) e = warm_enc_nt<L, XT, KM_PBK, false>();
-    if (e == hipSuccess) e = warm_enc_nt<L, XT, KM_PBK, true>();
-    return e;
-}
-template <int L, bool XT>
-static hipError_t warm_key() {
-    const size_t lds = TAB_BYTES + 4 * (size_t)(Stage<L>::KEY_BYTES + Stage<L>::RK_BYTES_W);
-    hipError_t e = allow_large_lds(reinterpret_cast<const void *>(&key_kernel<L, XT, 0>), lds);
-    if (e == hipSuccess) e = allow_large_lds(reinterpret_cast<const void *>(&key_kernel<L, XT, 1>), lds);
-    if (e == hipSuccess) e = allow_large_lds(reinterpret_cast<const void *>(&key_kernel<L, XT, 2>), lds);
-    return e;
-}
-template <bool XT>
-static hipError_t warm_all() {
-    hipError_t e = warm_layout<DENSE, XT>();
-    if (e == hipSuccess) e = warm_layout<PACKED, XT>();
-    if (e == hipSuccess) e = warm_layout<VALUES, XT>();
-    if (e == hipSuccess) e = warm_key<DENSE, XT>();
-    if (e == hipSuccess) e = warm_key<PACKED, XT>();
-    return e;
-}
+// while the caller's stream is being captured into a hipGraph (the capture tests of tests/test_gpu_round2.py).  Each for the
+// largest group any option can ask for: four waves, an encrypt group's staging capped at its 64 KiB bound.
 hipError_t warm_launch_attributes() {
-    hipError_t e = warm_all<true>();  // both table paths: "force_table_path" can flip a context later
-    if (e == hipSuccess) e = warm_all<false>();
+    hipError_t e = hipSuccess;
+    for (int xt = 1; xt >= 0; --xt) {  // both table paths: "force_table_path" can flip a context later
+        for (int layout : {DENSE, PACKED, VALUES})
+            for (int km : {KM_PRE, KM_SHARED, KM_PBK})
+                for (int kemit = 0; kemit <= (km == KM_PBK ? 1 : 0); ++kemit)
+                    for (int nt = 0; nt <= 2 && e == hipSuccess; ++nt)
+                        e = with_encrypt_kernel(layout, xt != 0, km, kemit != 0, nt, [](auto tag) {
+                            using T = decltype(tag);
+                            const size_t lds = TAB_BYTES + RKS_BYTES + 4 * (size_t)enc_wave_lds<T::L>(T::KEMIT);
+                            return allow_large_lds(reinterpret_cast<const void *>(&encrypt_kernel<T::L, T::XT, T::KM, T::KEMIT, T::NT>), lds > 65536 ? 65536 : lds);
+                        });
+        for (int layout : {DENSE, PACKED})
+            for (int nt = 0; nt <= 2 && e == hipSuccess; ++nt)
+                e = with_key_kernel(layout, xt != 0, nt, [](auto tag) {
+                    using T = decltype(tag);
+                    return allow_large_lds(reinterpret_cast<const void *>(&key_kernel<T::L, T::XT, T::NT>), TAB_BYTES + 4 * (size_t)(Stage<T::L>::KEY_BYTES + Stage<T::L>::RK_BYTES_W));
+                });
+    }
     return e;
 }
 
@@ -1179,15 +1160,11 @@ hipError_t launch_assemble(const AssembleParams &p0, bool as_fr, int nt, hipStre
         const uint64_t rows = (uint64_t)1 << p.k;
         const uint64_t segs = 1 + (rows + AES_ROWS - 1) / AES_ROWS;  // head + blocks (+ the tail, clipped in the kernel)
         const dim3 grid((AES_ROWS * 2 + 255) / 256, (unsigned)segs, p.col_count);
-        if (nt == 2) hipLaunchKernelGGL((assemble_fr_oneshot_kernel<2>), grid, dim3(256), 0, s, p);
-        else if (nt == 1) hipLaunchKernelGGL((assemble_fr_oneshot_kernel<1>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((assemble_fr_oneshot_kernel<0>), grid, dim3(256), 0, s, p);
+        with_nt(nt, [&](auto n) { hipLaunchKernelGGL((assemble_fr_oneshot_kernel<AESW_V(n)>), grid, dim3(256), 0, s, p); });
         return hipGetLastError();
     }
     if (choice == 2) {
-        if (nt == 2) launch_assemble_aligned<2>(p.geometry, p.k, p.col_count, s, p);
-        else if (nt == 1) launch_assemble_aligned<1>(p.geometry, p.k, p.col_count, s, p);
-        else launch_assemble_aligned<0>(p.geometry, p.k, p.col_count, s, p);
+        with_nt(nt, [&](auto n) { launch_assemble_aligned<AESW_V(n)>(p.geometry, p.k, p.col_count, s, p); });
         return hipGetLastError();
     }
     // the striding kernel: any K, any column count (also where geometry 1's segment grid or the aligned forms do not apply)
@@ -1196,9 +1173,7 @@ hipError_t launch_assemble(const AssembleParams &p0, bool as_fr, int nt, hipStre
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks == 0) blocks = 1;
     if (!as_fr) hipLaunchKernelGGL((assemble_kernel<false, 0>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (nt == 2) hipLaunchKernelGGL((assemble_kernel<true, 2>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (nt == 1) hipLaunchKernelGGL((assemble_kernel<true, 1>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((assemble_kernel<true, 0>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else with_nt(nt, [&](auto n) { hipLaunchKernelGGL((assemble_kernel<true, AESW_V(n)>), dim3((unsigned)blocks), dim3(256), 0, s, p); });
     return hipGetLastError();
 }
 
@@ -1207,9 +1182,7 @@ static hipError_t launch_expand_fr_oneshot(const uint8_t *cells, uint64_t n_cell
     const uint64_t per = GEO == 1 ? 256 : 1024;
     const uint64_t blocks = (n_cells * 2 + per - 1) / per;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (nt == 2) hipLaunchKernelGGL((expand_fr_oneshot_kernel<2, GEO>), dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o);
-    else if (nt == 1) hipLaunchKernelGGL((expand_fr_oneshot_kernel<1, GEO>), dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o);
-    else hipLaunchKernelGGL((expand_fr_oneshot_kernel<0, GEO>), dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o);
+    with_nt(nt, [&](auto n) { hipLaunchKernelGGL((expand_fr_oneshot_kernel<AESW_V(n), GEO>), dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o); });
     return hipGetLastError();
 }
 
@@ -1221,9 +1194,7 @@ hipError_t launch_expand_fr(const uint8_t *cells, uint64_t n_cells, const void *
     if (blocks > 256 * 8) blocks = 256 * 8;
     const u32x4 *lut = reinterpret_cast<const u32x4 *>(fr_lut);
     u32x4 *o = reinterpret_cast<u32x4 *>(out);
-    if (nt == 2) hipLaunchKernelGGL(expand_fr_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o);
-    else if (nt == 1) hipLaunchKernelGGL(expand_fr_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o);
-    else hipLaunchKernelGGL(expand_fr_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o);
+    with_nt(nt, [&](auto n) { hipLaunchKernelGGL(expand_fr_kernel<AESW_V(n)>, dim3((unsigned)blocks), dim3(256), 0, s, cells, n_cells, lut, o); });
     return hipGetLastError();
 }
 

@@ -3,13 +3,14 @@ CPU only: every tools/*.py parses, and what it takes from the package, from benc
 every tools/*.hip and tools/*.c (and the plain-C examples) passes a syntax-only compile against the current headers."""
 import ast
 import importlib.util
-import re
 import shutil
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import pytest
+
+import option_table
 
 ROOT = Path(__file__).resolve().parent.parent
 TOOLS = ROOT / "tools"
@@ -22,10 +23,9 @@ def _bench():
     return mod
 
 
-def test_python_tools_parse_and_use_names_that_exist(pkg):
+def test_python_tools_parse_and_use_names_that_exist(pkg, tmp_path):
     bench = _bench()
-    api_src = (ROOT / "halo2-aes_amd" / "csrc" / "aesw_api.cpp").read_text()
-    options = set(re.findall(r'std::strcmp\(name, "([a-z0-9_]+)"\)', api_src))
+    options = set(option_table.dump(option_table.build_driver(tmp_path)))  # the rows of csrc/aesw_options.h
     assert {"store_mode", "key_slots", "arena_cache", "split_small"} <= options
     ctx_methods = set(dir(pkg.Context))
     scripts = sorted(TOOLS.glob("*.py")) + sorted((ROOT / "examples").glob("*.py"))
@@ -45,7 +45,7 @@ def test_python_tools_parse_and_use_names_that_exist(pkg):
             if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in ("set_option", "get_option") \
                     and node.args and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str):
                 if node.args[0].value not in options:
-                    problems.append("%s:%d option %r is not in aesw_set_option / aesw_get_option" % (path.name, node.lineno, node.args[0].value))
+                    problems.append("%s:%d option %r is not in the option table (aesw_options.h)" % (path.name, node.lineno, node.args[0].value))
     assert not problems, "\n".join(problems)
 
 
