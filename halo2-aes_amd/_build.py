@@ -83,7 +83,7 @@ def build_host(force: bool = False) -> Path:
 PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_keyring.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp",
                                       "aesw_comm.cpp", "aesw_group.cpp", "aesw_circuits.cpp")]
 PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h",
-                                      "aesw_keyring.h", "aesw_options.h")] + \
+                                      "aesw_keyring.h", "aesw_options.h", "aesw_placement.h")] + \
     [INCLUDE / "aesw.h"]
 
 
@@ -103,7 +103,7 @@ def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_so
 # satellite's live one level down, in csrc/<name>/.  Each entry: its sources, the headers it depends on beyond
 # SATELLITE_HEADERS, its public header.
 SATELLITE_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_check.h", "aesw_layout.h", "aesw_internal.h", "aesw_ctx.h",
-                                        "aesw_keyring.h", "aesw_options.h")] + [INCLUDE / "aesw.h"]
+                                        "aesw_keyring.h", "aesw_options.h", "aesw_placement.h")] + [INCLUDE / "aesw.h"]
 SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),

@@ -472,38 +472,20 @@ int aesw_selector_tags(uint8_t enc_tag[AESW_AES_ROWS], uint8_t key_tag[AESW_KEY_
     return AESW_OK;
 }
 
-// FixedAes128Config::aes_callable, src/aes128.rs:303-325: set 0 is charged
-// KEY_SCHEDULE_ROWS (1760) of its 2^K rows, every set holds whole 1360-row
-// blocks.  Rows: set 0 starts behind the 400 rows the key schedule really uses.
-static uint64_t set_capacity(uint32_t k, uint32_t set) {
-    uint64_t max_row = (uint64_t)1 << k;
-    if (set == 0) {
-        if (max_row < AESW_KEY_SCHEDULE_ROWS) return 0;
-        max_row -= AESW_KEY_SCHEDULE_ROWS;
-    }
-    return max_row / AESW_AES_ROWS;
-}
-
+// The placement rule of FixedAes128Config::aes_callable (src/aes128.rs:303-325) is aesw_placement.h's.
 uint64_t aesw_block_capacity(uint32_t k, uint32_t n_sets) {
     if (k > 40 || n_sets == 0) return 0;
-    uint64_t total = 0;
-    for (uint32_t s = 0; s < n_sets; ++s) total += set_capacity(k, s);
-    return total;
+    return Placement(k).total(n_sets);
 }
 
 int aesw_block_placement(uint32_t k, uint32_t n_sets, uint64_t b, uint32_t *set, uint64_t *row) {
     if (k > 40 || n_sets == 0 || !set || !row) return AESW_ERR_INVALID_ARG;
-    uint64_t left = b;
-    for (uint32_t s = 0; s < n_sets; ++s) {
-        const uint64_t cap = set_capacity(k, s);
-        if (left < cap) {
-            *set = s;
-            *row = (s == 0 ? AESW_KEY_ROWS : 0) + left * AESW_AES_ROWS;
-            return AESW_OK;
-        }
-        left -= cap;
-    }
-    return AESW_ERR_CAPACITY;
+    const Placement pl(k);
+    if (b >= pl.total(n_sets)) return AESW_ERR_CAPACITY;
+    uint64_t bi;
+    pl.locate(b, *set, bi);
+    *row = Placement::row_of(*set, bi);
+    return AESW_OK;
 }
 
 int aesw_assemble_selectors(uint32_t k, uint32_t n_sets, uint64_t n_blocks, uint8_t *selectors, uint8_t *fixed) {
@@ -523,10 +505,12 @@ int aesw_assemble_selectors(uint32_t k, uint32_t n_sets, uint64_t n_blocks, uint
         selectors[(size_t)(5 * n_sets) * rows + r] = q[r];
         if (fixed) fixed[r] = rc[r];
     }
-    for (uint64_t b = 0; b < n_blocks; ++b) {
+    const Placement pl(k);
+    for (uint64_t b = 0; b < n_blocks; ++b) {  // below the capacity: checked above
         uint32_t set;
-        uint64_t row;
-        if (aesw_block_placement(k, n_sets, b, &set, &row) != AESW_OK) return AESW_ERR_CAPACITY;
+        uint64_t bi;
+        pl.locate(b, set, bi);
+        const uint64_t row = Placement::row_of(set, bi);
         for (uint32_t r = 0; r < AES_ROWS; ++r)
             if (enc[r]) sel(set, enc[r])[row + r] = 1;
     }

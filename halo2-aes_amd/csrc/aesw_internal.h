@@ -3,10 +3,12 @@
 // aesw_hostpath.cpp; not part of the public ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/aesw.h"
 #include "aesw_check.h"
+#include "aesw_placement.h"
 
 namespace aesw {
 
@@ -62,8 +64,10 @@ struct AssembleParams {
     uint32_t sx, sy, sz, kxs, kys, kzs;  // bytes per block / per key
     int packed;
     int geometry;         // Fr cells: 1 = one-shot 4 KiB workgroups on a (chunk, segment, column) grid, 0 = striding workgroups
-    uint64_t cap0, capn;  // blocks per column set (set 0 / the others): filled by the launcher
+    Placement place;      // blocks per column set (aesw_placement.h): filled by the launcher
 };
+static_assert(sizeof(AssembleParams) == 144 && offsetof(AssembleParams, n_blocks) == 72 && offsetof(AssembleParams, geometry) == 124 &&
+              offsetof(AssembleParams, place) == 128 && offsetof(Placement, capn) == 8, "kernel arguments are read by offset");
 hipError_t launch_assemble(const AssembleParams &p, bool as_fr, int store_mode, hipStream_t s);
 // placement probe of aesw_columns_alloc: columns x, y, z, w, kx, ky, kz (null = absent) of n blocks
 struct ProbeParams {
@@ -114,12 +118,15 @@ struct CircAsmParams {
     const void *fr_lut;
     uint8_t *out;                      // n_circuits x (3 n_sets + 1) << k cells
     const uint64_t *offsets;           // n_circuits + 1 (device)
-    uint64_t cap0, capn, cap;          // filled by the launcher
+    aesw::Placement place;             // filled by the launcher, as is cap = place.total(n_sets)
+    uint64_t cap;
     uint32_t k, n_sets;
     uint32_t sx, sy, sz, kxs, kys, kzs;
     int packed;
     uint32_t c_first, cshift;          // filled by the launcher
 };
+static_assert(sizeof(CircAsmParams) == 152 && offsetof(CircAsmParams, offsets) == 72 && offsetof(CircAsmParams, place) == 80 &&
+              offsetof(CircAsmParams, cap) == 96 && offsetof(CircAsmParams, k) == 104 && offsetof(CircAsmParams, cshift) == 144, "kernel arguments are read by offset");
 hipError_t launch_assemble_circuits(const CircAsmParams &p, uint32_t n_circuits, bool as_fr, hipStream_t s);
 }  // namespace aesw_circ
 

@@ -698,32 +698,14 @@ __global__ void __launch_bounds__(256) expand_fr_oneshot_kernel(const uint8_t *_
 // ---------------------------------------------------------------------------
 // full advice columns of a K/N circuit (bytes or Fr cells)
 // ---------------------------------------------------------------------------
-// Cell (column j, row r) -> the slab byte synthesize() puts there (aes_callable
-// placement, src/aes128.rs:303-325), 0 when nothing is ever assigned.
+// Which slab byte synthesize() puts into cell (column, row), 0 when nothing is ever assigned, is aesw_placement.h's to say
+// (aes_callable's placement, src/aes128.rs:303-325): column_source() for what the column decides, cell_byte() for the row.
+template <class P>  // AssembleParams or aesw_circ::CircAsmParams
+__device__ __forceinline__ ColumnSource column_of(const P &a, uint32_t col) {
+    return column_source(a.place, col, a.n_sets, a.kx, a.ky, a.kz, a.x, a.y, a.z, a.sx, a.sy, a.sz);
+}
 __device__ __forceinline__ uint32_t advice_cell(const AssembleParams &a, uint32_t col, uint64_t row) {
-    const uint32_t n_adv = 3 * a.n_sets;
-    if (col == n_adv) return (row < WORDS_ROWS && a.kw) ? a.kw[row] : 0u;  // words_column
-    const uint32_t set = col / 3, c = col - 3 * set;
-    const uint64_t rows = (uint64_t)1 << a.k;
-    const uint64_t cap0 = rows >= 1760 ? (rows - 1760) / AES_ROWS : 0, capn = rows / AES_ROWS;
-    if (set == 0 && row < KEY_ROWS) {
-        const uint8_t *kc = c == 0 ? a.kx : c == 1 ? a.ky : a.kz;
-        if (!kc) return 0u;
-        const int idx = a.packed ? packed_index_key((int)c, (int)row) : (int)row;
-        return idx >= 0 ? kc[idx] : 0u;
-    }
-    const uint64_t base = set == 0 ? KEY_ROWS : 0;
-    if (row < base) return 0u;
-    const uint64_t rr = row - base;
-    const uint64_t bi = rr / AES_ROWS;
-    const uint32_t r = (uint32_t)(rr - bi * AES_ROWS);
-    if (bi >= (set == 0 ? cap0 : capn)) return 0u;
-    const uint64_t b = (set == 0 ? 0 : cap0 + (uint64_t)(set - 1) * capn) + bi;
-    if (b >= a.n_blocks) return 0u;
-    const uint8_t *sc = c == 0 ? a.x : c == 1 ? a.y : a.z;
-    const uint32_t stride = c == 0 ? a.sx : c == 1 ? a.sy : a.sz;
-    const int idx = a.packed ? packed_index_enc((int)c, (int)r) : (int)r;
-    return idx >= 0 ? sc[b * stride + idx] : 0u;
+    return cell_byte(column_of(a, col), a.kw, a.packed, row, a.n_blocks);
 }
 
 // Round 3: the Fr form of the columns as ONE-SHOT workgroups without a division.  A column of 2^k rows
@@ -742,37 +724,20 @@ __global__ void __launch_bounds__(256) assemble_fr_oneshot_kernel(const Assemble
     const uint32_t piece = blockIdx.x * 256 + threadIdx.x;  // 16-byte piece of the segment: 2 per row
     const uint32_t r = piece >> 1;                           // row inside the segment
     if (r >= AES_ROWS) return;
-    const uint32_t col = a.col_first + blockIdx.z, seg = blockIdx.y;
-    const uint32_t n_adv = 3 * a.n_sets;
-    const bool words = col == n_adv;
-    const uint32_t set = col / 3, c = col - 3 * set;
+    const uint32_t seg = blockIdx.y;
+    const ColumnSource s = column_of(a, a.col_first + blockIdx.z);
     const uint64_t rows = (uint64_t)1 << a.k;
-    const uint32_t base = (!words && set == 0) ? KEY_ROWS : 0;
     uint64_t row;
-    uint32_t v = 0;
+    uint32_t v;
     if (seg == 0) {  // head: key rows of set 0
-        if (r >= base || r >= rows) return;  // (a circuit of fewer than 400 rows clips the key slab: K <= 8, found by round 4's K = 7 test)
+        if (r >= s.base || r >= rows) return;  // (a circuit of fewer than 400 rows clips the key slab: K <= 8, found by round 4's K = 7 test)
         row = r;
-        const uint8_t *kc = c == 0 ? a.kx : c == 1 ? a.ky : a.kz;
-        if (kc) {
-            const int idx = a.packed ? packed_index_key((int)c, (int)r) : (int)r;
-            if (idx >= 0) v = kc[idx];
-        }
+        v = key_byte(s, a.packed, r);
     } else {
         const uint64_t bi = seg - 1;
-        row = base + bi * AES_ROWS + r;
+        row = s.base + bi * AES_ROWS + r;
         if (row >= rows) return;
-        if (words) {
-            if (row < WORDS_ROWS && a.kw) v = a.kw[row];
-        } else if (bi < (set == 0 ? a.cap0 : a.capn)) {
-            const uint64_t b = (set == 0 ? 0 : a.cap0 + (uint64_t)(set - 1) * a.capn) + bi;
-            if (b < a.n_blocks) {
-                const uint8_t *sc = c == 0 ? a.x : c == 1 ? a.y : a.z;
-                const uint32_t stride = c == 0 ? a.sx : c == 1 ? a.sy : a.sz;
-                const int idx = a.packed ? packed_index_enc((int)c, (int)r) : (int)r;
-                if (idx >= 0) v = sc[b * stride + idx];
-            }
-        }
+        v = s.words ? words_byte(a.kw, row) : block_byte(s, a.packed, bi, r, a.n_blocks);
     }
     const u32x4 *lut = reinterpret_cast<const u32x4 *>(a.fr_lut);  // 8 KiB, L1 / L2 resident
     u32x4 *out = reinterpret_cast<u32x4 *>(a.out) + (((uint64_t)blockIdx.z << a.k) + row) * 2 + (piece & 1);
@@ -794,33 +759,14 @@ __global__ void __launch_bounds__(THREADS) assemble_fr_aligned_kernel(const Asse
     // every kernel argument in SGPRs before anything else: left alone the compiler loads them where they are first used,
     // behind branches, and a one-shot workgroup then waits for four scalar loads one after the other (worth 3 % in geometry 2)
     asm volatile("" ::"s"(a.x), "s"(a.y), "s"(a.z), "s"(a.kw), "s"(a.kx), "s"(a.ky), "s"(a.kz), "s"(a.fr_lut), "s"(a.out), "s"(a.n_blocks),
-                 "s"(a.k), "s"(a.n_sets), "s"(a.col_first), "s"(a.sx), "s"(a.sy), "s"(a.sz), "s"(a.packed), "s"(a.cap0), "s"(a.capn));
-    const uint32_t col = a.col_first + blockIdx.y;
-    const uint32_t n_adv = 3 * a.n_sets;
-    const bool words = col == n_adv;
-    const uint32_t set = col / 3, c = col - 3 * set;
-    const uint32_t base = (!words && set == 0) ? KEY_ROWS : 0;
-    const uint8_t *kc = c == 0 ? a.kx : c == 1 ? a.ky : a.kz;
-    const uint8_t *sc = c == 0 ? a.x : c == 1 ? a.y : a.z;
-    const uint32_t stride = c == 0 ? a.sx : c == 1 ? a.sy : a.sz;
-    const uint64_t cap = set == 0 ? a.cap0 : a.capn;
-    const uint64_t b0 = set == 0 ? 0 : a.cap0 + (uint64_t)(set - 1) * a.capn;
+                 "s"(a.k), "s"(a.n_sets), "s"(a.col_first), "s"(a.sx), "s"(a.sy), "s"(a.sz), "s"(a.packed), "s"(a.place.cap0), "s"(a.place.capn));
+    const ColumnSource s = column_of(a, a.col_first + blockIdx.y);
     const uint32_t half = threadIdx.x & 1;
     uint32_t row[PIECES], v[PIECES];
 #pragma unroll
     for (int j = 0; j < PIECES; ++j) {
         row[j] = ((blockIdx.x * PIECES + j) * THREADS + threadIdx.x) >> 1;
-        v[j] = 0;
-        if (words) {
-            if (row[j] < WORDS_ROWS && a.kw) v[j] = a.kw[row[j]];
-        } else if (row[j] < base) {
-            const int idx = a.packed ? packed_index_key((int)c, (int)row[j]) : (int)row[j];
-            if (kc && idx >= 0) v[j] = kc[idx];
-        } else {
-            const uint32_t rr = row[j] - base, bi = rr / AES_ROWS, r = rr - bi * AES_ROWS;
-            const int idx = a.packed ? packed_index_enc((int)c, (int)r) : (int)r;
-            if (bi < cap && b0 + bi < a.n_blocks && idx >= 0) v[j] = sc[(b0 + bi) * stride + idx];
-        }
+        v[j] = cell_byte(s, a.kw, a.packed, row[j], a.n_blocks);
     }
     const u32x4 *lut = reinterpret_cast<const u32x4 *>(a.fr_lut);
     u32x4 *out = reinterpret_cast<u32x4 *>(a.out) + ((uint64_t)blockIdx.y << (a.k + 1)) + half;
@@ -1150,11 +1096,7 @@ static void launch_assemble_aligned(int geo, uint32_t k, uint32_t cols, hipStrea
 
 hipError_t launch_assemble(const AssembleParams &p0, bool as_fr, int nt, hipStream_t s) {
     AssembleParams p = p0;
-    {   // capacities of aes_callable (src/aes128.rs:303-325): computed here so that no kernel divides
-        const uint64_t rows = (uint64_t)1 << p.k;
-        p.cap0 = rows >= 1760 ? (rows - 1760) / AES_ROWS : 0;
-        p.capn = rows / AES_ROWS;
-    }
+    p.place = Placement(p.k);  // computed here so that no kernel divides
     const int choice = assemble_kernel_choice(as_fr, p.geometry, p.k, p.col_count);
     if (choice == 1) {
         const uint64_t rows = (uint64_t)1 << p.k;
@@ -1219,39 +1161,20 @@ __global__ void __launch_bounds__(128) circuit_assemble_kernel(const CircAsmPara
     const uint32_t col = blockIdx.y, cols = 3 * a.n_sets + 1;
     const uint64_t o0 = a.offsets[ci], o1 = a.offsets[ci + 1];
     const uint64_t n_c = o1 > o0 ? (o1 - o0 < a.cap ? o1 - o0 : a.cap) : 0;
-    const bool words = col == 3 * a.n_sets;
-    const uint32_t set = col / 3, c = col - 3 * set;
-    const uint32_t base = (!words && set == 0) ? KEY_ROWS : 0;
-    const uint8_t *kc0 = c == 0 ? a.kx : c == 1 ? a.ky : a.kz;
-    const uint32_t kstride = c == 0 ? a.kxs : c == 1 ? a.kys : a.kzs;
-    const uint8_t *kc = kc0 ? kc0 + (uint64_t)ci * kstride : nullptr;
+    ColumnSource s = column_of(a, col);  // of the batch: moved to circuit ci's key slab and first block
+    const uint32_t kstride = s.c == 0 ? a.kxs : s.c == 1 ? a.kys : a.kzs;
+    s.kc = s.kc ? s.kc + (uint64_t)ci * kstride : nullptr;
+    s.sc += o0 * s.stride;  // dereferenced only below n_c
     const uint8_t *kw = a.kw ? a.kw + (uint64_t)ci * WORDS_ROWS : nullptr;
-    const uint32_t stride = c == 0 ? a.sx : c == 1 ? a.sy : a.sz;
-    const uint8_t *sc = (c == 0 ? a.x : c == 1 ? a.y : a.z) + o0 * stride;  // dereferenced only below n_c
-    const uint64_t cap = set == 0 ? a.cap0 : a.capn;
-    const uint64_t b0 = set == 0 ? 0 : a.cap0 + (uint64_t)(set - 1) * a.capn;
     const uint32_t rows = 1u << a.k;
     const uint64_t first_cell = ((uint64_t)ci * cols + col) << a.k;
-    // the cell code is written out as in assemble_fr_aligned_kernel (no lambda): the index helpers then see the same
-    // argument ranges from every caller, and the aesw:: kernels that share them compile to the code they had before
     constexpr int PER = AS_FR ? 2 : 4;
     const uint32_t half = threadIdx.x & 1;
     uint32_t row[PER], v[PER];
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         row[j] = AS_FR ? ((chunk * 2 + j) * 128 + threadIdx.x) >> 1 : chunk * RPW + threadIdx.x * 4 + j;  // rows % 4 == 0 (k >= 2)
-        v[j] = 0;
-        if (row[j] >= rows) continue;
-        if (words) {
-            if (row[j] < WORDS_ROWS && kw) v[j] = kw[row[j]];
-        } else if (row[j] < base) {
-            const int idx = a.packed ? packed_index_key((int)c, (int)row[j]) : (int)row[j];
-            if (kc && idx >= 0) v[j] = kc[idx];
-        } else {
-            const uint32_t rr = row[j] - base, bi = rr / AES_ROWS, r = rr - bi * AES_ROWS;
-            const int idx = a.packed ? packed_index_enc((int)c, (int)r) : (int)r;
-            if (bi < cap && b0 + bi < n_c && idx >= 0) v[j] = sc[(b0 + bi) * stride + idx];
-        }
+        v[j] = row[j] < rows ? cell_byte(s, kw, a.packed, row[j], n_c) : 0u;
     }
     if (AS_FR) {
         const u32x4 *lut = reinterpret_cast<const u32x4 *>(a.fr_lut);
@@ -1270,10 +1193,8 @@ __global__ void __launch_bounds__(128) circuit_assemble_kernel(const CircAsmPara
 hipError_t launch_assemble_circuits(const CircAsmParams &p0, uint32_t n_circuits, bool as_fr, hipStream_t s) {
     if (n_circuits == 0 || p0.k < 2 || p0.k > 30) return hipErrorInvalidValue;
     CircAsmParams p = p0;
-    const uint64_t rows = (uint64_t)1 << p.k;
-    p.cap0 = rows >= 1760 ? (rows - 1760) / AES_ROWS : 0;
-    p.capn = rows / AES_ROWS;
-    p.cap = p.cap0 + (uint64_t)(p.n_sets - 1) * p.capn;
+    p.place = Placement(p.k);
+    p.cap = p.place.total(p.n_sets);
     const uint32_t rpw_log = as_fr ? 7 : 9;
     p.cshift = p.k > rpw_log ? p.k - rpw_log : 0;
     // the grid's x dimension stays below 2^31 workgroups: circuits in slices (one launch for all but the largest shapes)

@@ -24,6 +24,7 @@
 #include "../aesw_check_dev.h"
 #include "../aesw_circ_search.h"
 #include "../aesw_ctx.h"
+#include "../aesw_placement.h"
 
 namespace aesw_cols {
 using namespace aesw;
@@ -40,11 +41,14 @@ struct ColsParams {
     const uint8_t *tab768;
     const u32x4 *fr_lut;      // 256 x 2 halves
     uint64_t *report;         // 12 x u64
-    uint64_t n, cap, cap0, capn;
+    uint64_t n, cap;          // cap = place.total(n_sets)
+    Placement place;
     uint64_t run;             // consecutive blocks a wave takes at a time
     uint32_t n_circuits, k, n_sets;
     uint32_t hmul, hbits;     // the Fr hash (as_fr)
 };
+static_assert(sizeof(ColsParams) == 136 && offsetof(ColsParams, n) == 72 && offsetof(ColsParams, cap) == 80 && offsetof(ColsParams, place) == 88 &&
+              offsetof(ColsParams, run) == 104 && offsetof(ColsParams, hbits) == 128, "kernel arguments are read by offset");
 
 // what a lane found among the cells themselves
 struct CellAcc {
@@ -214,13 +218,9 @@ __global__ void __launch_bounds__(256) cols_check_kernel(const ColsParams p) {
                 if (p.ct) lit |= (uint32_t)p.ct[b * 16 + lane] << 8;
             }
             if (!nx_ok) return;
-            uint32_t set = 0, bi = (uint32_t)j;
-            if (j >= p.cap0) {
-                const uint32_t jj = (uint32_t)(j - p.cap0), capn = (uint32_t)p.capn;
-                set = 1 + jj / capn;
-                bi = jj - (set - 1) * capn;
-            }
-            nx_cell = cell_of(c, 3 * set, (set == 0 ? KEY_ROWS : 0) + (uint64_t)bi * AES_ROWS);
+            uint32_t set, bi;  // 32 bits: j < cap < 2^30 / 1360 x 1024 (the entry point's k and n_sets)
+            p.place.locate(j, set, bi);
+            nx_cell = cell_of(c, 3 * set, Placement::row_of(set, bi));
             if (!AS_FR) {
                 sx.load(p.cols + nx_cell, lane); sy.load(p.cols + nx_cell + ((uint64_t)1 << p.k), lane); sz.load(p.cols + nx_cell + ((uint64_t)2 << p.k), lane);
             }
@@ -272,9 +272,7 @@ __global__ void __launch_bounds__(256) cols_check_kernel(const ColsParams p) {
                 const uint64_t o0 = offs[c], o1 = offs[c + 1];
                 const uint64_t n_c = o1 > o0 ? (o1 - o0 < p.cap ? o1 - o0 : p.cap) : 0;
                 const uint32_t set = col / 3;
-                const uint64_t cap_s = set == 0 ? p.cap0 : p.capn, b0s = set == 0 ? 0 : p.cap0 + (uint64_t)(set - 1) * p.capn;
-                const uint64_t nb = n_c > b0s ? (n_c - b0s < cap_s ? n_c - b0s : cap_s) : 0;
-                t0 = (set == 0 ? KEY_ROWS : 0) + nb * AES_ROWS;
+                t0 = Placement::row_of(set, p.place.filled(set, n_c));
             }
             const uint64_t hi = ((uint64_t)chunk + 1) << cs;
             uint64_t lo = (uint64_t)chunk << cs;
@@ -466,10 +464,8 @@ int aesw_cols_check_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32_t 
     p.fr_lut = reinterpret_cast<const aesw::u32x4 *>(ctx->d_fr_lut);
     p.report = reinterpret_cast<uint64_t *>(d_report);
     p.n = n;
-    const uint64_t rows = (uint64_t)1 << k;
-    p.cap0 = rows >= AESW_KEY_SCHEDULE_ROWS ? (rows - AESW_KEY_SCHEDULE_ROWS) / AESW_AES_ROWS : 0;
-    p.capn = rows / AESW_AES_ROWS;
-    p.cap = aesw_block_capacity(k, n_sets);
+    p.place = aesw::Placement(k);
+    p.cap = p.place.total(n_sets);
     p.n_circuits = n_circuits; p.k = k; p.n_sets = n_sets;
     p.hmul = h.mul; p.hbits = h.bits;
     HIP_TRY(ctx, aesw_cols::launch_cols_check(p, as_fr != 0, reinterpret_cast<hipStream_t>(stream)));

@@ -432,7 +432,7 @@ def _small_k_expectation(oracle, k, n_sets, key):
     return m
 
 
-@pytest.mark.parametrize("k,n_sets,spare", [(7, 2, 0), (8, 2, 0), (9, 1, 0), (11, 2, 0), (16, 3, 20)])
+@pytest.mark.parametrize("k,n_sets,spare", [(7, 2, 0), (8, 2, 0), (9, 1, 0), (11, 2, 0), (12, 2, 0), (12, 3, 1), (12, 3, 3), (16, 3, 20)])
 def test_assemble_geometries_at_the_fallback_boundary_and_with_a_partly_filled_last_set(ctx, pkg, oracle, k, n_sets, spare):
     """The five "assemble_geometry" forms write identical Fr columns and byte columns on both sides of K = 8 (below it the
     aligned forms 2-4 fall back to the striding kernel, aesw_layout.h assemble_kernel_choice), at K = 11 (the smallest circuit
@@ -442,7 +442,7 @@ def test_assemble_geometries_at_the_fallback_boundary_and_with_a_partly_filled_l
     lut = _fr_lut()
     cap = pkg.block_capacity(k, n_sets)
     n = cap - spare
-    assert n >= 0 and (k != 11 or n == 1) and (k != 16 or n == 46 + 48 + 48 - 20)
+    assert n >= 0 and (k != 11 or n == 1) and (k != 12 or n == {(2, 0): 4, (3, 1): 6, (3, 3): 4}[n_sets, spare]) and (k != 16 or n == 46 + 48 + 48 - 20)
     rng = np.random.default_rng(1000 + k)
     key = rng.integers(0, 256, 16, dtype=np.uint8)
     pts = rng.integers(0, 256, (max(n, 1), 16), dtype=np.uint8)
