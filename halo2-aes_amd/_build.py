@@ -82,7 +82,7 @@ def build_host(force: bool = False) -> Path:
 # key_ab.py, sanitize.sh) take it from here.
 PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_keyring.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp",
                                       "aesw_comm.cpp", "aesw_group.cpp", "aesw_circuits.cpp")]
-PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h",
+PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_flush.h", "aesw_slabmap.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h",
                                       "aesw_keyring.h", "aesw_options.h", "aesw_placement.h")] + \
     [INCLUDE / "aesw.h"]
 
@@ -102,7 +102,7 @@ def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_so
 # The checker libraries next to libaesw.so.  csrc/ itself holds exactly the sources of libaesw.so (PRODUCT_SOURCES); a
 # satellite's live one level down, in csrc/<name>/.  Each entry: its sources, the headers it depends on beyond
 # SATELLITE_HEADERS, its public header.
-SATELLITE_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_check.h", "aesw_layout.h", "aesw_internal.h", "aesw_ctx.h",
+SATELLITE_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_check.h", "aesw_layout.h", "aesw_slabmap.h", "aesw_internal.h", "aesw_ctx.h",
                                         "aesw_keyring.h", "aesw_options.h", "aesw_placement.h")] + [INCLUDE / "aesw.h"]
 SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),

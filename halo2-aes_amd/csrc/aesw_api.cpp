@@ -15,7 +15,6 @@
 
 #include "../../include/aesw.h"
 #include "aesw_internal.h"
-#include "aesw_layout.h"
 #include "aesw_check.h"
 
 using namespace aesw;
@@ -124,8 +123,7 @@ int fill_assemble_params(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t n_
     p->n_sets = n_sets;
     p->col_first = 0;
     p->col_count = 3 * n_sets + 1;
-    p->sx = aesw_column_stride(layout, 0); p->sy = aesw_column_stride(layout, 1); p->sz = aesw_column_stride(layout, 2);
-    p->kxs = aesw_key_column_stride(layout, 0); p->kys = aesw_key_column_stride(layout, 1); p->kzs = aesw_key_column_stride(layout, 2);
+    set_strides(*p, slab_strides(layout));
     p->packed = layout == AESW_LAYOUT_PACKED;
     p->geometry = ctx->opt.asm_geo;
     return AESW_OK;
@@ -154,7 +152,8 @@ int check_witness_impl(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_keys
     p.n = n;
     p.per_block_keys = per_block_keys ? 1u : 0u;
     p.skip_shared_key = skip_shared_key ? 1u : 0u;
-    p.sx = cg.sx; p.sy = cg.sy; p.sz = cg.sz; p.kxs = cg.kxs; p.kys = cg.kys; p.kzs = cg.kzs; p.bi = cg.bi;
+    set_strides(p, slab_strides(layout));  // DENSE or PACKED (checked above): check_geo's domain
+    p.bi = cg.bi;
     p.img = (cg.bi + cg.ki + 15u) & ~15u;
     HIP_TRY(ctx, launch_check(p, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;
@@ -188,7 +187,7 @@ bool validate_encrypt(const aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d
     *status = AESW_OK;
     if (n == 0) return false;
     *status = AESW_ERR_INVALID_ARG;
-    const bool has_x = aesw_column_stride(layout, 0) != 0;  // AESW_LAYOUT_VALUES has no x column: d_x is ignored
+    const bool has_x = slab_strides(layout).x != 0;  // AESW_LAYOUT_VALUES has no x column: d_x is ignored
     if (!d_pt || (has_x && !d_x) || !d_y || !d_z) return false;
     if ((has_x && !aligned16(d_x)) || !aligned16(d_y) || !aligned16(d_z) || !aligned4(d_pt) || (d_keys && !aligned4(d_keys)) ||
         (d_ct && !aligned4(d_ct)))
@@ -256,15 +255,15 @@ int encrypt_lone(aesw_ctx *ctx, const EncLaunch &L, hipStream_t s) {
     const uint32_t parts = (uint32_t)ctx->opt.split_small;
     const uint64_t per = ((L.n + parts - 1) / parts + 47) / 48 * 48;
     const uint32_t cnt = (uint32_t)((L.n + per - 1) / per);
-    const uint64_t sx = aesw_column_stride(L.layout, 0), sy = aesw_column_stride(L.layout, 1), sz = aesw_column_stride(L.layout, 2);
+    const SlabStrides st = slab_strides(L.layout);
     return fork_join(ctx, s, cnt, cnt, [&](uint32_t i, hipStream_t si) {
         const uint64_t lo = i * per;
         EncLaunch part = L;
         part.d_pt += lo * 16;
         part.n = L.n - lo < per ? L.n - lo : per;
-        if (L.d_x) part.d_x += lo * sx;
-        part.d_y += lo * sy;
-        part.d_z += lo * sz;
+        if (L.d_x) part.d_x += lo * st.x;
+        part.d_y += lo * st.y;
+        part.d_z += lo * st.z;
         if (L.d_ct) part.d_ct += lo * 16;
         return enqueue_encrypt(ctx, part, si);
     });
@@ -403,25 +402,15 @@ int aesw_uses_xtime_path(const aesw_ctx *ctx) {
 
 // ---- geometry ------------------------------------------------------------------
 
-uint32_t aesw_column_stride(int layout, int col) {
-    if (!valid_layout(layout) || col < 0 || col > 2) return 0;
-    if (layout == AESW_LAYOUT_DENSE) return AESW_AES_ROWS;
-    if (layout == AESW_LAYOUT_VALUES) return col == 0 ? Geo<VALUES>::XS : col == 1 ? Geo<VALUES>::YS : Geo<VALUES>::ZS;
-    return col == 0 ? Geo<PACKED>::XS : col == 1 ? Geo<PACKED>::YS : Geo<PACKED>::ZS;
-}
-
-uint32_t aesw_key_column_stride(int layout, int col) {
-    if (!valid_layout(layout) || col < 0 || col > 2) return 0;
-    if (layout == AESW_LAYOUT_DENSE) return AESW_KEY_ROWS;
-    return col == 0 ? Geo<PACKED>::KXS : col == 1 ? Geo<PACKED>::KYS : Geo<PACKED>::KZS;
-}
+// columns x, y, z and kx, ky, kz of slab_strides(layout), which is all zero for a layout that is none
+uint32_t aesw_column_stride(int layout, int col) { return col < 0 || col > 2 ? 0 : slab_strides(layout)[col]; }
+uint32_t aesw_key_column_stride(int layout, int col) { return col < 0 || col > 2 ? 0 : slab_strides(layout)[4 + col]; }
 
 int aesw_packed_index(int col, int32_t idx[AESW_AES_ROWS]) {
     if (col < 0 || col > 2 || !idx) return AESW_ERR_INVALID_ARG;
     uint8_t mask[AES_ROWS];
     encrypt_assigned_mask(col, mask);
-    int32_t n = 0;
-    for (int r = 0; r < AES_ROWS; ++r) idx[r] = mask[r] ? n++ : -1;
+    mask_to_index(mask, AES_ROWS, idx);
     return AESW_OK;
 }
 
@@ -434,8 +423,7 @@ int aesw_layout_index(int layout, int col, int32_t idx[AESW_AES_ROWS]) {
     if (layout == AESW_LAYOUT_PACKED) return aesw_packed_index(col, idx);
     uint8_t mask[AES_ROWS];
     encrypt_values_mask(col, mask);
-    int32_t n = 0;
-    for (int r = 0; r < AES_ROWS; ++r) idx[r] = mask[r] ? n++ : -1;
+    mask_to_index(mask, AES_ROWS, idx);
     return AESW_OK;
 }
 
@@ -443,8 +431,7 @@ int aesw_key_packed_index(int col, int32_t idx[AESW_KEY_ROWS]) {
     if (col < 0 || col > 2 || !idx) return AESW_ERR_INVALID_ARG;
     uint8_t mask[KEY_ROWS];
     key_assigned_mask(col, mask);
-    int32_t n = 0;
-    for (int r = 0; r < KEY_ROWS; ++r) idx[r] = mask[r] ? n++ : -1;
+    mask_to_index(mask, KEY_ROWS, idx);
     return AESW_OK;
 }
 

@@ -11,7 +11,6 @@
 #include "../../include/aesw.h"
 #include "aesw_ctx.h"
 #include "aesw_internal.h"
-#include "aesw_layout.h"
 
 using namespace aesw;
 
@@ -89,13 +88,13 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_columns_alloc");
     // with_key_slab 2: the key-schedule witness alone (aesw_key_schedule_witness_device): no encrypt columns
     const bool key_only = with_key_slab == 2;
-    const uint64_t sx = key_only ? 0 : aesw_column_stride(layout, 0), sy = key_only ? 0 : aesw_column_stride(layout, 1),
-                   sz = key_only ? 0 : aesw_column_stride(layout, 2);
+    const SlabStrides st = slab_strides(layout);
     const uint64_t align = ctx->opt.arena_align_log2 ? (uint64_t)1 << ctx->opt.arena_align_log2 : (uint64_t)2 << 20;
-    // sizes in the order the columns are laid out; a column of size 0 takes no room
-    const uint64_t size[8] = {n * sx, n * sy, n * sz, with_ct ? n * 16 : 0,
-                              with_key_slab ? n * WORDS_ROWS : 0, with_key_slab ? n * aesw_key_column_stride(layout, 0) : 0,
-                              with_key_slab ? n * aesw_key_column_stride(layout, 1) : 0, with_key_slab ? n * aesw_key_column_stride(layout, 2) : 0};
+    // sizes in the order the columns are laid out (x y z ct w kx ky kz); a column of size 0 takes no room
+    const int size_of7[7] = {0, 1, 2, 4, 5, 6, 7};  // column c of the seven (x y z w kx ky kz) -> index into size[] / off[]
+    uint64_t size[8];
+    size[3] = with_ct ? n * 16 : 0;
+    for (int c = 0; c < 7; ++c) size[size_of7[c]] = (c < 3 ? !key_only : with_key_slab != 0) ? n * st[c] : 0;
     uint64_t off[8], end = 0;
     for (int i = 0; i < 8; ++i) {
         end = (end + align - 1) / align * align;
@@ -150,9 +149,6 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     // runs fastest is kept (the search of a unit stops at the first candidate whose pattern runs as fast as its fill).  Candidates
     // that lose are HELD until the whole search is over (otherwise the driver hands the same memory out again), then released.
     using Range = aesw_ctx::ArenaRange;
-    const uint32_t strides7[7] = {(uint32_t)sx, (uint32_t)sy, (uint32_t)sz, WORDS_ROWS, aesw_key_column_stride(layout, 0),
-                                  aesw_key_column_stride(layout, 1), aesw_key_column_stride(layout, 2)};
-    const int size_of7[7] = {0, 1, 2, 4, 5, 6, 7};  // probe column c (x y z w kx ky kz) -> index into size[] / off[]
     const size_t MiB2 = (size_t)2 << 20;
     auto round2m = [&](uint64_t v) { return (size_t)((v + MiB2 - 1) / MiB2 * MiB2); };
     auto build = [&](int kind, size_t bytes, Range *r) -> int {
@@ -189,7 +185,7 @@ int aesw_columns_alloc(aesw_ctx *ctx, uint64_t n, int layout, int with_key_slab,
     HIP_TRY(ctx, hipEventCreate(&e1));
     HIP_TRY(ctx, hipEventCreate(&e2));
     ProbeParams pp = {};
-    for (int c = 0; c < 7; ++c) pp.stride[c] = strides7[c];
+    for (int c = 0; c < 7; ++c) pp.stride[c] = c < 3 && key_only ? 0 : st[c];
     pp.n = n;
     pp.xcd_mode = ctx->opt.xcd_remap;
     // two timed passes of a 2^20-block set; proportionally more for smaller batches (short launches time noisily)

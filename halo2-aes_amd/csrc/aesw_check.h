@@ -8,10 +8,10 @@
 // byte IMAGE -- block columns x | y | z, then key columns kx | ky | kz | words_column -- and every check is a table entry
 // holding 16-bit offsets into that image, built once per layout on the host (build_check_table):
 //   row entry   (2 words)  ox | oy << 16,  oz | tag << 16        tag = src/table.rs Tag of the lookup enabled on the row
-//   edge entry  (1 word)   dst | src << 16                        one copy_advice(): aesw_layout.h block_copy_graph / key_copy_graph
+//   edge entry  (1 word)   dst | src << 16                        one copy_advice(): aesw_slabmap.h block_copy_graph / key_copy_graph
 //   gate entry  (1 word)   ow | rcon << 16 | enabled << 24        q_eq_rcon * (words - fixed), src/key_schedule.rs:59-64
 #pragma once
-#include "aesw_layout.h"
+#include "aesw_slabmap.h"
 
 namespace aesw {
 
@@ -31,12 +31,14 @@ struct CheckGeo {
     uint32_t bi, ki;                     // block image bytes, key image bytes (kx | ky | kz | words)
 };
 
+// The checker reads DENSE and PACKED slabs; every layout other than DENSE counts as PACKED here (the values checker's key
+// image is check_geo(PACKED)'s).
 inline CheckGeo check_geo(int layout) {
+    const SlabStrides st = slab_strides(layout == DENSE ? DENSE : PACKED);
     CheckGeo g;
-    if (layout == DENSE) { g.sx = g.sy = g.sz = AES_ROWS; g.kxs = g.kys = g.kzs = KEY_ROWS; }
-    else { g.sx = Geo<PACKED>::XS; g.sy = Geo<PACKED>::YS; g.sz = Geo<PACKED>::ZS; g.kxs = Geo<PACKED>::KXS; g.kys = Geo<PACKED>::KYS; g.kzs = Geo<PACKED>::KZS; }
-    g.bi = g.sx + g.sy + g.sz;
-    g.ki = g.kxs + g.kys + g.kzs + WORDS_ROWS;
+    set_strides(g, st);
+    g.bi = st.block_bytes();
+    g.ki = st.key_bytes();
     return g;
 }
 

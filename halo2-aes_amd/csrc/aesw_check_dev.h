@@ -164,9 +164,9 @@ __device__ __forceinline__ uint32_t offsets_bad(const uint64_t *offsets, uint64_
 
 template <int LAYOUT>
 struct ChkLayout {
-    static constexpr int SX = AES_ROWS, SY = LAYOUT == DENSE ? AES_ROWS : Geo<PACKED>::YS, SZ = LAYOUT == DENSE ? AES_ROWS : Geo<PACKED>::ZS;
-    static constexpr int KXS = KEY_ROWS, KYS = LAYOUT == DENSE ? KEY_ROWS : Geo<PACKED>::KYS, KZS = LAYOUT == DENSE ? KEY_ROWS : Geo<PACKED>::KZS;
-    static constexpr int BI = SX + SY + SZ, O_KY = KXS, O_KZ = KXS + KYS, O_W = KXS + KYS + KZS, KI = O_W + WORDS_ROWS;
+    static constexpr SlabStrides ST = slab_strides(LAYOUT == DENSE ? DENSE : PACKED);  // check_geo's domain
+    static constexpr int SX = ST.x, SY = ST.y, SZ = ST.z, KXS = ST.kx, KYS = ST.ky, KZS = ST.kz;
+    static constexpr int BI = ST.block_bytes(), O_KY = KXS, O_KZ = KXS + KYS, O_W = KXS + KYS + KZS, KI = ST.key_bytes();
     static constexpr int IMG = (BI + KI + 15) / 16 * 16;
     static constexpr int KZV = KZS % 16 == 0 && (BI + O_KZ) % 16 == 0 ? 16 : 8, WV = (BI + O_W) % 16 == 0 ? 16 : 8;
     static_assert(SX % 16 == 0 && SY % 16 == 0 && SZ % 16 == 0 && KXS % 16 == 0 && KYS % 16 == 0 && BI % 16 == 0, "16-byte units");

@@ -32,8 +32,7 @@ int aesw_assemble_advice_circuits_device(aesw_ctx *ctx, uint32_t k, uint32_t n_s
     p.offsets = d_offsets;
     p.k = k;
     p.n_sets = n_sets;
-    p.sx = aesw_column_stride(layout, 0); p.sy = aesw_column_stride(layout, 1); p.sz = aesw_column_stride(layout, 2);
-    p.kxs = aesw_key_column_stride(layout, 0); p.kys = aesw_key_column_stride(layout, 1); p.kzs = aesw_key_column_stride(layout, 2);
+    aesw::set_strides(p, aesw::slab_strides(layout));
     p.packed = layout == AESW_LAYOUT_PACKED;
     HIP_TRY(ctx, aesw_circ::launch_assemble_circuits(p, n_circuits, as_fr != 0, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;

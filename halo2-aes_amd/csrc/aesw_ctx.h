@@ -19,7 +19,7 @@ struct aesw_ctx {
     int device = -1;
     uint8_t *d_tables = nullptr;  // 768 B
     uint8_t *d_fr_lut = nullptr;  // 256 x 32 B
-    uint32_t *d_ftab[3] = {nullptr, nullptr, nullptr};  // flush descriptors per layout (aesw_layout.h "scheduled flush")
+    uint32_t *d_ftab[3] = {nullptr, nullptr, nullptr};  // flush descriptors per layout (aesw_flush.h "scheduled flush")
     uint32_t *d_chktab[2] = {nullptr, nullptr};         // check tables of the DENSE / PACKED layout (aesw_check.h), uploaded by aesw_create
     KeyRing keys;  // the scheduled key: its round-key slots and their ordering (aesw_keyring.h)
     bool xt = false;

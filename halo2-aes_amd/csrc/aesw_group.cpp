@@ -17,11 +17,11 @@
 
 #include "../../include/aesw.h"
 #include "aesw_ctx.h"
+#include "aesw_slabmap.h"
 
 namespace {
 
 constexpr uint32_t MAX_MEMBERS = 64;
-constexpr size_t RK_BYTES = 176;  // round keys of one key (aesw_key_schedule_witness's rk)
 
 void shard_of(uint32_t members, uint64_t n, uint32_t i, uint64_t *first, uint64_t *count) {
     const unsigned __int128 lo = (unsigned __int128)n * i / members, hi = (unsigned __int128)n * (i + 1) / members;
@@ -134,8 +134,7 @@ int aesw_group_encrypt_witness(aesw_ctx *g, const uint8_t *pt, const uint8_t *ke
     if (!keys && (per_block_keys || kemit)) return AESW_ERR_INVALID_ARG;
     const uint32_t G = size_of(g);
     const bool pbk = per_block_keys != 0;
-    const size_t sx = aesw_column_stride(layout, 0), sy = aesw_column_stride(layout, 1), sz = aesw_column_stride(layout, 2);
-    const size_t kxs = aesw_key_column_stride(layout, 0), kys = aesw_key_column_stride(layout, 1), kzs = aesw_key_column_stride(layout, 2);
+    const aesw::SlabStrides st = aesw::slab_strides(layout);
     // a shared key's one slab is written by the first member that has blocks (member 0 whenever n >= G)
     uint32_t slab_member = 0;
     for (uint64_t b0, m; slab_member < G; ++slab_member) {
@@ -147,10 +146,10 @@ int aesw_group_encrypt_witness(aesw_ctx *g, const uint8_t *pt, const uint8_t *ke
         shard_of(G, n, i, &b0, &m);
         if (m == 0) return AESW_OK;
         aesw_key_slab own{nullptr, nullptr, nullptr, nullptr};
-        if (kemit && pbk) own = aesw_key_slab{at(ks->w, b0 * AESW_WORDS_ROWS), at(ks->kx, b0 * kxs), at(ks->ky, b0 * kys), at(ks->kz, b0 * kzs)};
+        if (kemit && pbk) own = aesw_key_slab{at(ks->w, b0 * st.words), at(ks->kx, b0 * st.kx), at(ks->ky, b0 * st.ky), at(ks->kz, b0 * st.kz)};
         else if (kemit && i == slab_member) own = *ks;
-        return aesw_encrypt_witness(g->members[i], pt + 16 * b0, pbk ? keys + 16 * b0 : keys, per_block_keys, m, layout, at(x, b0 * sx),
-                                    at(y, b0 * sy), at(z, b0 * sz), at(ct, 16 * b0), &own);
+        return aesw_encrypt_witness(g->members[i], pt + 16 * b0, pbk ? keys + 16 * b0 : keys, per_block_keys, m, layout, at(x, b0 * st.x),
+                                    at(y, b0 * st.y), at(z, b0 * st.z), at(ct, 16 * b0), &own);
     });
 }
 
@@ -247,13 +246,13 @@ int aesw_group_key_schedule_witness(aesw_ctx *g, const uint8_t *keys, uint64_t n
     if (n == 0) return AESW_OK;
     if (!keys) return AESW_ERR_INVALID_ARG;
     const uint32_t G = size_of(g);
-    const size_t kxs = aesw_key_column_stride(layout, 0), kys = aesw_key_column_stride(layout, 1), kzs = aesw_key_column_stride(layout, 2);
+    const aesw::SlabStrides st = aesw::slab_strides(layout);
     return run_members(g, [&](uint32_t i) -> int {
         uint64_t k0, m;
         shard_of(G, n, i, &k0, &m);
         if (m == 0) return AESW_OK;
-        return aesw_key_schedule_witness(g->members[i], keys + 16 * k0, m, layout, at(w, k0 * AESW_WORDS_ROWS), at(kx, k0 * kxs), at(ky, k0 * kys),
-                                         at(kz, k0 * kzs), at(rk, k0 * RK_BYTES));
+        return aesw_key_schedule_witness(g->members[i], keys + 16 * k0, m, layout, at(w, k0 * st.words), at(kx, k0 * st.kx), at(ky, k0 * st.ky),
+                                         at(kz, k0 * st.kz), at(rk, k0 * aesw::RK_BYTES));
     });
 }
 
@@ -266,8 +265,7 @@ int aesw_group_check_witness(aesw_ctx *g, const uint8_t *pt, const uint8_t *keys
     if (n == 0) return AESW_OK;
     const uint32_t G = size_of(g);
     const bool pbk = per_block_keys != 0;
-    const size_t sx = aesw_column_stride(layout, 0), sy = aesw_column_stride(layout, 1), sz = aesw_column_stride(layout, 2);
-    const size_t kxs = aesw_key_column_stride(layout, 0), kys = aesw_key_column_stride(layout, 1), kzs = aesw_key_column_stride(layout, 2);
+    const aesw::SlabStrides st = aesw::slab_strides(layout);
     std::vector<aesw_check_report> reps(G, aesw_check_report{0, 0, 0, 0, 0, 0, AESW_CHECK_NONE});
     std::vector<uint64_t> first(G), count(G);
     for (uint32_t i = 0; i < G; ++i) shard_of(G, n, i, &first[i], &count[i]);
@@ -275,9 +273,9 @@ int aesw_group_check_witness(aesw_ctx *g, const uint8_t *pt, const uint8_t *keys
         const uint64_t b0 = first[i], m = count[i];
         if (m == 0) return AESW_OK;
         // per-block keys: the member's own key slabs; a shared key: its one slab goes to every member
-        const aesw_key_slab own = pbk ? aesw_key_slab{ks->w + b0 * AESW_WORDS_ROWS, ks->kx + b0 * kxs, ks->ky + b0 * kys, ks->kz + b0 * kzs} : *ks;
-        return aesw_check_witness(g->members[i], pt + 16 * b0, pbk ? keys + 16 * b0 : keys, per_block_keys, m, layout, x + b0 * sx, y + b0 * sy,
-                                  z + b0 * sz, at(ct, 16 * b0), &own, &reps[i]);
+        const aesw_key_slab own = pbk ? aesw_key_slab{ks->w + b0 * st.words, ks->kx + b0 * st.kx, ks->ky + b0 * st.ky, ks->kz + b0 * st.kz} : *ks;
+        return aesw_check_witness(g->members[i], pt + 16 * b0, pbk ? keys + 16 * b0 : keys, per_block_keys, m, layout, x + b0 * st.x, y + b0 * st.y,
+                                  z + b0 * st.z, at(ct, 16 * b0), &own, &reps[i]);
     });
     if (rc != AESW_OK) return rc;
     for (uint32_t i = 0; i < G; ++i)

@@ -12,7 +12,6 @@
 
 #include "../../include/aesw.h"
 #include "aesw_internal.h"
-#include "aesw_layout.h"
 #include "aesw_check.h"
 
 using namespace aesw;
@@ -255,9 +254,10 @@ int run_consume(Pipeline &pl, uint64_t n, uint64_t chunk, size_t bytes_per_item,
 int copy_key_slab(aesw_ctx *ctx, const aesw_key_slab &host, uint64_t first, const aesw_key_slab &dev, uint64_t nk, int layout,
                   hipMemcpyKind kind, const hipStream_t *s) {
     uint8_t *const h[4] = {host.w, host.kx, host.ky, host.kz}, *const d[4] = {dev.w, dev.kx, dev.ky, dev.kz};
+    const SlabStrides st = slab_strides(layout);
     for (int c = 0; c < 4; ++c) {
         if (!h[c]) continue;
-        const size_t stride = c ? aesw_key_column_stride(layout, c - 1) : WORDS_ROWS;
+        const size_t stride = st[3 + c];  // w kx ky kz are columns 3..6 of the seven
         uint8_t *hp = h[c] + first * stride;
         void *dst = kind == hipMemcpyDeviceToHost ? hp : d[c];
         const void *src = kind == hipMemcpyDeviceToHost ? d[c] : hp;
@@ -306,8 +306,8 @@ int aesw_encrypt_witness(aesw_ctx *ctx, const uint8_t *pt, const uint8_t *keys, 
     Carve dev, host;
     const size_t o_pt = dev.take(n * 16), o_keys = dev.take(pbk ? n * 16 : 16), o_ct = dev.take(ct ? n * 16 : 0);
     const size_t kn = kemit ? (pbk ? chunk : 1) : 0;  // per-block keys: a key slab per block; shared key: one
-    for (int c = 0; c < 7; ++c)
-        cols[c].stride = c < 3 ? aesw_column_stride(layout, c) : c == 3 ? (size_t)WORDS_ROWS : aesw_key_column_stride(layout, c - 4);
+    const SlabStrides st = slab_strides(layout);
+    for (int c = 0; c < 7; ++c) cols[c].stride = st[c];
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 7; ++c) cols[c].doff[s] = dev.take((c < 3 ? chunk : kn) * cols[c].stride);
     for (int c = 0; c < 7; ++c) {
@@ -367,7 +367,7 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     int rc = ensure_streams(ctx);
     if (rc != AESW_OK) return rc;
-    const size_t strides[3] = {aesw_column_stride(layout, 0), aesw_column_stride(layout, 1), aesw_column_stride(layout, 2)};
+    const SlabStrides st = slab_strides(layout);
     const bool pbk = per_block_keys != 0;
     const uint64_t chunk = stage_blocks(ctx, n);
     // device scratch: inputs + two sets of columns; page-locked bounce: two sets of columns
@@ -375,8 +375,8 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
     size_t col_off[2][3], boff[3];
     const size_t o_pt = dev.take(n * 16), o_keys = dev.take(pbk ? n * 16 : 16);
     for (int s = 0; s < 2; ++s)
-        for (int c = 0; c < 3; ++c) col_off[s][c] = dev.take(chunk * strides[c]);
-    for (int c = 0; c < 3; ++c) boff[c] = host.take(chunk * strides[c]);
+        for (int c = 0; c < 3; ++c) col_off[s][c] = dev.take(chunk * st[c]);
+    for (int c = 0; c < 3; ++c) boff[c] = host.take(chunk * st[c]);
     // "stream_check": every chunk is checked on the device behind its kernel (aesw_check.h).  Needs the key slab(s) the blocks' AddRoundKey
     // rows copy from -- one for a shared / scheduled key (made once, below), one per block with per-block keys (emitted by the chunk's
     // own launch into two more scratch sets) -- and one report per chunk, summed after the last one.
@@ -386,8 +386,7 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
     if (checking) {
         const uint64_t nk = pbk ? chunk : 1;
         for (int s = 0; s < (pbk ? 2 : 1); ++s) {
-            ks_off[s][0] = dev.take(nk * WORDS_ROWS);
-            for (int c = 0; c < 3; ++c) ks_off[s][1 + c] = dev.take(nk * aesw_key_column_stride(layout, c));
+            for (int c = 0; c < 4; ++c) ks_off[s][c] = dev.take(nk * st[3 + c]);  // w kx ky kz
         }
         if (!pbk) for (int c = 0; c < 4; ++c) ks_off[1][c] = ks_off[0][c];
         o_rep = dev.take(n_chunks * sizeof(aesw_check_report));
@@ -424,8 +423,8 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
             // diagnostic: two cells of one block are overwritten between the kernel and the check (tests/test_gpu_round4.py shows the
             // stream check names that block, by its batch-wide index, in whatever chunk it lies)
             const uint64_t pb = (uint64_t)ctx->opt.stream_poison - 1 - b0;
-            HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][1] + pb * strides[1] + 5, 0x5A, 1, ctx->s_compute));
-            HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][2] + pb * strides[2] + 7, 0xA5, 1, ctx->s_compute));
+            HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][1] + pb * st[1] + 5, 0x5A, 1, ctx->s_compute));
+            HIP_TRY(ctx, hipMemsetAsync(d + col_off[s][2] + pb * st[2] + 7, 0xA5, 1, ctx->s_compute));
         }
         if (!checking) return AESW_OK;
         r = check_witness_impl(ctx, d + o_pt + 16 * b0, pbk ? d + o_keys + 16 * b0 : d_key16, per_block_keys, m, layout, d + col_off[s][0],
@@ -436,13 +435,13 @@ int aesw_encrypt_witness_stream(aesw_ctx *ctx, const uint8_t *pt, const uint8_t 
     };
     auto copies = [&](int s, uint64_t, uint64_t m, std::vector<CopyJob> &d2h, std::vector<CopyJob> &) {
         for (int c = 0; c < 3; ++c)
-            if (strides[c]) d2h.push_back(CopyJob{ctx->bounce[s] + boff[c], d + col_off[s][c], (size_t)(m * strides[c])});
+            if (st[c]) d2h.push_back(CopyJob{ctx->bounce[s] + boff[c], d + col_off[s][c], (size_t)(m * st[c])});
     };
     auto hand_over = [&](int s, uint64_t first, uint64_t count) {
-        return consume(user, first, count, strides[0] ? ctx->bounce[s] + boff[0] : nullptr /* AESW_LAYOUT_VALUES: no x */,
+        return consume(user, first, count, st[0] ? ctx->bounce[s] + boff[0] : nullptr /* AESW_LAYOUT_VALUES: no x */,
                        ctx->bounce[s] + boff[1], ctx->bounce[s] + boff[2]);
     };
-    rc = run_consume(pl, n, chunk, strides[0] + strides[1] + strides[2], launch, copies, hand_over);
+    rc = run_consume(pl, n, chunk, st.block_bytes(), launch, copies, hand_over);
     if (rc != AESW_OK) return rc;
     if (checking) {  // every chunk's kernel and check have finished (their columns have been copied): sum the reports
         std::vector<aesw_check_report> reps((size_t)n_chunks);
@@ -554,10 +553,11 @@ int aesw_key_schedule_witness(aesw_ctx *ctx, const uint8_t *keys, uint64_t n, in
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     DevBuf dk, dw, dkx, dky, dkz, drk;
     HIP_TRY(ctx, dk.alloc(n * 16));
-    if (w) HIP_TRY(ctx, dw.alloc(n * WORDS_ROWS));
-    if (kx) HIP_TRY(ctx, dkx.alloc(n * aesw_key_column_stride(layout, 0)));
-    if (ky) HIP_TRY(ctx, dky.alloc(n * aesw_key_column_stride(layout, 1)));
-    if (kz) HIP_TRY(ctx, dkz.alloc(n * aesw_key_column_stride(layout, 2)));
+    const SlabStrides st = slab_strides(layout);
+    if (w) HIP_TRY(ctx, dw.alloc(n * st.words));
+    if (kx) HIP_TRY(ctx, dkx.alloc(n * st.kx));
+    if (ky) HIP_TRY(ctx, dky.alloc(n * st.ky));
+    if (kz) HIP_TRY(ctx, dkz.alloc(n * st.kz));
     if (rk) HIP_TRY(ctx, drk.alloc(n * RK_BYTES));
     HIP_TRY(ctx, hipMemcpy(dk.p, keys, n * 16, hipMemcpyHostToDevice));
     int rc = aesw_key_schedule_witness_device(ctx, dk.p, n, layout, dw.p, dkx.p, dky.p, dkz.p, drk.p, nullptr);  // (not allocated = null = not wanted)
@@ -626,10 +626,11 @@ int aesw_schedule_key(aesw_ctx *ctx, const uint8_t key[16], int layout, const ae
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     DevBuf dk, dw, dkx, dky, dkz;
     HIP_TRY(ctx, dk.alloc(16));
-    HIP_TRY(ctx, dw.alloc(WORDS_ROWS));
-    HIP_TRY(ctx, dkx.alloc(aesw_key_column_stride(layout, 0)));
-    HIP_TRY(ctx, dky.alloc(aesw_key_column_stride(layout, 1)));
-    HIP_TRY(ctx, dkz.alloc(aesw_key_column_stride(layout, 2)));
+    const SlabStrides st = slab_strides(layout);
+    HIP_TRY(ctx, dw.alloc(st.words));
+    HIP_TRY(ctx, dkx.alloc(st.kx));
+    HIP_TRY(ctx, dky.alloc(st.ky));
+    HIP_TRY(ctx, dkz.alloc(st.kz));
     HIP_TRY(ctx, hipMemcpy(dk.p, key, 16, hipMemcpyHostToDevice));
     aesw_key_slab dks{dw.p, dkx.p, dky.p, dkz.p};
     int rc = aesw_schedule_key_device(ctx, dk.p, layout, ks ? &dks : nullptr, nullptr);

@@ -46,7 +46,7 @@ struct KeyParams {
 // key mode: 0 = per-block keys, 1 = shared key expanded in the kernel, 2 = shared key scheduled earlier (p.rk)
 hipError_t launch_encrypt(const EncParams &p, int layout, bool xt, int keymode, bool kemit, int waves, int store_mode,
                           uint32_t max_groups_in_flight, uint32_t xcd_remap, uint32_t lds_pad, hipStream_t s);
-// flush-descriptor table of a layout (aesw_layout.h "scheduled flush"): size in 32-bit words, and the host-side builder
+// flush-descriptor table of a layout (aesw_flush.h "scheduled flush"): size in 32-bit words, and the host-side builder
 int flush_table_words(int layout);
 void build_flush_tables(int layout, uint32_t *out);
 // hipFuncSetAttribute(max dynamic LDS) for every instantiation, once per device: called by aesw_create()

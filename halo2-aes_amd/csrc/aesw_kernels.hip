@@ -14,7 +14,7 @@
 // output columns that just became complete leave as whole lines, 8 lanes x 16 B
 // per line, 8 lines per store instruction, following a fixed schedule whose
 // per-lane descriptors (LDS address | global offset) sit in registers
-// (aesw_layout.h "scheduled flush").  Partial-line stores are what caps a
+// (aesw_flush.h "scheduled flush").  Partial-line stores are what caps a
 // naive per-round flush at ~3 TB/s; whole lines reach ~5.5 TB/s (tools/storebench).
 // The S-box / mul2 / mul3 tables live in LDS (768 B); when the host's mul
 // tables equal GF(2^8) xtime the packed arithmetic path replaces 8 of the 12
@@ -162,7 +162,7 @@ __device__ __forceinline__ uint8_t *uniform_ptr(uint8_t *p) {
     return reinterpret_cast<uint8_t *>(((uint64_t)hi << 32) | lo);
 }
 
-// Scheduled whole-line flush (aesw_layout.h "scheduled flush").  A lane holds one descriptor word per store
+// Scheduled whole-line flush (aesw_flush.h "scheduled flush").  A lane holds one descriptor word per store
 // instruction of its column (loaded once per workgroup from the host-built table, stage base added):
 //   bits 0..15  LDS address of the lane's 16-byte piece      bits 16..30  byte offset in the wave's global range
 // Round R issues all its ds_read_b128 first (their LDS round trips overlap), then the stores: 8 whole lines per

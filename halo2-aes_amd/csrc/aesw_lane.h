@@ -14,7 +14,7 @@
 //   mix<COL>(off, k, v): dword k of this lane's lcon() record group
 // which is LDS on the device and the output arrays in the host model.
 #pragma once
-#include "aesw_layout.h"
+#include "aesw_flush.h"  // the windows (aesw_layout.h) and their flush: whoever runs the lane code stores through both
 
 namespace aesw {
 

@@ -6,7 +6,7 @@
 // g++ and holds it against the reference's rule, restated there a second time, and against the oracle's circuit.
 #pragma once
 #include "../../include/aesw.h"
-#include "aesw_layout.h"
+#include "aesw_slabmap.h"
 
 namespace aesw {
 

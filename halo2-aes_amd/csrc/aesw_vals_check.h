@@ -18,14 +18,16 @@
 // witness has no copy checks and no plaintext literal check; key slabs are walked by aesw_check.h's check_key as they are.
 #pragma once
 #include "aesw_check.h"
+#include "aesw_layout.h"  // Geo<VALUES>: the kernel and the CPU model stage a block's y and z by its byte counts
 
 namespace aesw {
 
 constexpr int VALS_ROWS = 1056;                                              // checked rows of a block = VALUES cells of a block
-constexpr int VALS_O_Z = Geo<VALUES>::YS, VALS_O_PT = VALS_O_Z + Geo<VALUES>::ZS;  // image offsets of z and of the plaintext
+constexpr SlabStrides VALS_ST = slab_strides(VALUES);                        // y, z of a block; the PACKED key slab
+constexpr int VALS_O_Z = VALS_ST.y, VALS_O_PT = VALS_O_Z + VALS_ST.z;        // image offsets of z and of the plaintext
 constexpr int VALS_BI = VALS_O_PT + 16;                                      // block image bytes: 1 072
-constexpr int VALS_KI = Geo<PACKED>::KXS + Geo<PACKED>::KYS + Geo<PACKED>::KZS + WORDS_ROWS;  // key image bytes: 936
-static_assert(VALS_ROWS == Geo<VALUES>::YS + Geo<VALUES>::ZS, "every VALUES cell is the output of one checked row");
+constexpr int VALS_KI = VALS_ST.key_bytes();                                 // key image bytes: 936
+static_assert(VALS_ROWS == VALS_ST.block_bytes(), "every VALUES cell is the output of one checked row");
 
 // The device form of the table keeps aesw_check.h's word positions, so that check_key and the fast path's key walk read it
 // unchanged: the 1 056 row entries at CHK_ROWS, their slab rows behind them (two per word), nothing at CHK_EDGES, and the key
@@ -41,10 +43,8 @@ inline int build_values_check_table(uint32_t *words, uint16_t *rows) {
     encrypt_values_mask(1, my);
     encrypt_values_mask(2, mz);
     encrypt_selector_tags(etag);
-    for (int r = 0, ny = 0, nz = 0; r < AES_ROWS; ++r) {
-        iy[r] = my[r] ? ny++ : -1;
-        iz[r] = mz[r] ? nz++ : -1;
-    }
+    mask_to_index(my, AES_ROWS, iy);
+    mask_to_index(mz, AES_ROWS, iz);
     CopyEdge be[BLOCK_COPIES];
     block_copy_graph(be);
     int from[2][AES_ROWS];  // the edge that writes x / y of a slab row, -1: none
@@ -53,7 +53,7 @@ inline int build_values_check_table(uint32_t *words, uint16_t *rows) {
         if (be[i].dst_space != 0 || be[i].dst_col > 1) return -1;
         from[be[i].dst_col][be[i].dst_row] = i;
     }
-    const uint32_t kz0 = VALS_BI + Geo<PACKED>::KXS + Geo<PACKED>::KYS, w0 = kz0 + Geo<PACKED>::KZS;
+    const uint32_t kz0 = VALS_BI + VALS_ST.kx + VALS_ST.ky, w0 = kz0 + VALS_ST.kz;
     auto root = [&](uint8_t col, uint16_t row) -> uint32_t {
         CellRef c{0, col, row};
         for (int hops = 0; c.space == 0 && c.col < 2 && from[c.col][c.row] >= 0 && hops < BLOCK_COPIES; ++hops) {

@@ -138,7 +138,8 @@ int aesw_circ_check_witness_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, u
     p.c.report = reinterpret_cast<uint64_t *>(d_report);
     p.c.n = n;
     p.c.per_block_keys = 1;
-    p.c.sx = cg.sx; p.c.sy = cg.sy; p.c.sz = cg.sz; p.c.kxs = cg.kxs; p.c.kys = cg.kys; p.c.kzs = cg.kzs; p.c.bi = cg.bi;
+    aesw::set_strides(p.c, aesw::slab_strides(layout));  // DENSE or PACKED (checked above): check_geo's domain
+    p.c.bi = cg.bi;
     p.c.img = (cg.bi + cg.ki + 15u) & ~15u;
     p.offsets = d_offsets;
     p.cap = aesw_block_capacity(k, n_sets);

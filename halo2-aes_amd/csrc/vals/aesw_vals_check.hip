@@ -170,8 +170,7 @@ int aesw_vals_check_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_
     p.report = reinterpret_cast<uint64_t *>(d_report);
     p.n = n;
     p.per_block_keys = per_block_keys ? 1u : 0u;
-    p.sy = aesw::Geo<aesw::VALUES>::YS; p.sz = aesw::Geo<aesw::VALUES>::ZS;
-    p.kxs = aesw::Geo<aesw::PACKED>::KXS; p.kys = aesw::Geo<aesw::PACKED>::KYS; p.kzs = aesw::Geo<aesw::PACKED>::KZS;
+    aesw::set_strides(p, aesw::VALS_ST);  // no x; the PACKED key slab
     p.bi = aesw_vals::BI; p.img = aesw_vals::IMG;
     HIP_TRY(ctx, aesw_vals::launch_vals_check(p, reinterpret_cast<hipStream_t>(stream)));
     return AESW_OK;

@@ -1,6 +1,6 @@
 // lane_model.cpp -- CPU execution of the device program's shared source:
 // the per-lane code (halo2-aes_amd/csrc/aesw_lane.h), the staging windows and
-// the scheduled whole-line flush (aesw_layout.h: descriptor table), wave by wave (16 blocks),
+// the scheduled whole-line flush (aesw_flush.h: descriptor table), wave by wave (16 blocks),
 // with the cross-lane steps (DPP quad permutes) and LDS replaced by arrays.
 // TEST INFRASTRUCTURE: lets `-m "not gpu"` tests compare the device program
 // with the oracle before any GPU run.  Not reachable from the product library.

@@ -1,5 +1,5 @@
 """The device program's shared source (aesw_lane.h + the staging windows and
-whole-line flush math of aesw_layout.h) run on the CPU, against the oracle.
+whole-line flush math of aesw_flush.h) run on the CPU, against the oracle.
 This is host logic: it catches wrong v_perm selectors, slab offsets, window
 slots and flush indices without a GPU."""
 import ctypes as C
