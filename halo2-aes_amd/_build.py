@@ -3,10 +3,11 @@
   halo2-aes_amd/libaesw.so        HIP kernels + the C ABI of include/aesw.h (hipcc --offload-arch=gfx950)
   halo2-aes_amd/libaesw_host.so   the C++ mirror of the reference's host interface (include/aesw_host.h): plain g++,
                                   no device code, linked against libaesw.so -- it only calls the C ABI
-  halo2-aes_amd/libaesw_<name>.so one checker library per entry of SATELLITES (circ: many circuits, include/aesw_circ.h;
+  halo2-aes_amd/libaesw_<name>.so one library per entry of SATELLITES (the checkers -- circ: many circuits, include/aesw_circ.h;
                                   cols: the assembled advice columns, include/aesw_cols.h; vals: a VALUES witness,
-                                  include/aesw_vals.h): its own gfx950 kernels and entry point (hipcc), linked against
-                                  libaesw.so, whose context it takes.  All are built by build_satellite() alike.
+                                  include/aesw_vals.h -- and mult: the lookup multiplicities, include/aesw_mult.h): its
+                                  own gfx950 kernels and entry point (hipcc), linked against libaesw.so, whose context it
+                                  takes.  All are built by build_satellite() alike.
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -108,8 +109,9 @@ SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),
     "vals": ([CSRC / "vals" / "aesw_vals_check.hip"], [CSRC / "aesw_vals_check.h"], INCLUDE / "aesw_vals.h"),
+    "mult": ([CSRC / "mult" / "aesw_mult.hip"], [CSRC / "aesw_mult.h"], INCLUDE / "aesw_mult.h"),
 }
-CIRC_LIB, COLS_LIB, VALS_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
+CIRC_LIB, COLS_LIB, VALS_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
 
 
 def build_satellite(name: str, force: bool = False) -> Path:

@@ -21,6 +21,7 @@ LIB_PATH = _PKG / "libaesw.so"            # HIP kernels + the C ABI of include/a
 HOST_LIB_PATH = _PKG / "libaesw_host.so"  # C++ mirror of the reference's host interface (include/aesw_host.h), above the C ABI
 COLS_LIB_PATH = _PKG / "libaesw_cols.so"  # the checker of the assembled advice columns (include/aesw_cols.h), next to libaesw.so
 VALS_LIB_PATH = _PKG / "libaesw_vals.so"  # the checker of a VALUES witness (include/aesw_vals.h), next to libaesw.so
+MULT_LIB_PATH = _PKG / "libaesw_mult.so"  # the lookup multiplicities of a many-circuit batch (include/aesw_mult.h), next to libaesw.so
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -72,6 +73,11 @@ class CheckReport(C.Structure):
 class CircCheckReport(C.Structure):
     """aesw_circ_check_report: what aesw_circ_check_witness_device found."""
     _fields_ = CheckReport._fields_ + [("offset_failures", C.c_uint64)]
+
+
+class MultReport(C.Structure):
+    """aesw_mult_report: what aesw_mult_count_device saw next to the histograms."""
+    _fields_ = [("lookups", C.c_uint64), ("misses", C.c_uint64), ("first_miss", C.c_uint64)]
 
 
 class _DevView:
@@ -191,6 +197,16 @@ VALS_SYMBOLS = {
     "aesw_vals_image_bytes": (_U32, []),
 }
 
+# include/aesw_mult.h
+_MULT_ARGS = [_P, _U32, _U32, _U32, _P, _I, _P, _P, _P, C.POINTER(KeySlab), _P, _P, _P]
+MULT_SYMBOLS = {
+    "aesw_mult_count_device": (_I, _MULT_ARGS),
+    "aesw_mult_count_device_form": (_I, _MULT_ARGS + [_I]),
+    "aesw_mult_default_form": (_I, [_U32, _U32, _U32]),
+    "aesw_mult_bin": (_U32, [_U32, _U32, _U32]),
+}
+MULT_FORM_AUTO, MULT_FORM_DIRECT, MULT_FORM_PRIVATE = 0, 1, 2
+
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 _NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
 # the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT)
@@ -200,6 +216,7 @@ _LIBRARIES = {
     "circ": (CIRC_LIB_PATH, CIRC_SYMBOLS, _NO_FALLBACK),
     "cols": (COLS_LIB_PATH, COLS_SYMBOLS, _NO_FALLBACK),
     "vals": (VALS_LIB_PATH, VALS_SYMBOLS, _NO_FALLBACK),
+    "mult": (MULT_LIB_PATH, MULT_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -260,6 +277,17 @@ def load_vals_library(path: Path | None = None) -> C.CDLL:
     return _load("vals", path)
 
 
+def load_mult_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_mult.so (in-tree): the lookup multiplicities behind Context.lookup_multiplicities."""
+    return _load("mult", path)
+
+
+def mult_bin(tag: int, x: int, y: int = 0):
+    """aesw_mult_bin: the table row the input operands of a lookup name (None for tag 0 and for anything that is no tag)."""
+    b = int(load_mult_library().aesw_mult_bin(tag, x, y))
+    return None if b == 0xFFFFFFFF else b
+
+
 def vals_check_table():
     """aesw_vals_check_table: (words uint32[1056, 2], rows uint16[1056]) -- the resolved lookups of a VALUES block; the image
     order and the offset encoding are in include/aesw_vals.h."""
@@ -311,6 +339,15 @@ def cols_report_dict(rep) -> dict:
     out.update(cell_failures=v[8], unassigned_failures=v[9], first_cell=None if v[10] == _NONE else v[10], cells=v[11],
                satisfied=out["satisfied"] and v[8] == 0 and v[9] == 0)
     return out
+
+
+def mult_report_dict(rep) -> dict:
+    """The uint64[3] report tensor of Context.lookup_multiplicities(sync=False), read back, as the dict sync=True returns:
+    lookups, misses and first_miss = None or (unit, is_key_slab, row) -- the unit is the batch-wide block index, or the circuit
+    for a key slab."""
+    v = _words(rep)
+    first = None if v[2] == _NONE else (v[2] >> 20, bool((v[2] >> 19) & 1), v[2] & 0xFFFF)
+    return {"lookups": v[0], "misses": v[1], "first_miss": first}
 
 
 def _ptr(x):
@@ -932,6 +969,35 @@ class Context:
         self._check(rc, "aesw_circ_check_witness_device")
         return self._report(rep, sync, circ_report_dict)
 
+    def lookup_multiplicities(self, k: int, n_sets: int, witness: Witness, key_witness: KeyWitness | None, counts,
+                              layout: int = K.LAYOUT_PACKED, sync: bool = True, _offsets=None, _form: int = MULT_FORM_AUTO, _out=None):
+        """How often every row of the lookup table is looked up, per circuit and column set (aesw_mult_count_device,
+        libaesw_mult.so): (mult, report) with mult an int32 [C, n_sets, 66561] tensor in the row order of lookup_table() --
+        histogram (c, s) counts the blocks of set s of circuit c, (c, 0) also the rows of key slab c of `key_witness` (None: no
+        key lookups) -- and report the dict of mult_report_dict after synchronising the stream, or with sync=False the uint64[3]
+        device tensor.  The all-zero row stays 0: for the argument (set s, tag t) its multiplicity is 2^k minus the sum of section
+        t of histogram (c, s).  counts / _offsets as for check_circuits; _form forces one of the two forms (MULT_FORM_*) and
+        _out is an int32 [C, n_sets, 66561] tensor to count into (tests, tools)."""
+        lib = load_mult_library()
+        torch = self._torch()
+        n = sum(int(c) for c in counts)
+        for i, t in enumerate(witness[:3]):
+            if int(self._u8(t, "witness").numel()) < n * column_stride(layout, i):
+                raise ValueError("witness holds fewer blocks than the counts sum to")
+        nc, d_offs = self._circuit_args(k, n_sets, n, counts, None, _offsets)
+        ks = self._key_slabs(key_witness, nc) if key_witness is not None else None
+        shape = (nc, n_sets, K.TABLE_ROWS)
+        if _out is None:
+            _out = torch.empty(shape, dtype=torch.int32, device=self._dev())
+        elif tuple(_out.shape) != shape or _out.dtype != torch.int32 or not _out.is_contiguous():
+            raise ValueError("_out must be a contiguous int32 tensor of shape %r" % (shape,))
+        rep = torch.empty(3, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_mult_count_device_form(
+            self._h, k, n_sets, nc, d_offs.data_ptr(), layout, witness.x.data_ptr(), witness.y.data_ptr(), witness.z.data_ptr(),
+            _ptr(ks), _out.data_ptr(), rep.data_ptr(), self._stream(), _form)
+        self._check(rc, "aesw_mult_count_device")
+        return _out, self._report(rep, sync, mult_report_dict)
+
     def check_columns(self, k: int, n_sets: int, pt, keys, advice, counts, ct=None, sync: bool = True, _offsets=None):
         """MockProver::assert_satisfied over the ASSEMBLED advice columns of C FixedAes128Config<k, n_sets> circuits in one launch
         (aesw_cols_check_device, libaesw_cols.so).  advice: what assemble_advice_circuits returns, [C, 3*n_sets+1, 2^k] bytes or
@@ -1172,7 +1238,8 @@ class Group(Context):
 # the device-tensor methods of Context (the C ABI refuses them on a group as well)
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
-              "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values"):
+              "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values",
+              "lookup_multiplicities"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
