@@ -5,7 +5,8 @@
                                   no device code, linked against libaesw.so -- it only calls the C ABI
   halo2-aes_amd/libaesw_<name>.so one library per entry of SATELLITES (the checkers -- circ: many circuits, include/aesw_circ.h;
                                   cols: the assembled advice columns, include/aesw_cols.h; vals: a VALUES witness,
-                                  include/aesw_vals.h -- and mult: the lookup multiplicities, include/aesw_mult.h): its
+                                  include/aesw_vals.h --, mult: the lookup multiplicities, include/aesw_mult.h, and acc: the same
+                                  accumulated chunk by chunk, include/aesw_acc.h): its
                                   own gfx950 kernels and entry point (hipcc), linked against libaesw.so, whose context it
                                   takes.  All are built by build_satellite() alike.
 
@@ -102,16 +103,18 @@ def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_so
 
 # The checker libraries next to libaesw.so.  csrc/ itself holds exactly the sources of libaesw.so (PRODUCT_SOURCES); a
 # satellite's live one level down, in csrc/<name>/.  Each entry: its sources, the headers it depends on beyond
-# SATELLITE_HEADERS, its public header.
+# SATELLITE_HEADERS, its public header.  (The order is no build order -- each depends on libaesw.so alone -- but "mult" stays
+# the last entry: tests/test_mult_library.py holds it there.)
 SATELLITE_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_check.h", "aesw_layout.h", "aesw_slabmap.h", "aesw_internal.h", "aesw_ctx.h",
                                         "aesw_keyring.h", "aesw_options.h", "aesw_placement.h")] + [INCLUDE / "aesw.h"]
 SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),
     "vals": ([CSRC / "vals" / "aesw_vals_check.hip"], [CSRC / "aesw_vals_check.h"], INCLUDE / "aesw_vals.h"),
+    "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
     "mult": ([CSRC / "mult" / "aesw_mult.hip"], [CSRC / "aesw_mult.h"], INCLUDE / "aesw_mult.h"),
 }
-CIRC_LIB, COLS_LIB, VALS_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
+CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
 
 
 def build_satellite(name: str, force: bool = False) -> Path:

@@ -22,6 +22,7 @@ HOST_LIB_PATH = _PKG / "libaesw_host.so"  # C++ mirror of the reference's host i
 COLS_LIB_PATH = _PKG / "libaesw_cols.so"  # the checker of the assembled advice columns (include/aesw_cols.h), next to libaesw.so
 VALS_LIB_PATH = _PKG / "libaesw_vals.so"  # the checker of a VALUES witness (include/aesw_vals.h), next to libaesw.so
 MULT_LIB_PATH = _PKG / "libaesw_mult.so"  # the lookup multiplicities of a many-circuit batch (include/aesw_mult.h), next to libaesw.so
+ACC_LIB_PATH = _PKG / "libaesw_acc.so"    # the lookup multiplicities of one circuit, accumulated chunk by chunk (include/aesw_acc.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -207,6 +208,16 @@ MULT_SYMBOLS = {
 }
 MULT_FORM_AUTO, MULT_FORM_DIRECT, MULT_FORM_PRIVATE = 0, 1, 2
 
+# include/aesw_acc.h
+_ACC_ADD_ARGS = [_P, _U32, _U32, _U64, _U64, _I, _P, _P, _P, _P, _P, _P]
+ACC_SYMBOLS = {
+    "aesw_acc_reset_device": (_I, [_P, _U32, _P, _P, _P]),
+    "aesw_acc_add_device": (_I, _ACC_ADD_ARGS),
+    "aesw_acc_add_device_chunk": (_I, _ACC_ADD_ARGS + [_U32]),
+    "aesw_acc_add_key_device": (_I, [_P, _U32, _I, C.POINTER(KeySlab), _P, _P, _P]),
+    "aesw_acc_default_chunk": (_U32, [_U32, _U32, _U64, _U64]),
+}
+
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 _NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
 # the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT)
@@ -217,6 +228,7 @@ _LIBRARIES = {
     "cols": (COLS_LIB_PATH, COLS_SYMBOLS, _NO_FALLBACK),
     "vals": (VALS_LIB_PATH, VALS_SYMBOLS, _NO_FALLBACK),
     "mult": (MULT_LIB_PATH, MULT_SYMBOLS, _NO_FALLBACK),
+    "acc": (ACC_LIB_PATH, ACC_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -280,6 +292,11 @@ def load_vals_library(path: Path | None = None) -> C.CDLL:
 def load_mult_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_mult.so (in-tree): the lookup multiplicities behind Context.lookup_multiplicities."""
     return _load("mult", path)
+
+
+def load_acc_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_acc.so (in-tree): the chunk-by-chunk lookup multiplicities behind Context.multiplicity_accumulator."""
+    return _load("acc", path)
 
 
 def mult_bin(tag: int, x: int, y: int = 0):
@@ -998,6 +1015,13 @@ class Context:
         self._check(rc, "aesw_mult_count_device")
         return _out, self._report(rep, sync, mult_report_dict)
 
+    def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
+        """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
+        (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
+        order, and add_key() its key slab; histograms() is then what lookup_multiplicities gives over the whole circuit.  `layout`
+        is the layout of every witness handed in; _out is an int32 [n_sets, 66561] tensor to count into (tests, tools)."""
+        return MultiplicityAccumulator(self, k, n_sets, layout, _out)
+
     def check_columns(self, k: int, n_sets: int, pt, keys, advice, counts, ct=None, sync: bool = True, _offsets=None):
         """MockProver::assert_satisfied over the ASSEMBLED advice columns of C FixedAes128Config<k, n_sets> circuits in one launch
         (aesw_cols_check_device, libaesw_cols.so).  advice: what assemble_advice_circuits returns, [C, 3*n_sets+1, 2^k] bytes or
@@ -1190,6 +1214,65 @@ def group_shard(members: int, n: int, i: int):
     return int(first.value), int(count.value)
 
 
+class MultiplicityAccumulator:
+    """What Context.multiplicity_accumulator returns.  Nothing here waits on the host or allocates after the constructor, so a
+    reset() and its add()s can be captured into one graph; a replay of captured add()s adds again."""
+
+    def __init__(self, ctx: "Context", k: int, n_sets: int, layout: int, _out=None):
+        torch = ctx._torch()
+        self._lib = load_acc_library()
+        self.ctx, self.k, self.n_sets, self.layout = ctx, int(k), int(n_sets), int(layout)
+        shape = (self.n_sets, K.TABLE_ROWS)
+        if _out is None:
+            _out = torch.empty(shape, dtype=torch.int32, device=ctx._dev())
+        elif tuple(_out.shape) != shape or _out.dtype != torch.int32 or not _out.is_contiguous():
+            raise ValueError("_out must be a contiguous int32 tensor of shape %r" % (shape,))
+        self._mult = _out
+        self._rep = torch.empty(3, dtype=torch.int64, device=ctx._dev())
+
+    def _stream(self, stream):
+        return self.ctx._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+
+    def reset(self, stream=None):
+        """Histograms to zero, the report to (0 lookups, 0 misses, no miss).  The first call of every count."""
+        rc = self._lib.aesw_acc_reset_device(self.ctx._h, self.n_sets, self._mult.data_ptr(), self._rep.data_ptr(), self._stream(stream))
+        self.ctx._check(rc, "aesw_acc_reset_device")
+        return self
+
+    def add(self, first_block: int, witness: Witness, stream=None, n_blocks: int | None = None, _chunk: int = 0):
+        """Adds circuit blocks [first_block, first_block + n_blocks): slab i of `witness` (x, y, z) is block first_block + i.
+        n_blocks: default every block `witness` holds; fewer when a reused buffer is only partly filled.  _chunk forces the
+        blocks a pair of workgroups takes (tests, tools)."""
+        x, y, z = [self.ctx._u8(t, "witness") for t in witness[:3]]
+        held = int(y.numel()) // column_stride(self.layout, 1) if self.layout in (K.LAYOUT_DENSE, K.LAYOUT_PACKED) else 0
+        n = held if n_blocks is None else int(n_blocks)
+        for i, t in enumerate((x, y, z)):
+            if n and int(t.numel()) < n * column_stride(self.layout, i):
+                raise ValueError("witness holds fewer than n_blocks blocks")
+        rc = self._lib.aesw_acc_add_device_chunk(self.ctx._h, self.k, self.n_sets, int(first_block), n, self.layout, x.data_ptr(), y.data_ptr(),
+                                                 z.data_ptr(), self._mult.data_ptr(), self._rep.data_ptr(), self._stream(stream), int(_chunk))
+        self.ctx._check(rc, "aesw_acc_add_device")
+        return self
+
+    def add_key(self, key_witness: KeyWitness, stream=None):
+        """Adds the 400 rows of the circuit's key slab (the first one `key_witness` holds) to set 0; nothing for k < 9."""
+        kx, ky, kz = [self.ctx._u8(t, "key_witness") for t in key_witness[1:4]]
+        ks = KeySlab(None, kx.data_ptr(), ky.data_ptr(), kz.data_ptr())
+        rc = self._lib.aesw_acc_add_key_device(self.ctx._h, self.k, self.layout, C.byref(ks), self._mult.data_ptr(), self._rep.data_ptr(),
+                                               self._stream(stream))
+        self.ctx._check(rc, "aesw_acc_add_key_device")
+        return self
+
+    def histograms(self):
+        """The int32 [n_sets, 66561] device tensor every call adds to (not a copy; nothing is synchronised)."""
+        return self._mult
+
+    def report(self, sync: bool = True):
+        """The dict of mult_report_dict over everything added since reset() -- a block's unit is its index in the circuit, the
+        key slab's 0 -- after synchronising the stream; with sync=False the uint64[3] device tensor."""
+        return self.ctx._report(self._rep, sync, mult_report_dict)
+
+
 def _group_refuses(name):
     def refuse(self, *args, **kwargs):
         raise AeswError(ERR_INVALID_ARG, "Group.%s: device pointers belong to one GPU; use a member (Group.member_handle(i) is its aesw_ctx*)" % name)
@@ -1239,7 +1322,7 @@ class Group(Context):
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
               "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values",
-              "lookup_multiplicities"):
+              "lookup_multiplicities", "multiplicity_accumulator"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
