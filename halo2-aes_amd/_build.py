@@ -111,8 +111,8 @@ SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),
     "vals": ([CSRC / "vals" / "aesw_vals_check.hip"], [CSRC / "aesw_vals_check.h"], INCLUDE / "aesw_vals.h"),
-    "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
-    "mult": ([CSRC / "mult" / "aesw_mult.hip"], [CSRC / "aesw_mult.h"], INCLUDE / "aesw_mult.h"),
+    "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
+    "mult": ([CSRC / "mult" / "aesw_mult.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h"], INCLUDE / "aesw_mult.h"),
 }
 CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
 

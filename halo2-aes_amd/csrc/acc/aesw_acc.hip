@@ -1,29 +1,28 @@
-// acc/aesw_acc.hip -- libaesw_acc.so (include/aesw_acc.h): the lookup multiplicities of ONE circuit, accumulated over any number
-// of calls, each of which adds a contiguous run of the circuit's blocks.  The bin rule is aesw_mult.h's, the
-// set of a block Placement's, the tag and the cell offsets of a row the check table's (aesw_check.h, uploaded by aesw_create),
-// and the way a slab travels -- 16-byte loads into registers, issued for the next block before the current one is walked out of
-// the wave's LDS image -- aesw_check_dev.h's.  What is here:
-//   * acc_reset_kernel: the histograms to zero (16-byte stores), the report to (0, 0, none);
-//   * acc_add_kernel<LAYOUT>: the division of labour of mult_private_kernel (mult/aesw_mult.hip) with (set, chunk) in place of
-//     (circuit, set).  The run is cut at the set boundaries and every piece into chunks of `chunk` blocks; a pair of workgroups
-//     owns a chunk -- workgroup 0 counts the Xor rows with x < 128 and the four small sections, workgroup 1 the Xor rows with
-//     x >= 128, in 32-bit LDS counters -- and each ADDS its half to the histogram of the set: lane i of a flush instruction adds
-//     bin base + i, a wave 64 consecutive words, a bin that stayed zero is skipped.  Integer adds commute, so the histograms do
-//     not depend on how the run was cut, on the order of the calls or on which workgroup arrives first;
-//   * acc_key_kernel<LAYOUT>: the 400 rows of one key slab by one wave, one global add per hit (not a hot path).
-// The row walk restates the one of mult/aesw_mult.hip: that file is a translation unit, not a header, and moving the walk into
-// one would recompile libaesw_mult.so, whose kernels are pinned.
+// acc/aesw_acc.hip -- libaesw_acc.so (include/aesw_acc.h): the lookup multiplicities of ONE circuit, accumulated over any
+// number of calls, each of which adds a contiguous run of the circuit's blocks.  The bin rule and the sizes
+// of the counter split are aesw_mult.h's, the set of a block Placement's, and the counting of a staged unit -- row entries,
+// the sinks (and with the LDS one which workgroup of a pair owns which bin), block staging, the
+// workgroup's report, the wave count next to the LDS counters -- aesw_mult_dev.h's, shared with libaesw_mult.so.  What is
+// here:
+//   * acc_reset_kernel: the histograms to zero, the report to (0, 0, none);
+//   * acc_add_kernel<LAYOUT>: the run is cut at the set boundaries and every piece into chunks of `chunk` blocks; a pair of
+//     workgroups owns a chunk, each counts the bins of its half in LDS and ADDS them to the histogram of the set: lane i of a
+//     flush instruction adds bin base + i, a wave 64 consecutive words, a bin that stayed zero is skipped.  Integer adds
+//     commute, so the histograms do not depend on how the run was cut, on the order of the calls or on which workgroup arrives
+//     first;
+//   * acc_key_kernel<LAYOUT>: the 400 rows of one key slab by one wave, one global add per hit (not a hot path);
+// and the entry points: their checks, the pieces of a run, the default chunk, the launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../../include/aesw_acc.h"
-#include "../aesw_check_dev.h"
 #include "../aesw_ctx.h"
-#include "../aesw_mult.h"
+#include "../aesw_mult_dev.h"
 #include "../aesw_placement.h"
 
 namespace aesw_acc {
 using namespace aesw;
+using namespace aesw::multdev;
 
 struct RunParams {
     const uint8_t *x, *y, *z;  // the slabs of circuit blocks [first, end): slab i is block first + i
@@ -44,104 +43,6 @@ struct KeySlabParams {
     uint64_t *report;
 };
 
-// What one lane found: enabled lookups, misses and the smallest miss (CheckAcc's key, kind CHK_LOOKUP).
-struct LaneAcc {
-    uint32_t lookups = 0, misses = 0;  // a lane sees at most 22 rows of 2^30 / AES_ROWS blocks
-    uint64_t first = ~0ull;
-};
-
-// A row entry of the check table with its offsets taken relative to `base` (0: a block image, BI: a key image on its own);
-// a cell the layout leaves out (CHECK_NONE: the rule never reads it on that row) points at byte 0.
-__device__ __forceinline__ void row_entry(const uint32_t *t, uint32_t at, uint32_t base, uint32_t &w0, uint32_t &w1) {
-    const uint32_t a = t[at], b = t[at + 1];
-    const uint32_t ox = (a & 0xffffu) == CHECK_NONE ? 0u : (a & 0xffffu) - base, oy = (a >> 16) == CHECK_NONE ? 0u : (a >> 16) - base,
-                   oz = (b & 0xffffu) == CHECK_NONE ? 0u : (b & 0xffffu) - base;
-    w0 = ox | oy << 16;
-    w1 = oz | (b >> 16) << 16;
-}
-
-// One row of a staged unit: the rule of aesw_mult.h, the hit into the sink, the miss into the lane's findings.
-template <class Sink>
-__device__ __forceinline__ void count_row(const uint8_t *img, const uint8_t *t768, uint32_t w0, uint32_t w1, uint64_t unit, uint32_t is_key,
-                                          uint32_t row, Sink &sink, LaneAcc &acc) {
-    const uint32_t tag = w1 >> 16;
-    const uint32_t x = img[w0 & 0xffffu], y = img[w0 >> 16], z = img[w1 & 0xffffu];
-    const bool enabled = tag != 0, hit = mult_hit(tag, x, y, z, t768), miss = enabled && !hit;
-    acc.lookups += enabled;
-    acc.misses += miss;
-    const uint64_t key = unit << 20 | (uint64_t)(is_key << 19 | (uint32_t)CHK_LOOKUP << 16 | row);
-    acc.first = miss && key < acc.first ? key : acc.first;
-    sink.add(hit, tag, x, y);
-}
-
-// The key rows: one global add per hit (no return value: nothing waits for it)
-struct GlobalSink {
-    uint32_t *hist;
-    __device__ __forceinline__ void add(bool hit, uint32_t tag, uint32_t x, uint32_t y) {
-        if (hit) atomicAdd(hist + mult_bin(tag, x, y), 1u);
-    }
-};
-// The blocks: the workgroup's counters.  half 0: Xor rows 512 .. 33 279 and the small sections (U8, Sbox | GfMul2, GfMul3 as
-// 1 024 consecutive counters); half 1: Xor rows 33 280 .. 66 047.
-constexpr uint32_t XOR_FIRST = mult_section_first(2), XOR_HALF = mult_section_rows(2) / 2, SMALL = 4 * 256, SMALL_LOW = 2 * 256;
-static_assert(XOR_FIRST == SMALL_LOW && mult_section_first(4) == XOR_FIRST + 2 * XOR_HALF && MULT_ZERO_ROW == mult_section_first(4) + SMALL_LOW,
-              "two small sections in front of the Xor section, two behind it");
-struct LdsSink {
-    uint32_t *cnt;  // XOR_HALF counters of the Xor half, then the SMALL ones
-    uint32_t half;
-    __device__ __forceinline__ void add(bool hit, uint32_t tag, uint32_t x, uint32_t y) {  // one predicated ds_add, no branch on the tag
-        const uint32_t bin = mult_bin(tag, x, y);
-        const bool is_xor = tag == 2;
-        const uint32_t at = is_xor ? bin - XOR_FIRST - half * XOR_HALF : XOR_HALF + (bin < XOR_FIRST ? bin : bin - 2 * XOR_HALF);
-        if (hit && (is_xor ? (x >> 7) == half : half == 0)) atomicAdd(cnt + at, 1u);
-    }
-};
-
-template <int LAYOUT>
-struct BlockStage {
-    using G = ChkLayout<LAYOUT>;
-    Staged<G::SX, 16> sx; Staged<G::SY, 16> sy; Staged<G::SZ, 16> sz;
-    __device__ __forceinline__ void load(const RunParams &a, uint64_t slab, uint32_t lane) {
-        sx.load(a.x + slab * G::SX, lane); sy.load(a.y + slab * G::SY, lane); sz.load(a.z + slab * G::SZ, lane);
-    }
-    __device__ __forceinline__ void store(uint8_t *img, uint32_t lane) const {
-        sx.store(img, lane); sy.store(img + G::SX, lane); sz.store(img + G::SX + G::SY, lane);
-    }
-};
-constexpr int ROW_STEPS = (AES_ROWS + LANES - 1) / LANES;  // 22 rows per lane
-// The lane's rows of a block, lane + 64 j: their entries, read once.  Past the last row: tag 0, no lookup.
-struct BlockRows {
-    uint32_t w0[ROW_STEPS], w1[ROW_STEPS];
-    __device__ __forceinline__ void load(const uint32_t *table, uint32_t lane) {
-#pragma unroll
-        for (int j = 0; j < ROW_STEPS; ++j) {
-            const uint32_t r = lane + LANES * j;
-            w0[j] = w1[j] = 0;
-            if (r < (uint32_t)AES_ROWS) row_entry(table, CHK_ROWS + 2 * r, 0, w0[j], w1[j]);
-        }
-    }
-    template <class Sink>
-    __device__ __forceinline__ void count(const uint8_t *img, const uint8_t *t768, uint64_t b, uint32_t lane, Sink &sink, LaneAcc &acc) const {
-#pragma unroll
-        for (int j = 0; j < ROW_STEPS; ++j) count_row(img, t768, w0[j], w1[j], b, 0, lane + LANES * j, sink, acc);
-    }
-};
-
-// The workgroup's findings: lanes -> three LDS words -> one lane's global atomics (a lane per workgroup, not per wave).
-__device__ __forceinline__ void rep_init(unsigned long long *rep) {
-    if (threadIdx.x < 3) rep[threadIdx.x] = threadIdx.x == 2 ? ~0ull : 0ull;
-}
-__device__ __forceinline__ void rep_collect(unsigned long long *rep, const LaneAcc &acc) {
-    if (acc.lookups) atomicAdd(rep, (unsigned long long)acc.lookups);
-    if (acc.misses) { atomicAdd(rep + 1, (unsigned long long)acc.misses); atomicMin(rep + 2, (unsigned long long)acc.first); }
-}
-__device__ __forceinline__ void rep_flush(uint64_t *report, const unsigned long long *rep) {  // after __syncthreads()
-    if (threadIdx.x == 0) { report_add(report, rep[0]); report_add(report + 1, rep[1]); report_min(report + 2, rep[2]); }
-}
-__device__ __forceinline__ void load_t768(uint32_t *t768w, const uint8_t *tab768) {
-    for (uint32_t i = threadIdx.x; i < 768 / 4; i += blockDim.x) t768w[i] = reinterpret_cast<const uint32_t *>(tab768)[i];
-}
-
 // `n` counters added to out[0 .. n): lane i of an instruction adds word i of 64 consecutive ones; zeros are skipped.
 __device__ __forceinline__ void flush_add(uint32_t *out, const uint32_t *cnt, uint32_t n) {
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
@@ -150,19 +51,12 @@ __device__ __forceinline__ void flush_add(uint32_t *out, const uint32_t *cnt, ui
     }
 }
 
-// as many waves as the LDS next to the counters holds images for
-template <int LAYOUT>
-struct AddGeo {
-    static constexpr int LDS = 160 * 1024, FIXED = (int)(XOR_HALF + SMALL) * 4 + 768 + 3 * 8;
-    static constexpr int WAVES = (LDS - FIXED) / ChkLayout<LAYOUT>::BI >= 8 ? 8 : (LDS - FIXED) / ChkLayout<LAYOUT>::BI;
-    static_assert(WAVES >= 4, "a workgroup of at least four waves");
-};
 // grid: x = 2 * (chunks of the longest piece), y = the pieces (one per set the run touches)
 template <int LAYOUT>
-__global__ void __launch_bounds__(AddGeo<LAYOUT>::WAVES * LANES) acc_add_kernel(const RunParams a) {
+__global__ void __launch_bounds__(CounterGeo<LAYOUT>::WAVES * LANES) acc_add_kernel(const RunParams a) {
     using G = ChkLayout<LAYOUT>;
-    constexpr int WAVES = AddGeo<LAYOUT>::WAVES;
-    __shared__ __attribute__((aligned(16))) uint32_t s_cnt[XOR_HALF + SMALL];
+    constexpr int WAVES = CounterGeo<LAYOUT>::WAVES;
+    __shared__ __attribute__((aligned(16))) uint32_t s_cnt[MULT_COUNTERS];
     __shared__ __attribute__((aligned(16))) uint8_t s_img[WAVES * G::BI];
     __shared__ uint32_t s_t768[768 / 4];
     __shared__ unsigned long long s_rep[3];
@@ -177,14 +71,14 @@ __global__ void __launch_bounds__(AddGeo<LAYOUT>::WAVES * LANES) acc_add_kernel(
     const uint8_t *t768 = reinterpret_cast<const uint8_t *>(s_t768);
     uint8_t *img = s_img + wave * G::BI;
     const u32x4 zero = {0, 0, 0, 0};
-    for (uint32_t i = threadIdx.x; i < (XOR_HALF + SMALL) / 4; i += blockDim.x) reinterpret_cast<u32x4 *>(s_cnt)[i] = zero;
+    for (uint32_t i = threadIdx.x; i < MULT_COUNTERS / 4; i += blockDim.x) reinterpret_cast<u32x4 *>(s_cnt)[i] = zero;
     load_t768(s_t768, a.tab768);
     rep_init(s_rep);
     BlockRows rows;
     rows.load(a.table, lane);
     __syncthreads();
     LdsSink sink{s_cnt, half};
-    LaneAcc acc;
+    Findings acc;
     BlockStage<LAYOUT> st;
     if (wave < cnt) st.load(a, b0 + wave - a.first, lane);
     for (uint64_t i = wave; i < cnt; i += WAVES) {
@@ -198,31 +92,33 @@ __global__ void __launch_bounds__(AddGeo<LAYOUT>::WAVES * LANES) acc_add_kernel(
     __syncthreads();
     // the bins this workgroup owns, added to the set's histogram
     uint32_t *const out = a.mult + (uint64_t)set * MULT_BINS;
-    const uint32_t *const s_xor = s_cnt, *const s_small = s_cnt + XOR_HALF;
-    flush_add(out + XOR_FIRST + half * XOR_HALF, s_xor, XOR_HALF);
+    // (the ranges are aesw_mult.h's, taken as constants: the Xor range of half 1 lies a constant stride behind half 0's)
+    constexpr MultFlushRange xr = mult_flush_range(0, 0), xr1 = mult_flush_range(1, 0), low = mult_flush_range(0, 1), high = mult_flush_range(0, 2);
+    static_assert(xr1.counter == xr.counter && xr1.length == xr.length, "the two Xor halves differ in their first bin alone");
+    flush_add(out + xr.bin + half * (xr1.bin - xr.bin), s_cnt + xr.counter, xr.length);
     if (half == 0) {
-        flush_add(out, s_small, SMALL_LOW);
-        flush_add(out + XOR_FIRST + 2 * XOR_HALF, s_small + SMALL_LOW, SMALL_LOW);
+        flush_add(out + low.bin, s_cnt + low.counter, low.length);
+        flush_add(out + high.bin, s_cnt + high.counter, high.length);
         rep_flush(a.report, s_rep);
     }
 }
 
-// One wave: kx | ky | kz into its image, the 400 rows into histogram 0.
+// One wave: kx | ky | kz into its image, the 400 rows into histogram 0 as unit 0.
 template <int LAYOUT>
 __global__ void __launch_bounds__(LANES) acc_key_kernel(const KeySlabParams a) {
     using G = ChkLayout<LAYOUT>;
     __shared__ __attribute__((aligned(16))) uint8_t s_img[(G::O_W + 15) / 16 * 16];
     __shared__ uint32_t s_t768[768 / 4];
-    constexpr int KZV = G::KZS % 16 == 0 ? 16 : 8;  // a packed kz is 200 bytes
     const uint32_t lane = threadIdx.x;
-    const uint8_t *t768 = reinterpret_cast<const uint8_t *>(s_t768);
     load_t768(s_t768, a.tab768);
+    constexpr int KZV = G::KZS % 16 == 0 ? 16 : 8;  // a packed kz is 200 bytes
     Staged<G::KXS, 16> kx; Staged<G::KYS, 16> ky; Staged<G::KZS, KZV> kz;
     kx.load(a.kx, lane); ky.load(a.ky, lane); kz.load(a.kz, lane);
     kx.store(s_img, lane); ky.store(s_img + G::O_KY, lane); kz.store(s_img + G::O_KZ, lane);
     wave_lds_sync();
     GlobalSink sink{a.mult};
-    LaneAcc acc;
+    Findings acc;
+    const uint8_t *t768 = reinterpret_cast<const uint8_t *>(s_t768);
     for (uint32_t r = lane; r < (uint32_t)KEY_ROWS; r += LANES) {
         uint32_t w0, w1;
         row_entry(a.table, CHK_KROWS + 2 * r, G::BI, w0, w1);
@@ -258,8 +154,8 @@ static int refuse(aesw_ctx *ctx, const char *call, const char *why, int status =
 }
 // what every call checks of its outputs and of the circuit's shape (with_k: the call takes a k)
 static const char *bad_outputs(uint32_t k, bool with_k, uint32_t n_sets, const uint32_t *d_mult, const aesw_mult_report *d_report) {
-    if (with_k && (k < 2 || k > 30)) return "k must be 2 ... 30";
-    if (n_sets == 0 || n_sets > 1024) return "n_sets must be 1 ... 1024";
+    if (with_k && !mult_k_ok(k)) return "k must be 2 ... 30";
+    if (!mult_sets_ok(n_sets)) return "n_sets must be 1 ... 1024";
     if (!d_report || !aligned_to(d_report, 8)) return "d_report must be there and 8-byte aligned";
     if (!d_mult || !aligned_to(d_mult, 16)) return "d_mult must be there and 16-byte aligned";
     return nullptr;
@@ -292,8 +188,6 @@ int aesw_acc_add_device_chunk(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64
     if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
     if (!ctx) return AESW_ERR_INVALID_ARG;
     if (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED) return refuse(ctx, call, "the layout must be DENSE or PACKED (a VALUES witness has no x)");
-    // A histogram counts rows of one set, and a set has 2^k rows: with k <= 30 every count fits the 32 bits of a bin (and of an
-    // LDS counter), identical blocks included.
     if (const char *why = bad_outputs(k, true, n_sets, d_mult, d_report)) return refuse(ctx, call, why);
     const Placement place(k);
     const uint64_t cap = place.total(n_sets);
@@ -330,8 +224,8 @@ int aesw_acc_add_device_chunk(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     const dim3 grid((unsigned)(2 * pairs), set1 - p.set0 + 1);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (layout == AESW_LAYOUT_DENSE) hipLaunchKernelGGL((acc_add_kernel<DENSE>), grid, dim3(AddGeo<DENSE>::WAVES * LANES), 0, s, p);
-    else hipLaunchKernelGGL((acc_add_kernel<PACKED>), grid, dim3(AddGeo<PACKED>::WAVES * LANES), 0, s, p);
+    if (layout == AESW_LAYOUT_DENSE) hipLaunchKernelGGL((acc_add_kernel<DENSE>), grid, dim3(CounterGeo<DENSE>::WAVES * LANES), 0, s, p);
+    else hipLaunchKernelGGL((acc_add_kernel<PACKED>), grid, dim3(CounterGeo<PACKED>::WAVES * LANES), 0, s, p);
     HIP_TRY(ctx, hipGetLastError());
     return AESW_OK;
 }
@@ -352,8 +246,7 @@ int aesw_acc_add_key_device(aesw_ctx *ctx, uint32_t k, int layout, const aesw_ke
     const aesw_key_slab *ks = d_key_slab;
     if (!ks || !ks->kx || !ks->ky || !ks->kz || !aligned_to(ks->kx, 16) || !aligned_to(ks->ky, 16) || !aligned_to(ks->kz, 16))
         return refuse(ctx, call, "the key columns kx, ky and kz must be there and 16-byte aligned");
-    // a circuit of fewer than KEY_ROWS rows has no room for the key schedule: no key selector is enabled there (aesw_assemble_selectors)
-    if (((uint64_t)1 << k) < aesw::KEY_ROWS) return AESW_OK;
+    if (!mult_has_key_rows(k)) return AESW_OK;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     KeySlabParams p{};

@@ -6,7 +6,10 @@ with g++ -- no ROCm include, no GPU -- into tests/mult_rule_driver.cpp:
   * whatever is no table row is a miss: for the one-operand tags exhaustively over (x, y) -- exactly 256 hits, each the table's
     --, for Xor every (x, y) with the right z hits and a wrong z, one per (x, y) and varied by a seed, never does;
   * tag 0 and numbers that are no tag have no bin and never hit;
-  * the library's aesw_mult_bin is the header's."""
+  * the library's aesw_mult_bin is the header's;
+  * the counter split of the kernels that count in LDS: every lookup is owned by exactly one half of a pair, its counter lies
+    inside the half's counters, no two bins of a half share one, and the flush ranges of the two halves cover every bin but
+    the zero row exactly once and map each counter back to the bin the index rule sent there."""
 import subprocess
 from pathlib import Path
 
@@ -55,6 +58,16 @@ def test_what_is_no_table_row_is_a_miss(driver, which):
     # tag 0, and numbers that are no tag: no bin, no hit; a range lookup always hits and ignores y and z
     none = 2 ** 32 - 1
     assert driver(tables, [("r", 0, 5, 5, 0), ("r", 6, 1, 2, 3), ("r", 7, 0, 0, 0), ("r", 1, 200, 9, 9)]) == [[none, 0], [none, 0], [none, 0], [200, 1]]
+
+
+def test_the_counter_split_and_the_flush_ranges_agree_bin_for_bin(driver):
+    tables = ol.Oracle().tables()  # the split reads no table; the driver wants one
+    once, over, clash, covered, stray, back = driver(tables, [("s",)])[0]
+    assert once == 5 * 65536, "a lookup owned by both halves or by none"
+    assert over == 0, "a counter index at or past XOR_HALF + SMALL"
+    assert clash == 0, "two bins of one half on one counter"
+    assert covered == 66560 and stray == 0, "the ranges cover bins 0 ... 66 559 exactly once and never the zero row"
+    assert back == 0, "a range maps a counter to another bin than the index rule"
 
 
 def test_the_library_exports_the_same_rule(pkg, driver):
