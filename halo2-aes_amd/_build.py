@@ -5,8 +5,9 @@
                                   no device code, linked against libaesw.so -- it only calls the C ABI
   halo2-aes_amd/libaesw_<name>.so one library per entry of SATELLITES (the checkers -- circ: many circuits, include/aesw_circ.h;
                                   cols: the assembled advice columns, include/aesw_cols.h; vals: a VALUES witness,
-                                  include/aesw_vals.h --, mult: the lookup multiplicities, include/aesw_mult.h, and acc: the same
-                                  accumulated chunk by chunk, include/aesw_acc.h): its
+                                  include/aesw_vals.h --, mult: the lookup multiplicities, include/aesw_mult.h, acc: the same
+                                  accumulated chunk by chunk, include/aesw_acc.h, and vacc: accumulated from a VALUES
+                                  witness, include/aesw_vacc.h): its
                                   own gfx950 kernels and entry point (hipcc), linked against libaesw.so, whose context it
                                   takes.  All are built by build_satellite() alike.
 
@@ -112,14 +113,17 @@ SATELLITES = {
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),
     "vals": ([CSRC / "vals" / "aesw_vals_check.hip"], [CSRC / "aesw_vals_check.h"], INCLUDE / "aesw_vals.h"),
     "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
+    "vacc": ([CSRC / "vacc" / "aesw_vacc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", CSRC / "aesw_vals_check.h", CSRC / "aesw_vacc.h", INCLUDE / "aesw_mult.h"],
+             INCLUDE / "aesw_vacc.h"),
     "mult": ([CSRC / "mult" / "aesw_mult.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h"], INCLUDE / "aesw_mult.h"),
 }
-CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
+CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, VACC_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
 
 
-def build_satellite(name: str, force: bool = False) -> Path:
+def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
     """libaesw_<name>.so: a checker's kernels and its entry point (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
-    A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are."""
+    A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are.  With `extra_flags` and
+    another `out` (a file name next to libaesw.so) a measurement variant of it (tools/vacc_bench.py: -DAESW_VACC_WAVES=16)."""
     sources, headers, public = SATELLITES[name]
-    return _build(PKG / ("libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
-                  lambda tmp: _hipcc_shared(sources, tmp, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)
+    return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
+                  lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)

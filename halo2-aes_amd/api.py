@@ -23,6 +23,7 @@ COLS_LIB_PATH = _PKG / "libaesw_cols.so"  # the checker of the assembled advice 
 VALS_LIB_PATH = _PKG / "libaesw_vals.so"  # the checker of a VALUES witness (include/aesw_vals.h), next to libaesw.so
 MULT_LIB_PATH = _PKG / "libaesw_mult.so"  # the lookup multiplicities of a many-circuit batch (include/aesw_mult.h), next to libaesw.so
 ACC_LIB_PATH = _PKG / "libaesw_acc.so"    # the lookup multiplicities of one circuit, accumulated chunk by chunk (include/aesw_acc.h)
+VACC_LIB_PATH = _PKG / "libaesw_vacc.so"  # the same accumulated from a VALUES witness (include/aesw_vacc.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -218,6 +219,15 @@ ACC_SYMBOLS = {
     "aesw_acc_default_chunk": (_U32, [_U32, _U32, _U64, _U64]),
 }
 
+# include/aesw_vacc.h
+_VACC_ADD_ARGS = [_P, _U32, _U32, _U64, _U64, _P, _P, _P, C.POINTER(KeySlab), _P, _P, _P]
+VACC_SYMBOLS = {
+    "aesw_vacc_add_device": (_I, _VACC_ADD_ARGS),
+    "aesw_vacc_add_device_chunk": (_I, _VACC_ADD_ARGS + [_U32]),
+    "aesw_vacc_default_chunk": (_U32, [_U32, _U32, _U64, _U64]),
+    "aesw_vacc_prepare": (_I, [_P]),
+}
+
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 _NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
 # the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT)
@@ -229,6 +239,7 @@ _LIBRARIES = {
     "vals": (VALS_LIB_PATH, VALS_SYMBOLS, _NO_FALLBACK),
     "mult": (MULT_LIB_PATH, MULT_SYMBOLS, _NO_FALLBACK),
     "acc": (ACC_LIB_PATH, ACC_SYMBOLS, _NO_FALLBACK),
+    "vacc": (VACC_LIB_PATH, VACC_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -297,6 +308,11 @@ def load_mult_library(path: Path | None = None) -> C.CDLL:
 def load_acc_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_acc.so (in-tree): the chunk-by-chunk lookup multiplicities behind Context.multiplicity_accumulator."""
     return _load("acc", path)
+
+
+def load_vacc_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_vacc.so (in-tree): the lookup multiplicities of a VALUES witness behind MultiplicityAccumulator.add_values."""
+    return _load("vacc", path)
 
 
 def mult_bin(tag: int, x: int, y: int = 0):
@@ -1252,6 +1268,27 @@ class MultiplicityAccumulator:
         rc = self._lib.aesw_acc_add_device_chunk(self.ctx._h, self.k, self.n_sets, int(first_block), n, self.layout, x.data_ptr(), y.data_ptr(),
                                                  z.data_ptr(), self._mult.data_ptr(), self._rep.data_ptr(), self._stream(stream), int(_chunk))
         self.ctx._check(rc, "aesw_acc_add_device")
+        return self
+
+    def add_values(self, first_block: int, pt, witness: Witness, key_witness: KeyWitness, stream=None, n_blocks: int | None = None, _chunk: int = 0):
+        """Adds circuit blocks [first_block, first_block + n_blocks) given as a VALUES witness (libaesw_vacc.so, loaded on the
+        first call): `witness` is what encrypt_witness(layout=LAYOUT_VALUES) returns (its y and z are read, x is ignored), pt
+        uint8[n,16] the plaintext of the same blocks, key_witness the circuit's packed key slab, of which the round-key cells are
+        read -- its own 400 rows are add_key()'s.  Whatever `layout` the accumulator was made with: the histograms do not depend
+        on it.  n_blocks and _chunk as for add()."""
+        lib = load_vacc_library()
+        pt, y, z = self.ctx._u8(pt, "pt"), self.ctx._u8(witness.y, "witness"), self.ctx._u8(witness.z, "witness")
+        w, kz = self.ctx._u8(key_witness[0], "key_witness"), self.ctx._u8(key_witness[3], "key_witness")
+        n = int(y.numel()) // column_stride(K.LAYOUT_VALUES, 1) if n_blocks is None else int(n_blocks)
+        for t, per in ((pt, 16), (y, column_stride(K.LAYOUT_VALUES, 1)), (z, column_stride(K.LAYOUT_VALUES, 2))):
+            if int(t.numel()) < n * per:
+                raise ValueError("pt or witness holds fewer than n_blocks blocks")
+        if int(w.numel()) < K.WORDS_ROWS or int(kz.numel()) < key_column_stride(K.LAYOUT_PACKED, 2):
+            raise ValueError("key_witness must hold one packed key slab")
+        ks = KeySlab(w.data_ptr(), None, None, kz.data_ptr())
+        rc = lib.aesw_vacc_add_device_chunk(self.ctx._h, self.k, self.n_sets, int(first_block), n, pt.data_ptr(), y.data_ptr(), z.data_ptr(),
+                                            C.byref(ks), self._mult.data_ptr(), self._rep.data_ptr(), self._stream(stream), int(_chunk))
+        self.ctx._check(rc, "aesw_vacc_add_device")
         return self
 
     def add_key(self, key_witness: KeyWitness, stream=None):

@@ -1,0 +1,124 @@
+"""libaesw_vacc.so without a GPU: that build() makes it and what it is made of.
+
+  * it exists after build(), exports exactly the aesw_vacc_ functions include/aesw_vacc.h declares, api.VACC_SYMBOLS binds exactly
+    those, its NEEDED entry is libaesw.so via $ORIGIN (and no other satellite is one), "vacc" is an entry of _build.SATELLITES with
+    "mult" still the last, and the Python face is there;
+  * every __global__ in it is launched by the GPU sweep (tests/vacc_cases.py), and that list names nothing else;
+  * its code object: no scratch, no VGPR spills, at most 256 unified registers, the counters and at most 160 KiB of static LDS, an
+    LDS add per row step, the flushes and the report as global atomics; compared with the tracked table
+    profiles/isa_resources_vacc.json (regenerate it on purpose with AESW_UPDATE_ISA_JSON=1 python -m pytest
+    tests/test_vacc_library.py);
+  * aesw_vacc_default_chunk is aesw_acc_default_chunk on the shapes of tests/test_acc_library.py;
+  * the other libraries and their headers carry none of the new symbols, and the accumulator still refuses VALUES by name."""
+import importlib.util
+import subprocess
+
+import pytest
+
+import check_library as cl
+import vacc_cases as vc
+from isa_extract import needs_llvm
+
+TABLE = cl.ROOT / "profiles" / "isa_resources_vacc.json"
+code_object = cl.code_object_fixture("VACC_LIB_PATH")
+DECLARED = ["aesw_vacc_add_device", "aesw_vacc_add_device_chunk", "aesw_vacc_default_chunk", "aesw_vacc_prepare"]
+OTHERS = ("LIB_PATH", "CIRC_LIB_PATH", "COLS_LIB_PATH", "VALS_LIB_PATH", "ACC_LIB_PATH", "MULT_LIB_PATH", "HOST_LIB_PATH")
+
+
+def _build_module():
+    spec = importlib.util.spec_from_file_location("b", cl.ROOT / "halo2-aes_amd" / "_build.py")
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_build_makes_the_library_and_it_exports_the_header(pkg):
+    api = pkg.api
+    lib = api.VACC_LIB_PATH
+    assert lib.name == "libaesw_vacc.so" and lib.parent == api.LIB_PATH.parent and lib.exists()
+    decl = cl.declared("aesw_vacc.h", "aesw_vacc_")
+    assert decl == DECLARED
+    exported = {line.split()[-1] for line in cl.nm(lib, "-D", "--defined-only").splitlines() if " T " in line}
+    assert sorted(f for f in exported if f.startswith("aesw_")) == decl, sorted(exported)[:20]
+    loaded = api.load_vacc_library()
+    assert api.load_vacc_library() is loaded
+    assert sorted(api.VACC_SYMBOLS) == decl and all(getattr(loaded, f) is not None for f in decl)
+    assert api._LIBRARIES["vacc"][:2] == (lib, api.VACC_SYMBOLS)
+    dyn = subprocess.run(["readelf", "-d", str(lib)], stdout=subprocess.PIPE, text=True, check=True).stdout
+    assert "libaesw.so" in dyn and "$ORIGIN" in dyn, dyn
+    assert not [s for s in ("libaesw_acc", "libaesw_mult", "libaesw_vals", "libaesw_circ", "libaesw_cols", "libaesw_host") if s in dyn], dyn
+    assert (cl.ROOT / "halo2-aes_amd" / "csrc" / "vacc" / "aesw_vacc.hip").exists()  # one level below csrc/, as every satellite's
+    b = _build_module()
+    names = list(b.SATELLITES)
+    assert "vacc" in names and names[-1] == "mult" and names.index("vacc") == len(names) - 2 and b.VACC_LIB == lib
+    assert b.MULT_LIB.name == "libaesw_mult.so" and b.ACC_LIB.name == "libaesw_acc.so"  # the tuple below SATELLITES still names each its own
+    assert callable(api.MultiplicityAccumulator.add_values)
+    header = (cl.ROOT / "include" / "aesw_vacc.h").read_text()
+    assert '#include "aesw_mult.h"' in header and "aesw_acc.h\"" not in header and "aesw_vals.h\"" not in header
+
+
+def test_a_missing_path_says_how_to_build_it(pkg, tmp_path):
+    missing = tmp_path / "nowhere" / pkg.api.VACC_LIB_PATH.name
+    with pytest.raises(FileNotFoundError) as e:
+        pkg.api.load_vacc_library(missing)
+    assert str(missing) in str(e.value) and "There is no fallback implementation." in str(e.value)
+
+
+def test_an_accumulator_that_never_sees_values_does_not_load_the_library():
+    """add_values loads libaesw_vacc.so on its first call: the constructor binds libaesw_acc.so alone."""
+    import ast
+    tree = ast.parse((cl.ROOT / "halo2-aes_amd" / "api.py").read_text())
+    cls = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "MultiplicityAccumulator")
+    loads = {f.name: [c.func.id for c in ast.walk(f) if isinstance(c, ast.Call) and isinstance(c.func, ast.Name) and c.func.id.startswith("load_")]
+             for f in cls.body if isinstance(f, ast.FunctionDef)}
+    assert loads["add_values"] == ["load_vacc_library"] and loads["__init__"] == ["load_acc_library"]
+    assert not [name for name, ls in loads.items() if "load_vacc_library" in ls and name != "add_values"]
+
+
+def test_the_default_chunk_is_the_accumulators(pkg):
+    chunk, acc_chunk = pkg.api.load_vacc_library().aesw_vacc_default_chunk, pkg.api.load_acc_library().aesw_acc_default_chunk
+    cap = pkg.block_capacity(24, 4)
+    big = pkg.block_capacity(30, 1024)
+    shapes = ((14, 3, 0, 34), (14, 3, 7, 1), (20, 4, 0, 3083), (24, 4, 0, cap), (24, 4, 0, 1 << 15), (24, 4, 1 << 15, cap - (1 << 15)), (30, 1024, 0, big),
+              (12, 1, 0, 0), (9, 1, 0, 0), (12, 2, 3, 1), (16, 3, 5, 100), (24, 4, 0, 40000), (30, 7, 1 << 20, 1 << 22))
+    for shape in shapes:
+        assert chunk(*shape) == acc_chunk(*shape) >= 1, shape
+    assert chunk(14, 3, 0, 34) == 256 and chunk(24, 4, 0, cap) == 386 and chunk(30, 1024, 0, big) == -(-big // 128)
+
+
+def test_the_other_libraries_are_left_alone(pkg):
+    for other in OTHERS:
+        text = cl.nm(getattr(pkg.api, other), "-C")
+        assert "aesw_vacc" not in text and "vacc_count_kernel" not in text, other
+    for header in sorted((cl.ROOT / "include").glob("*.h")):
+        if header.name != "aesw_vacc.h":
+            assert "aesw_vacc" not in header.read_text(), header.name
+    # every refusal of VALUES stays, by name
+    acc = (cl.ROOT / "halo2-aes_amd" / "csrc" / "acc" / "aesw_acc.hip").read_text()
+    assert acc.count("the layout must be DENSE or PACKED (a VALUES witness has no x)") == 2
+
+
+def test_a_group_refuses(pkg):
+    with pytest.raises(pkg.AeswError) as e:
+        pkg.Group.multiplicity_accumulator(None, 12, 1)
+    assert e.value.status == pkg.api.ERR_INVALID_ARG
+
+
+def test_every_kernel_of_the_library_is_swept_and_the_list_names_nothing_else(pkg):
+    cl.check_swept(pkg.api.VACC_LIB_PATH, vc.launched())
+    assert len(vc.launched()) == 1
+    src = (cl.ROOT / "tests" / "test_gpu_vacc.py").read_text()
+    assert all(name in src for name in ("vc.SHAPES", "vc.TABLE_SETS", "vc.FORCED_CHUNKS", "vc.CONTENTION", "vc.ragged", "vc.CORRUPTIONS"))
+
+
+@needs_llvm
+def test_gfx950_code_without_scratch_or_spills_and_the_tracked_table(code_object):
+    columns = dict(cl.GLOBAL_COLUMNS, lds_adds="ds_add_u32")
+    table = cl.resource_table(code_object, columns)  # no scratch, no VGPR spills, at most 256 unified registers
+    assert set(table) == vc.launched(), sorted(table)
+    row = table["aesw_vacc::vacc_count_kernel"]
+    # the counters: LDS adds, one per row step; global atomics: the flushes of the Xor half and of the two small ranges, and the
+    # three words of the report; LDS: the counters and more, within a workgroup's 160 KiB
+    assert row["lds_adds"] >= 17 and 3 + 3 <= row["global_atomics"] and 132 * 1024 < row["static_lds"] <= 160 * 1024, row
+    assert row["global_stores"] == 0, row
+    cl.assert_tracked(table, TABLE)
