@@ -102,6 +102,30 @@ class DeviceArena(_Base):
         self.torch.cuda.synchronize(self.dev)
         super().check()
 
+    def check_on_device(self):
+        """check() for buffers too large to copy to the host: the same guard bytes, compared by torch on the device."""
+        self.torch.cuda.synchronize(self.dev)
+        for name, (buf, lo, nbytes) in self._bufs.items():
+            for part, rel0 in ((buf[:lo], -lo), (buf[lo + nbytes:], nbytes)):
+                bad = self.torch.nonzero(part != self.canary)
+                if bad.numel():
+                    at = int(bad[0])
+                    raise AssertionError("%s: guard damaged at offset %d of the %d-byte view (0x%02x, canary 0x%02x; %d bytes damaged)" %
+                                         (name, rel0 + at, nbytes, int(part[at]), self.canary, bad.numel()))
+
+    def poisoned_on_device(self, view) -> bool:
+        """poisoned() without the copy to the host."""
+        v = view.contiguous().view(self.torch.uint8).reshape(-1)
+        if v.numel() % 4 == 0 and v.data_ptr() % 4 == 0:  # word by word: a quarter of the temporary
+            word = int.from_bytes(bytes([self.canary]) * 4, "little", signed=True)
+            return bool((v.view(self.torch.int32) == word).all())
+        return bool((v == self.canary).all())
+
+    def repoison(self):
+        """Every byte of every buffer, views and guards, back to the canary: a large buffer is used a second time."""
+        for buf, _lo, _nbytes in self._bufs.values():
+            buf.fill_(self.canary)
+
     def witness(self, pkg, n, layout, want_ct=True, key_slab=True, n_keys=None):
         """A Witness as Context.alloc_witness shapes it, every member guarded and poisoned."""
         cols = [self.out("xyz"[c], n * pkg.column_stride(layout, c)) for c in range(3)]

@@ -38,3 +38,32 @@ def multiplicities(advice, selectors, tables):
             hist[s] += np.bincount(bins[hit], minlength=BINS)
             misses += int((~hit).sum())
     return hist, misses
+
+
+BLOCK_ROWS, KEY_ROWS = 1360, 400
+
+
+def _rows(advice, selectors, tables, s, first, n):
+    """(hist int64[66561], misses) of rows [first, first + n) of set s alone: multiplicities over the slice of the set's three
+    advice and five selector columns, as a circuit of one set (its last advice and last selector column play no part)."""
+    advice, selectors = np.asarray(advice), np.asarray(selectors)
+    pad = np.zeros((1, n), np.uint8)
+    a3, s5 = advice[3 * s:3 * s + 3, first:first + n], selectors[5 * s:5 * s + 5, first:first + n]
+    assert a3.shape == (3, n) and s5.shape == (5, n), "rows %d ... %d of set %d are not all there" % (first, first + n, s)
+    hist, misses = multiplicities(np.concatenate([a3, pad]), np.concatenate([s5, pad]), tables)
+    return hist[0], misses
+
+
+def block_histograms(advice, selectors, tables, places):
+    """(hist int64[len(places), 66561], misses int64[len(places)]): for every (set, first row) of `places` -- where the circuit
+    placed a block -- what the block's 1 360 rows look up.  Which blocks a circuit counts, and into which set, is the caller's
+    to say: nothing here knows a slab index or an offset list."""
+    hist, misses = np.zeros((len(places), BINS), np.int64), np.zeros(len(places), np.int64)
+    for i, (s, first) in enumerate(places):
+        hist[i], misses[i] = _rows(advice, selectors, tables, s, first, BLOCK_ROWS)
+    return hist, misses
+
+
+def key_histogram(advice, selectors, tables):
+    """(hist int64[66561], misses) of the key schedule's rows: rows 0 ... 399 of set 0."""
+    return _rows(advice, selectors, tables, 0, 0, KEY_ROWS)

@@ -183,7 +183,8 @@ def test_every_cut_of_a_circuit_equals_the_model(pkg, worlds, k, n_sets, n, layo
     same(got, exp_blocks, "one slab buffer")
     assert rep == {"lookups": 1056 * n, "misses": 0, "first_miss": None}, rep
 
-    for chunk in ac.FORCED_CHUNKS:  # several pairs of workgroups add into the same bins
+    # several pairs of workgroups add into the same bins; from LONG_FROM blocks on also chunks longer than one round of the waves
+    for chunk in ac.FORCED_CHUNKS + (ac.LONG_CHUNKS if n >= ac.LONG_FROM else ()):
         a = Acc(c, arenas[1], "_chunk%d" % chunk)
         a.reset(), a.add_key(), a.add(0, n, chunk=chunk)
         got, rep = a.result()
@@ -218,6 +219,94 @@ def test_identical_blocks_count_exactly(pkg, worlds):
     got, rep = a.result()
     same(got, exp, "identical blocks")
     assert rep == clean(k, n)
+
+
+def many_sets_expectation(pkg, orc, key, pt):
+    """{set: int64[BINS]} after ac.MANY_RUNS, the runs' blocks being those of `pt` in the order of the runs.  The histogram of a
+    block does not depend on where a circuit places it: mult_model's block_histograms over the oracle's K = 14 / N = 3 circuit of
+    the same key and plaintexts; the set of a circuit block is the product's placement (held against the oracle's in
+    tests/test_placement.py)."""
+    k, n_sets = ac.MANY_SETS
+    assert len(pt) == sum(count for _first, count in ac.MANY_RUNS) <= pkg.block_capacity(14, 3)
+    with orc.circuit(14, 3, key, pt, record_copies=False) as c:
+        assert c.status == 0
+        adv = np.stack([c.advice(i) for i in range(3 * 3 + 1)])
+        sel = np.stack([c.selector(i) for i in range(5 * 3 + 1)])
+        places = [c.block_placement(b) for b in range(len(pt))]
+    h, misses = mm.block_histograms(adv, sel, orc.tables(), places)
+    assert not misses.any() and h.sum(axis=1).tolist() == [1056] * len(pt)
+    exp, at = {}, 0
+    for first, count in ac.MANY_RUNS:
+        for j in range(count):
+            s = pkg.block_placement(k, n_sets, first + j)[0]
+            exp[s] = exp.get(s, 0) + h[at]
+            at += 1
+    assert tuple(sorted(exp)) == ac.MANY_TOUCHED
+    return exp
+
+
+def check_many_sets(a, exp, n):
+    """The histograms of a.mult32 [n_sets, BINS] are `exp` in its sets and zero in every other one -- looked at on the device, only
+    the sets of `exp` are copied to the host --, the report is clean over n blocks, the guards are intact."""
+    import torch
+    a.arena.check_on_device()
+    touched = sorted(exp)
+    busy = torch.nonzero((a.mult32 != 0).any(dim=1)).flatten().tolist()
+    assert busy == touched, "sets with a count: %s, expected %s" % (busy[:16], touched)
+    got = a.mult32[torch.as_tensor(touched, device=a.mult32.device)].cpu().numpy().astype(np.int64)
+    same(got, np.stack([exp[s] for s in touched]), "the sets %s" % (touched,))
+    rep = a.c.pkg.api.mult_report_dict(a.rep.view(torch.int64))
+    assert rep == {"lookups": 1056 * n, "misses": 0, "first_miss": None}, rep
+
+
+@pytest.mark.parametrize("layout", ac.LAYOUTS)
+def test_a_circuit_of_1024_sets(pkg, worlds, layout):
+    """n_sets at its bound: runs that start and end deep inside the set index, each add out of slab views of its own."""
+    ctx, orc = worlds["reference"]
+    k, n_sets = ac.MANY_SETS
+    assert pkg.block_capacity(k, n_sets) == 3070
+    c = Circuit(pkg, ctx, layout, k, n_sets, 16, seed=1024)
+    exp = many_sets_expectation(pkg, orc, c.key, c.pt)
+    a = Acc(c, G.DeviceArena(), "_many")
+    a.reset()
+    at = 0
+    for first, count in ac.MANY_RUNS:
+        a.add(first, count, slabs=c.slabs(at, count))  # slab i of a run is block first + i
+        at += count
+    check_many_sets(a, exp, 16)
+
+
+def test_one_run_through_all_1024_sets(pkg, worlds):
+    """One add of all 3 070 blocks: a grid 1 024 pieces high.  The yardstick is mult_model's block_histograms over the columns the
+    product assembles for the same blocks at K = 22 / N = 1 (3 082 blocks in one set), every bin of every set compared."""
+    import torch
+    ctx, _orc = worlds["reference"]
+    k, n_sets = ac.MANY_SETS
+    n = pkg.block_capacity(k, n_sets)
+    assert n == 3070 <= pkg.block_capacity(22, 1)
+    c = Circuit(pkg, ctx, ac.PACKED, k, n_sets, n, seed=3070)
+    adv = ctx.assemble_advice_circuits(22, 1, c.wit, c.kw, [n], as_fr=False, layout=ac.PACKED, n_blocks=n).cpu().numpy()[0]
+    sel, _fixed = pkg.assemble_selectors(22, 1, n)
+    sets = [pkg.block_placement(k, n_sets, b)[0] for b in range(n)]
+    assert sets == [0] + [1 + (b - 1) // 3 for b in range(1, n)]
+    places = {}  # set of the K = 12 circuit -> where the K = 22 circuit placed its blocks: set s >= 1 holds blocks 1 + 3 (s - 1) ... 3 + 3 (s - 1)
+    for b in range(n):
+        places.setdefault(sets[b], []).append(pkg.block_placement(22, 1, b))
+    exp = np.zeros((n_sets, BINS), np.int32)
+    for s in range(n_sets):
+        h, misses = mm.block_histograms(adv, sel, ctx._tables, places[s])
+        assert not misses.any()
+        exp[s] = h.sum(axis=0)
+    assert int(exp.sum(dtype=np.int64)) == 1056 * n
+    a = Acc(c, G.DeviceArena(G.CANARIES[1]), "_all")
+    a.reset(), a.add(0, n)
+    a.arena.check_on_device()
+    want = torch.from_numpy(exp).cuda()
+    bad = torch.nonzero(a.mult32 != want)
+    assert not bad.numel(), "%d bins differ, first (set, bin) = %s: got %d, expected %d" % (
+        len(bad), bad[0].tolist(), int(a.mult32[tuple(bad[0])]), int(want[tuple(bad[0])]))
+    rep = pkg.api.mult_report_dict(a.rep.view(torch.int64))
+    assert rep == {"lookups": 1056 * n, "misses": 0, "first_miss": None}, rep
 
 
 def test_misses_are_counted_named_and_left_out_of_the_bins(pkg, worlds):

@@ -44,12 +44,15 @@ class Batch:
         self.d_offs = torch.from_numpy(self.offs.view(np.int64)).cuda()
         torch.cuda.synchronize()
 
-    def raw(self, mult, report, form, key_slabs=True, layout=None, k=None, expect=0):
-        """The test-facing C entry point on torch's current stream; returns the status."""
+    def raw(self, mult, report, form, key_slabs=True, layout=None, k=None, expect=0, offsets=None):
+        """The test-facing C entry point on torch's current stream; returns the status.  offsets: a device tensor of C + 1 int64 in
+        place of the batch's own."""
         lib, ctx = self.pkg.api.load_mult_library(), self.ctx
         ks = self.pkg.api.KeySlab(*[t.data_ptr() for t in self.kw[:4]])
+        d_offs = self.d_offs if offsets is None else offsets
+        assert str(d_offs.dtype) == "torch.int64" and d_offs.is_cuda and d_offs.numel() == self.nc + 1
         rc = lib.aesw_mult_count_device_form(
-            ctx._h, self.k if k is None else k, self.n_sets, self.nc, self.d_offs.data_ptr(), self.layout if layout is None else layout,
+            ctx._h, self.k if k is None else k, self.n_sets, self.nc, d_offs.data_ptr(), self.layout if layout is None else layout,
             self.wit.x.data_ptr(), self.wit.y.data_ptr(), self.wit.z.data_ptr(), C.byref(ks) if key_slabs else None,
             mult.data_ptr(), report.data_ptr(), ctx._stream(), form)
         assert rc == expect, (rc, ctx._lib.aesw_last_error(ctx._h))
@@ -84,6 +87,23 @@ class Batch:
             hist[c], m = mm.multiplicities(adv[c], sel, ctx._tables)
             misses += m
         return hist, misses
+
+    def parts(self):
+        """(h int64[n, BINS], kh int64[C, BINS]): what every slab block and every key slab looks up, by mult_model's block_histograms
+        and key_histogram over the assembled byte columns and the selectors of the batch as its own offsets cut it."""
+        pkg, ctx = self.pkg, self.ctx
+        adv = ctx.assemble_advice_circuits(self.k, self.n_sets, self.wit, self.kw, self.counts, as_fr=False, layout=self.layout,
+                                           n_blocks=self.n).cpu().numpy()
+        h, kh = np.zeros((self.n, BINS), np.int64), np.zeros((self.nc, BINS), np.int64)
+        for c in range(self.nc):
+            sel, _fixed = pkg.assemble_selectors(self.k, self.n_sets, self.counts[c])
+            places = [pkg.block_placement(self.k, self.n_sets, j) for j in range(self.counts[c])]
+            at = int(self.offs[c])
+            h[at:at + self.counts[c]], misses = mm.block_histograms(adv[c], sel, ctx._tables, places)
+            kh[c], key_misses = mm.key_histogram(adv[c], sel, ctx._tables)
+            assert not misses.any() and key_misses == 0
+        assert h.sum(axis=1).tolist() == [1056] * self.n and kh.sum(axis=1).tolist() == [400] * self.nc
+        return h, kh
 
 
 def untouched(arena, *tensors):
@@ -196,6 +216,126 @@ def test_misses_are_counted_named_and_left_out_of_the_bins(pkg, ctx):
         assert misses == len(case)
         for t, at, *_ in case:
             t[at] ^= 0x40
+
+
+# (K, N): K = 14 / N = 1 holds 10 blocks, K = 13 / N = 2 holds 4 + 6, so that a clamped circuit also crosses a set boundary
+CLAMP_SHAPES = ((14, 1), (13, 2))
+CLAMP_COUNTS = [3, 0, 10, 4, 0, 5]  # n = 22, the offsets 0 3 3 13 17 17 22; slab block 15 is block 2 of circuit 3
+# offsets edited at {index: value}: none; a decreasing pair (circuit 2 counts nothing, circuit 3 from block 2 on: 10 of 15); a
+# count of 14 above the capacity of 10 (blocks 13 ... 16 are counted by nobody); blocks 0 and 1 in front of offsets[0]; blocks 20
+# and 21 behind offsets[C]; block 17 handed to the neighbouring circuit
+CLAMP_EDITS = ({}, {3: 2}, {3: 3}, {0: 2}, {6: 20}, {4: 18, 5: 18})
+CLAMPED_OUT = 2  # the edit of CLAMP_EDITS under which nobody counts slab block 15
+
+
+def offsets_spec(pkg, k, n_sets, o, h, kh):
+    """(hist int64[C, N, BINS], lookups) as include/aesw_mult.h words it: circuit c counts slab blocks o[c] + j for
+    j < min(o[c+1] - o[c], capacity) when o[c+1] > o[c], and none otherwise; block j goes to the set Placement names for j; key
+    slab c always counts into (c, 0)."""
+    cap, nc = pkg.block_capacity(k, n_sets), len(o) - 1
+    hist, blocks = np.zeros((nc, n_sets, BINS), np.int64), 0
+    for c in range(nc):
+        hist[c, 0] += kh[c]
+        for j in range(min(o[c + 1] - o[c], cap) if o[c + 1] > o[c] else 0):
+            hist[c, pkg.block_placement(k, n_sets, j)[0]] += h[o[c] + j]
+            blocks += 1
+    return hist, 400 * nc + 1056 * blocks
+
+
+@pytest.mark.parametrize("layout", mc.LAYOUTS)
+def test_offsets_are_clamped_as_the_header_says(pkg, ctx, layout):
+    """Offsets that no valid counts make: "a count is clamped to aesw_block_capacity(k, n_sets), so the kernel reads only inside
+    each circuit's own range" (include/aesw_mult.h), for both forms.  Every offset is at most n, so every block the specification
+    names lies inside the slabs."""
+    import torch
+    for k, n_sets in CLAMP_SHAPES:
+        cap = pkg.block_capacity(k, n_sets)
+        assert cap == 10 and pkg.block_placement(k, n_sets, 9)[0] == n_sets - 1
+        b = Batch(pkg, ctx, layout, k, n_sets, CLAMP_COUNTS, seed=k + layout)
+        n, nc = b.n, b.nc
+        assert n == 22 and b.offs.tolist() == [0, 3, 3, 13, 17, 17, 22]
+        h, kh = b.parts()
+        lists = []
+        for edit in CLAMP_EDITS:
+            o = [int(v) for v in b.offs]
+            for at, value in edit.items():
+                o[at] = value
+            lists.append(o)
+        rng = np.random.default_rng(1000 * k + layout)
+        for i in range(40):  # anything at all inside [0, n], half of the lists sorted
+            o = rng.integers(0, n + 1, nc + 1).tolist()
+            lists.append(sorted(o) if i % 2 else o)
+        assert any(o[c + 1] < o[c] for o in lists[:6] for c in range(nc)) and any(o[c + 1] - o[c] > cap for o in lists[:6] for c in range(nc))
+
+        def count_all(o, miss=None):
+            """Both forms under the offsets o; miss: None, or (report's first miss, (c, s, bin) one short) or () where nobody counts it"""
+            assert len(o) == nc + 1 and all(0 <= v <= n for v in o), o  # nothing a kernel is told to read lies outside the slabs
+            exp, lookups = offsets_spec(pkg, k, n_sets, o, h, kh)
+            assert int(exp.max()) < min(G.CANARIES)  # no count holds a canary byte: one found in d_mult was left there
+            want = {"lookups": lookups, "misses": 0, "first_miss": None}
+            if miss:
+                exp[miss[1]] -= 1
+                want.update(misses=1, first_miss=miss[0])
+            d_offs = torch.tensor(o, dtype=torch.int64, device="cuda")
+            for canary, form in zip(G.CANARIES, mc.FORMS):
+                got, rep = b.count(G.DeviceArena(canary), form, offsets=d_offs)  # the guards are checked in there
+                same(got, exp, "offsets %s, form %d" % (o, form))
+                assert rep == want, (o, form, rep, want)
+                # no byte of d_mult is left as it was: an empty circuit's histograms are stored or zeroed too
+                assert not (got.astype(np.uint32).view(np.uint8) == canary).any(), (o, form)
+
+        for o in lists:
+            count_all(o)
+
+        # one miss: an S-box output of slab block 15 -- block 2 of circuit 3 as the batch is cut, set 0 in both shapes
+        st = [pkg.column_stride(layout, i) for i in range(3)]
+        row = 37
+        assert pkg.selector_tags()[0][row] == 3 and pkg.block_placement(k, n_sets, 2)[0] == 0
+        at = 15 * st[1] + (int(pkg.packed_index(1)[row]) if layout == mc.PACKED else row)
+        lost = (3, 0, 256 + int(b.wit.x[15 * st[0] + row]))
+        b.wit.y[at] ^= 0x40
+        torch.cuda.synchronize()
+        count_all(lists[0], miss=((15, False, row), lost))
+        count_all(lists[CLAMPED_OUT], miss=())  # clamped out: nobody reads the cell
+        b.wit.y[at] ^= 0x40
+        torch.cuda.synchronize()
+
+
+# K = 12 / N = 1024 / C = 4: 4 096 histograms, 1.09 GB of d_mult.  Zeroing them takes 66 561 workgroups of 1 024 16-byte stores; the
+# DIRECT form launches 65 536 at most, so its zeroing loop takes a second trip.  5 and 7 blocks reach sets 0 ... 2 (1 + 3 + 3 blocks).
+MANY = (12, 1024, [5, 0, 7, 1])
+
+
+def test_more_histograms_than_the_zeroing_grid_has_workgroups(pkg, ctx):
+    import torch
+    k, n_sets, counts = MANY
+    b = Batch(pkg, ctx, mc.PACKED, k, n_sets, counts, seed=4096)
+    nc, words = b.nc, b.nc * n_sets * BINS
+    assert nc * n_sets > 4033 and (words // 4 + 1023) // 1024 == 66561 > 65536
+    h, kh = b.parts()
+    exp = np.zeros((nc, 3, BINS), np.int64)
+    for c in range(nc):
+        exp[c, 0] += kh[c]
+        for j in range(counts[c]):
+            exp[c, pkg.block_placement(k, n_sets, j)[0]] += h[int(b.offs[c]) + j]  # sets 0 ... 2: IndexError otherwise
+    assert exp[2, :, :].sum(axis=1).tolist() == [400 + 1056, 3 * 1056, 3 * 1056]
+    arena = G.DeviceArena()
+    mult = arena.out("mult", words * 4).view(torch.int32).view(nc, n_sets, BINS)  # the one large buffer, used by both forms in turn
+    rep = arena.out("report", 24)
+    word = int.from_bytes(bytes([arena.canary]) * 4, "little", signed=True)
+    kept = []
+    for form in mc.FORMS:
+        assert arena.poisoned_on_device(mult) and arena.poisoned_on_device(rep)
+        b.raw(mult, rep, form)
+        arena.check_on_device()  # synchronises; the guard bands compared on the device
+        assert not bool((mult == word).any()), "form %d left words of d_mult as they were" % form
+        assert not bool(mult[:, 3:].any()), "form %d: a count in a set that holds no block" % form
+        kept.append(mult[:, :3].clone())
+        same(kept[-1].cpu().numpy().astype(np.int64), exp, "form %d" % form)
+        assert pkg.api.mult_report_dict(rep.view(torch.int64)) == {"lookups": 400 * nc + 1056 * b.n, "misses": 0, "first_miss": None}
+        arena.repoison()
+    # equal everywhere: all zero from set 3 on, and the same in sets 0 ... 2
+    assert torch.equal(kept[0], kept[1])
 
 
 def test_a_captured_call_recounts_on_every_replay(pkg, ctx):

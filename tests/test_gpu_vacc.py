@@ -14,7 +14,7 @@ import pytest
 import guarded as G
 import mult_model as mm
 import vacc_cases as vc
-from test_gpu_acc import expected, same, untouched, worlds  # noqa: F401  (the oracle's circuits, computed once, and the fixture)
+from test_gpu_acc import check_many_sets, expected, many_sets_expectation, same, untouched, worlds  # noqa: F401  (the oracle's circuits, computed once, and the fixture)
 from vals_recon import reconstruct
 
 pytestmark = pytest.mark.gpu
@@ -152,7 +152,8 @@ def test_every_cut_of_a_values_circuit_equals_the_model(pkg, worlds, k, n_sets, 
     same(got, exp_blocks, "one buffer")
     assert rep == clean(k, n, key=False), rep
 
-    for chunk in vc.FORCED_CHUNKS:  # several pairs of workgroups add into the same bins
+    # several pairs of workgroups add into the same bins; from LONG_FROM blocks on also chunks longer than one round of the waves
+    for chunk in vc.FORCED_CHUNKS + (vc.LONG_CHUNKS if n >= vc.LONG_FROM else ()):
         a = Acc(c, arenas[1], "_chunk%d" % chunk)
         a.reset(), a.add_key(), a.add(0, n, chunk=chunk)
         got, rep = a.result()
@@ -199,6 +200,22 @@ def test_identical_blocks_count_exactly(pkg, worlds):
     got, rep = a.result()
     same(got, exp, "identical blocks")
     assert rep == clean(k, n)
+
+
+def test_a_circuit_of_1024_sets(pkg, worlds):
+    """n_sets at its bound: runs that start and end deep inside the set index, each add out of pt / y / z views of its own."""
+    ctx, orc = worlds["reference"]
+    k, n_sets = vc.MANY_SETS
+    assert pkg.block_capacity(k, n_sets) == 3070
+    c = Circuit(pkg, ctx, k, n_sets, 16, seed=1024)
+    exp = many_sets_expectation(pkg, orc, c.key, c.pt)
+    a = Acc(c, G.DeviceArena(), "_many")
+    a.reset()
+    at = 0
+    for first, count in vc.MANY_RUNS:
+        a.add(first, count, bufs=c.values(at, count))  # block first + i of a run is entry i of its buffers
+        at += count
+    check_many_sets(a, exp, 16)
 
 
 def rebuilt_expectation(pkg, ctx, c, pt, y, z, kw_np):
