@@ -6,8 +6,9 @@
   halo2-aes_amd/libaesw_<name>.so one library per entry of SATELLITES (the checkers -- circ: many circuits, include/aesw_circ.h;
                                   cols: the assembled advice columns, include/aesw_cols.h; vals: a VALUES witness,
                                   include/aesw_vals.h --, mult: the lookup multiplicities, include/aesw_mult.h, acc: the same
-                                  accumulated chunk by chunk, include/aesw_acc.h, and vacc: accumulated from a VALUES
-                                  witness, include/aesw_vacc.h): its
+                                  accumulated chunk by chunk, include/aesw_acc.h, vacc: accumulated from a VALUES
+                                  witness, include/aesw_vacc.h, and perm: plookup's permuted columns arranged from
+                                  them, include/aesw_perm.h): its
                                   own gfx950 kernels and entry point (hipcc), linked against libaesw.so, whose context it
                                   takes.  All are built by build_satellite() alike.
 
@@ -113,11 +114,12 @@ SATELLITES = {
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),
     "vals": ([CSRC / "vals" / "aesw_vals_check.hip"], [CSRC / "aesw_vals_check.h"], INCLUDE / "aesw_vals.h"),
     "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
+    "perm": ([CSRC / "perm" / "aesw_perm.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_perm.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_perm.h"),
     "vacc": ([CSRC / "vacc" / "aesw_vacc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", CSRC / "aesw_vals_check.h", CSRC / "aesw_vacc.h", INCLUDE / "aesw_mult.h"],
              INCLUDE / "aesw_vacc.h"),
     "mult": ([CSRC / "mult" / "aesw_mult.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h"], INCLUDE / "aesw_mult.h"),
 }
-CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, VACC_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
+CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, PERM_LIB, VACC_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
 
 
 def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:

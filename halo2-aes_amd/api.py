@@ -24,6 +24,7 @@ VALS_LIB_PATH = _PKG / "libaesw_vals.so"  # the checker of a VALUES witness (inc
 MULT_LIB_PATH = _PKG / "libaesw_mult.so"  # the lookup multiplicities of a many-circuit batch (include/aesw_mult.h), next to libaesw.so
 ACC_LIB_PATH = _PKG / "libaesw_acc.so"    # the lookup multiplicities of one circuit, accumulated chunk by chunk (include/aesw_acc.h)
 VACC_LIB_PATH = _PKG / "libaesw_vacc.so"  # the same accumulated from a VALUES witness (include/aesw_vacc.h)
+PERM_LIB_PATH = _PKG / "libaesw_perm.so"  # plookup's permuted columns arranged from the multiplicities (include/aesw_perm.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -228,6 +229,13 @@ VACC_SYMBOLS = {
     "aesw_vacc_prepare": (_I, [_P]),
 }
 
+# include/aesw_perm.h
+PERM_SYMBOLS = {
+    "aesw_perm_workspace_bytes": (C.c_size_t, [_U32]),
+    "aesw_perm_build_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P]),
+    "aesw_perm_gather_fr_device": (_I, [_P, _U64, _P, _P, _P, _P]),
+}
+
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 _NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
 # the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT)
@@ -240,6 +248,7 @@ _LIBRARIES = {
     "mult": (MULT_LIB_PATH, MULT_SYMBOLS, _NO_FALLBACK),
     "acc": (ACC_LIB_PATH, ACC_SYMBOLS, _NO_FALLBACK),
     "vacc": (VACC_LIB_PATH, VACC_SYMBOLS, _NO_FALLBACK),
+    "perm": (PERM_LIB_PATH, PERM_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -315,6 +324,11 @@ def load_vacc_library(path: Path | None = None) -> C.CDLL:
     return _load("vacc", path)
 
 
+def load_perm_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_perm.so (in-tree): plookup's permuted columns behind Context.permuted_columns and Context.gather_fr."""
+    return _load("perm", path)
+
+
 def mult_bin(tag: int, x: int, y: int = 0):
     """aesw_mult_bin: the table row the input operands of a lookup name (None for tag 0 and for anything that is no tag)."""
     b = int(load_mult_library().aesw_mult_bin(tag, x, y))
@@ -381,6 +395,13 @@ def mult_report_dict(rep) -> dict:
     v = _words(rep)
     first = None if v[2] == _NONE else (v[2] >> 20, bool((v[2] >> 19) & 1), v[2] & 0xFFFF)
     return {"lookups": v[0], "misses": v[1], "first_miss": first}
+
+
+def perm_report_dict(rep) -> dict:
+    """The uint64[3] report tensor of Context.permuted_columns(sync=False), read back, as the dict sync=True returns: arguments,
+    overflowed and first_overflow = None or (set, tag)."""
+    v = _words(rep)
+    return {"arguments": v[0], "overflowed": v[1], "first_overflow": None if v[2] == _NONE else (v[2] >> 3, v[2] & 7)}
 
 
 def _ptr(x):
@@ -1031,6 +1052,60 @@ class Context:
         self._check(rc, "aesw_mult_count_device")
         return _out, self._report(rep, sync, mult_report_dict)
 
+    def permuted_columns(self, k: int, n_sets: int, mult, n_rows: int | None = None, pad_row: int = 0, sync: bool = True, _out=None):
+        """plookup's permuted columns of the 5 * n_sets lookup arguments of one circuit, arranged from its lookup multiplicities
+        (aesw_perm_build_device, libaesw_perm.so): (a, s, report) with a and s int32 [n_sets, 5, 2^k] tensors of table-row
+        indices in the row order of lookup_table() -- argument (set, tag) at [set, tag - 1], A' and S' -- of which rows
+        0 ... n_rows - 1 are written (n_rows: the usable rows, default 2^k; the rest is the host's blinding rows).  mult: the
+        int32 [n_sets, 66561] histograms of lookup_multiplicities (one circuit) or MultiplicityAccumulator.histograms();
+        pad_row: the table row the table columns hold below row 66 560.  report: the dict of perm_report_dict after synchronising
+        the stream, or with sync=False the uint64[3] device tensor.  The call owns its workspace; _out is an (a, s) pair of
+        such tensors to write into (tests, tools)."""
+        lib = load_perm_library()
+        torch = self._torch()
+        k, n_sets = int(k), int(n_sets)
+        if not isinstance(mult, torch.Tensor) or mult.dtype != torch.int32 or not mult.is_cuda or mult.device.index != self.device:
+            raise TypeError("mult must be an int32 tensor on cuda:%d" % self.device)
+        if tuple(mult.shape) == (1, n_sets, K.TABLE_ROWS):
+            mult = mult[0]
+        if tuple(mult.shape) != (n_sets, K.TABLE_ROWS) or not mult.is_contiguous():
+            raise ValueError("mult must be a contiguous int32 tensor of shape %r" % ((n_sets, K.TABLE_ROWS),))
+        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 else (0,)
+        if _out is None:
+            _out = (torch.empty(shape, dtype=torch.int32, device=self._dev()), torch.empty(shape, dtype=torch.int32, device=self._dev()))
+        for t in _out:
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
+                raise ValueError("_out must be two contiguous int32 tensors of shape %r" % (shape,))
+        # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
+        ws = torch.empty(max(int(lib.aesw_perm_workspace_bytes(n_sets)), 16), dtype=torch.uint8, device=self._dev())
+        rep = torch.empty(3, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_perm_build_device(self._h, k, n_sets, (1 << k) if n_rows is None else int(n_rows), int(pad_row), mult.data_ptr(),
+                                        _out[0].data_ptr(), _out[1].data_ptr(), ws.data_ptr(), rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_perm_build_device")
+        return _out[0], _out[1], self._report(rep, sync, perm_report_dict)
+
+    def gather_fr(self, index, table_fr, out=None):
+        """int32 table-row indices (any shape; a column of permuted_columns) -> [..., 32] uint8 cells: table_fr[index]
+        (aesw_perm_gather_fr_device).  table_fr: uint8 [66561, 32], the host's compressed table; an index outside the table gives
+        a cell of zeros."""
+        lib = load_perm_library()
+        torch = self._torch()
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or not index.is_cuda or index.device.index != self.device:
+            raise TypeError("index must be an int32 tensor on cuda:%d" % self.device)
+        if not index.is_contiguous():
+            raise ValueError("index must be contiguous")
+        table_fr = self._u8(table_fr, "table_fr")
+        if tuple(table_fr.shape) != (K.TABLE_ROWS, 32):
+            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((K.TABLE_ROWS, 32),))
+        n = index.numel()
+        if out is None:
+            out = torch.empty(tuple(index.shape) + (32,), dtype=torch.uint8, device=self._dev())
+        elif self._u8(out, "out").numel() != n * 32:
+            raise ValueError("out must hold 32 bytes per index")
+        rc = lib.aesw_perm_gather_fr_device(self._h, n, index.data_ptr(), table_fr.data_ptr(), out.data_ptr(), self._stream())
+        self._check(rc, "aesw_perm_gather_fr_device")
+        return out
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1304,6 +1379,10 @@ class MultiplicityAccumulator:
         """The int32 [n_sets, 66561] device tensor every call adds to (not a copy; nothing is synchronised)."""
         return self._mult
 
+    def permuted_columns(self, n_rows: int | None = None, pad_row: int = 0, sync: bool = True):
+        """Context.permuted_columns over these histograms as they stand on the current stream."""
+        return self.ctx.permuted_columns(self.k, self.n_sets, self._mult, n_rows, pad_row, sync)
+
     def report(self, sync: bool = True):
         """The dict of mult_report_dict over everything added since reset() -- a block's unit is its index in the circuit, the
         key slab's 0 -- after synchronising the stream; with sync=False the uint64[3] device tensor."""
@@ -1359,7 +1438,7 @@ class Group(Context):
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
               "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values",
-              "lookup_multiplicities", "multiplicity_accumulator"):
+              "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
