@@ -113,9 +113,10 @@ SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),
     "vals": ([CSRC / "vals" / "aesw_vals_check.hip"], [CSRC / "aesw_vals_check.h"], INCLUDE / "aesw_vals.h"),
-    "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
+    "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", CSRC / "aesw_run.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
     "perm": ([CSRC / "perm" / "aesw_perm.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_perm.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_perm.h"),
-    "vacc": ([CSRC / "vacc" / "aesw_vacc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", CSRC / "aesw_vals_check.h", CSRC / "aesw_vacc.h", INCLUDE / "aesw_mult.h"],
+    "vacc": ([CSRC / "vacc" / "aesw_vacc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", CSRC / "aesw_run.h", CSRC / "aesw_vals_check.h", CSRC / "aesw_vacc.h",
+              INCLUDE / "aesw_mult.h"],
              INCLUDE / "aesw_vacc.h"),
     "mult": ([CSRC / "mult" / "aesw_mult.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h"], INCLUDE / "aesw_mult.h"),
 }

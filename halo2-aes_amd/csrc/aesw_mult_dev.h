@@ -1,14 +1,18 @@
 // aesw_mult_dev.h -- the wave-level core of counting lookup multiplicities, one source for the kernels of libaesw_mult.so
-// (mult/aesw_mult.hip) and of libaesw_acc.so (acc/aesw_acc.hip).  aesw_mult.h holds the rule (bins, hits, the sizes of the
-// counter split); aesw_check_dev.h how a slab travels (Staged) and how a wave synchronises on its LDS image.  This header holds
-// what counts a staged unit: a lane's findings, a row of the check table as the walk reads it, the two sinks a hit goes to (a
-// global atomic add; the workgroup's LDS counters, and with them which workgroup of a pair owns which bin), the staging of a
-// block and the 22 rows a lane keeps of it, the key slab of one wave, the workgroup's report and the wave count that fits next
-// to the counters.  A kernel adds its prologue and its staging loop -- which blocks, which unit numbers -- and what becomes
-// of the counters.  The loop over the blocks and the zeroing body stay in the kernels: moved into a function here, the same
-// statements compile to other code ("Shared machinery").  Device code only: include from a HIP translation unit.
+// (mult/aesw_mult.hip), libaesw_acc.so (acc/aesw_acc.hip) and libaesw_vacc.so (vacc/aesw_vacc.hip).  aesw_mult.h holds the rule
+// (bins, hits, the sizes of the counter split); aesw_check_dev.h how a slab travels (Staged) and how a wave synchronises on its
+// LDS image.  This header holds what counts a staged unit: a lane's findings, a row of the check table as the walk reads it, the
+// two sinks a hit goes to (a global atomic add; the workgroup's LDS counters, and with them which workgroup of a pair owns
+// which bin), the staging of a block and the 22 rows a lane keeps of it, the key slab of one wave, the workgroup's report and
+// the wave count that fits next to the counters; the add flush of both accumulators (flush_add, flush_pair_add); and the body
+// that zeroes histograms and resets a report (zero_and_reset: a library's kernel of its own name wraps it; a __global__ here
+// would be a kernel of every library that includes this).  A kernel adds its prologue and its staging loop -- which blocks,
+// which unit numbers: that loop stays in the kernels ("Shared machinery").  Device code, and behind it the host
+// lines the entry points of the two accumulators share (refuse, bad_outputs): include from a HIP translation unit.
 #pragma once
+#include "../../include/aesw_mult.h"
 #include "aesw_check_dev.h"
+#include "aesw_ctx.h"
 #include "aesw_mult.h"
 
 namespace aesw {
@@ -140,6 +144,51 @@ struct CounterGeo {
     static constexpr int WAVES = (LDS - FIXED) / ChkLayout<LAYOUT>::BI >= 8 ? 8 : (LDS - FIXED) / ChkLayout<LAYOUT>::BI;
     static_assert(WAVES >= 4, "a workgroup of at least four waves");
 };
+
+// `threads` below: the kernel's blockDim.x, read in the kernel (read in a function here it is loaded the long way round).
+// `n` counters added to out[0 .. n): lane i of an instruction adds word i of 64 consecutive ones; zeros are skipped.
+__device__ __forceinline__ void flush_add(uint32_t *out, const uint32_t *cnt, uint32_t n, uint32_t threads) {
+    for (uint32_t i = threadIdx.x; i < n; i += threads) {
+        const uint32_t v = cnt[i];
+        if (v) atomicAdd(out + i, v);
+    }
+}
+// The bins `half` of a pair owns, added to the histogram `out` of its set, after __syncthreads(); half 0 reports.
+// (The ranges are aesw_mult.h's, taken as constants: the Xor range of half 1 lies a constant stride behind half 0's.)
+__device__ __forceinline__ void flush_pair_add(uint32_t *out, const uint32_t *cnt, uint32_t half, uint64_t *report, const unsigned long long *rep, uint32_t threads) {
+    constexpr MultFlushRange xr = mult_flush_range(0, 0), xr1 = mult_flush_range(1, 0), low = mult_flush_range(0, 1), high = mult_flush_range(0, 2);
+    static_assert(xr1.counter == xr.counter && xr1.length == xr.length, "the two Xor halves differ in their first bin alone");
+    flush_add(out + xr.bin + half * (xr1.bin - xr.bin), cnt + xr.counter, xr.length, threads);
+    if (half == 0) {
+        flush_add(out + low.bin, cnt + low.counter, low.length, threads);
+        flush_add(out + high.bin, cnt + high.counter, high.length, threads);
+        rep_flush(report, rep);
+    }
+}
+
+// `words` histogram words to zero and the report to (0 lookups, 0 misses, no miss), by a whole grid: the body of a kernel node,
+// not memset nodes, so that a captured graph replays it as it runs eagerly.
+__device__ __forceinline__ void zero_and_reset(uint32_t *mult, uint64_t words, uint64_t *report, uint32_t threads) {
+    const uint64_t tid = (uint64_t)blockIdx.x * threads + threadIdx.x, n = (uint64_t)gridDim.x * threads;
+    if (tid < 3) report[tid] = tid == 2 ? ~0ull : 0ull;
+    const u32x4 zero = {0, 0, 0, 0};
+    for (uint64_t i = tid; i < words / 4; i += n) reinterpret_cast<u32x4 *>(mult)[i] = zero;
+    if (tid < words % 4) mult[words - 1 - tid] = 0;
+}
+
+// Host: what the entry points of the two accumulators share.
+inline int refuse(aesw_ctx *ctx, const char *call, const char *why, int status = AESW_ERR_INVALID_ARG) {
+    if (ctx) ctx->last_error = std::string(call) + ": " + why;
+    return status;
+}
+// what every call checks of its outputs and of the circuit's shape (with_k: the call takes a k)
+inline const char *bad_outputs(uint32_t k, bool with_k, uint32_t n_sets, const uint32_t *d_mult, const aesw_mult_report *d_report) {
+    if (with_k && !mult_k_ok(k)) return "k must be 2 ... 30";
+    if (!mult_sets_ok(n_sets)) return "n_sets must be 1 ... 1024";
+    if (!d_report || !aligned_to(d_report, 8)) return "d_report must be there and 8-byte aligned";
+    if (!d_mult || !aligned_to(d_mult, 16)) return "d_mult must be there and 16-byte aligned";
+    return nullptr;
+}
 
 }  // namespace multdev
 }  // namespace aesw

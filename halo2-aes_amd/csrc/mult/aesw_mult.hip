@@ -3,7 +3,7 @@
 // itself holds the sources of libaesw.so.)  The bin rule and the sizes of the counter split are aesw_mult.h's, the set of a
 // block Placement's, and the counting of a staged unit -- row entries, the sinks (and with the LDS one which workgroup of a
 // pair owns which bin), block staging, the key slab of a wave, the workgroup's report, the wave count next to the LDS counters
-// -- aesw_mult_dev.h's, shared with libaesw_acc.so.  What is here is what a workgroup counts and what becomes of its counts, in
+// -- aesw_mult_dev.h's, shared with libaesw_acc.so and libaesw_vacc.so.  What is here is what a workgroup counts and what becomes of its counts, in
 // two forms that give the same bytes:
 //   * DIRECT: d_mult is zeroed by a launch of its own; workgroups of four waves share a circuit's blocks, and every hit is one
 //     global atomic add into the histogram of the block's set;
@@ -143,14 +143,10 @@ __global__ void __launch_bounds__(CounterGeo<LAYOUT>::WAVES * LANES) mult_privat
     }
 }
 
-// The report starts as (0 lookups, 0 misses, no miss), and for the DIRECT form d_mult as zeros: a kernel node, not memset nodes,
-// so a captured graph replays it as it runs eagerly.  words == 0: the report alone.
+// The report starts as (0 lookups, 0 misses, no miss), and for the DIRECT form d_mult as zeros (zero_and_reset under this
+// library's name).  words == 0: the report alone.
 __global__ void __launch_bounds__(256) mult_init_kernel(uint32_t *mult, uint64_t words, uint64_t *report) {
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, n = (uint64_t)gridDim.x * blockDim.x;
-    if (tid < 3) report[tid] = tid == 2 ? ~0ull : 0ull;
-    const u32x4 zero = {0, 0, 0, 0};
-    for (uint64_t i = tid; i < words / 4; i += n) reinterpret_cast<u32x4 *>(mult)[i] = zero;
-    if (tid < words % 4) mult[words - 1 - tid] = 0;
+    zero_and_reset(mult, words, report, blockDim.x);
 }
 
 static hipError_t launch_count(const MultParams &p0, bool dense, int form, hipStream_t s) {

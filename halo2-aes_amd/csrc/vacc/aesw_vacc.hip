@@ -1,12 +1,13 @@
 // vacc/aesw_vacc.hip -- libaesw_vacc.so (include/aesw_vacc.h): the lookups of a run of ONE circuit's blocks, given as a VALUES
 // witness, added to the histograms of libaesw_acc.so.  The bin rule and the counter split are aesw_mult.h's, the
-// set of a block Placement's, the counting of a row, the sinks, the findings and the workgroup's report aesw_mult_dev.h's, and
-// which cell an operand of a lookup is aesw_vals_check.h's, rebased onto the image of aesw_vacc.h.  What is here:
+// set of a block Placement's, the run -- its pieces, its chunks, the grid, the default chunk -- aesw_run.h's, the counting of a
+// row, the sinks, the findings, the workgroup's report, the add flush of a pair and the checks of the outputs aesw_mult_dev.h's,
+// and which cell an operand of a lookup is aesw_vals_check.h's, rebased onto the image of aesw_vacc.h.  What is here:
 //   * vacc_count_kernel: acc_add_kernel's division of labour -- the run cut at the set boundaries, every piece into chunks, a
 //     pair of workgroups per chunk, each counting the bins of its half in LDS and ADDING them to the histogram of the set -- over
 //     a block's 448 y + 608 z + 16 plaintext bytes and the circuit's 176 round-key cells: 17 row steps per lane, no x column;
 //   * the table, in the code object's own storage, filled once per device;
-//   * the entry points: their checks, the pieces of a run, the default chunk, the launch.
+//   * the entry points: their checks and the launch.
 // The reset and the key slab's own 400 rows are libaesw_acc.so's (the key slabs of VALUES are the packed ones): nothing of them
 // is restated here.
 #include <hip/hip_runtime.h>
@@ -18,7 +19,7 @@
 #include "../../../include/aesw_vacc.h"
 #include "../aesw_ctx.h"
 #include "../aesw_mult_dev.h"
-#include "../aesw_placement.h"
+#include "../aesw_run.h"
 #include "../aesw_vacc.h"
 
 namespace aesw_vacc {
@@ -41,22 +42,11 @@ struct RunParams {
     const uint8_t *tab768;      // sbox | mul2 | mul3
     uint32_t *mult;             // [n_sets][MULT_BINS]
     uint64_t *report;           // aesw_mult_report as 3 x u64
-    Placement place;
-    uint64_t first, end;
-    uint32_t set0;              // the set of block `first`: blockIdx.y counts the pieces from it
-    uint32_t chunk;             // blocks per pair of workgroups
+    Run run;
 };
 
 // The table of this library, one copy per device, filled by ensure_table().
 __device__ uint32_t g_vacc_table[VACC_WORDS];
-
-// `n` counters added to out[0 .. n): lane i of an instruction adds word i of 64 consecutive ones; zeros are skipped (4.16's flush).
-__device__ __forceinline__ void flush_add(uint32_t *out, const uint32_t *cnt, uint32_t n) {
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint32_t v = cnt[i];
-        if (v) atomicAdd(out + i, v);
-    }
-}
 
 // A block on its way into the wave's image: y and z as 16-byte units, the plaintext as one 16-byte load of lane 0.
 struct ValuesStage {
@@ -102,13 +92,8 @@ __global__ void __launch_bounds__(WAVES * LANES) vacc_count_kernel(const RunPara
     __shared__ __attribute__((aligned(16))) uint8_t s_img[WAVES * VACC_IMG];
     __shared__ uint32_t s_t768[768 / 4];
     __shared__ unsigned long long s_rep[3];
-    const uint32_t half = blockIdx.x & 1u, set = a.set0 + blockIdx.y;
-    // the piece: the run's blocks in this set; the chunk: `chunk` of them (fewer at the piece's end)
-    const uint64_t s_lo = a.place.first_block(set), s_hi = s_lo + a.place.capacity(set);
-    const uint64_t lo = a.first > s_lo ? a.first : s_lo, hi = a.end < s_hi ? a.end : s_hi;
-    const uint64_t b0 = lo + (uint64_t)(blockIdx.x >> 1) * a.chunk;
-    if (b0 >= hi) return;  // the whole workgroup: a shorter piece than the longest one
-    const uint64_t cnt = hi - b0 < a.chunk ? hi - b0 : a.chunk;
+    const auto [half, set, b0, cnt] = a.run.chunk_at(blockIdx.x, blockIdx.y);
+    if (cnt == 0) return;  // the whole workgroup: a shorter piece than the longest one
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / LANES), lane = threadIdx.x % LANES;
     const uint8_t *t768 = reinterpret_cast<const uint8_t *>(s_t768);
     uint8_t *img = s_img + wave * VACC_IMG;
@@ -127,11 +112,11 @@ __global__ void __launch_bounds__(WAVES * LANES) vacc_count_kernel(const RunPara
     LdsSink sink{s_cnt, half};
     Findings acc;
     ValuesStage st;
-    if (wave < cnt) st.load(a, b0 + wave - a.first, lane);
+    if (wave < cnt) st.load(a, b0 + wave - a.run.first, lane);
     for (uint64_t i = wave; i < cnt; i += WAVES) {
         st.store(img, lane);
         wave_lds_sync();
-        if (i + WAVES < cnt) st.load(a, b0 + i + WAVES - a.first, lane);  // in flight while this block is counted
+        if (i + WAVES < cnt) st.load(a, b0 + i + WAVES - a.run.first, lane);  // in flight while this block is counted
         rows.count(img, t768, b0 + i, lane, sink, acc);
         wave_lds_sync();  // the next block overwrites the image
     }
@@ -140,29 +125,7 @@ __global__ void __launch_bounds__(WAVES * LANES) vacc_count_kernel(const RunPara
         rep_collect(s_rep, acc);
     }
     __syncthreads();
-    // the bins this workgroup owns, added to the set's histogram
-    uint32_t *const out = a.mult + (uint64_t)set * MULT_BINS;
-    constexpr MultFlushRange xr = mult_flush_range(0, 0), xr1 = mult_flush_range(1, 0), low = mult_flush_range(0, 1), high = mult_flush_range(0, 2);
-    static_assert(xr1.counter == xr.counter && xr1.length == xr.length, "the two Xor halves differ in their first bin alone");
-    flush_add(out + xr.bin + half * (xr1.bin - xr.bin), s_cnt + xr.counter, xr.length);
-    if (half == 0) {
-        flush_add(out + low.bin, s_cnt + low.counter, low.length);
-        flush_add(out + high.bin, s_cnt + high.counter, high.length);
-        rep_flush(a.report, s_rep);
-    }
-}
-
-// The default chunk is 4.16's rule: the flush a chunk amortises is the same 65 536 + 1 024 words, and tests/test_vacc_library.py
-// holds the two rules equal.
-constexpr uint64_t MIN_CHUNK = 256, TARGET_PAIRS = 128, MAX_PAIRS_PER_SET = 1ull << 22;
-static uint32_t default_chunk(uint64_t n_blocks) {
-    const uint64_t spread = (n_blocks + TARGET_PAIRS - 1) / TARGET_PAIRS;  // n_blocks < 2^30: it fits
-    return (uint32_t)(spread < MIN_CHUNK ? MIN_CHUNK : spread);
-}
-
-static int refuse(aesw_ctx *ctx, const char *call, const char *why, int status = AESW_ERR_INVALID_ARG) {
-    if (ctx) ctx->last_error = std::string(call) + ": " + why;
-    return status;
+    flush_pair_add(a.mult + (uint64_t)set * MULT_BINS, s_cnt, half, a.report, s_rep, blockDim.x);
 }
 
 // The table lives in the code object's own storage: nothing to allocate, nothing to free.  It is filled once per
@@ -205,10 +168,7 @@ int aesw_vacc_add_device_chunk(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint6
     const char *const call = "aesw_vacc_add_device";
     if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
     if (!ctx) return AESW_ERR_INVALID_ARG;
-    if (!mult_k_ok(k)) return refuse(ctx, call, "k must be 2 ... 30");
-    if (!mult_sets_ok(n_sets)) return refuse(ctx, call, "n_sets must be 1 ... 1024");
-    if (!d_report || !aligned_to(d_report, 8)) return refuse(ctx, call, "d_report must be there and 8-byte aligned");
-    if (!d_mult || !aligned_to(d_mult, 16)) return refuse(ctx, call, "d_mult must be there and 16-byte aligned");
+    if (const char *why = bad_outputs(k, true, n_sets, d_mult, d_report)) return refuse(ctx, call, why);
     const Placement place(k);
     const uint64_t cap = place.total(n_sets);
     if (first_block > cap || n_blocks > cap - first_block)
@@ -225,29 +185,14 @@ int aesw_vacc_add_device_chunk(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint6
     p.tab768 = ctx->d_tables;
     p.mult = d_mult;
     p.report = reinterpret_cast<uint64_t *>(d_report);
-    p.place = place;
-    p.first = first_block;
-    p.end = first_block + n_blocks;
-    p.chunk = blocks_per_workgroup ? blocks_per_workgroup : default_chunk(n_blocks);
-    // the pieces: one per set from the first block's to the last block's; the longest one decides the grid's width
-    uint32_t set1;
-    uint64_t bi;
-    place.locate<uint64_t>(first_block, p.set0, bi);
-    place.locate<uint64_t>(p.end - 1, set1, bi);
-    const auto piece = [&](uint32_t s) {
-        const uint64_t s_lo = place.first_block(s), s_hi = s_lo + place.capacity(s);
-        return (p.end < s_hi ? p.end : s_hi) - (p.first > s_lo ? p.first : s_lo);
-    };
-    uint64_t longest = piece(p.set0);
-    if (set1 > p.set0 && piece(set1) > longest) longest = piece(set1);
-    if (set1 > p.set0 + 1 && piece(p.set0 + 1) > longest) longest = piece(p.set0 + 1);  // every piece between the two is a whole set
-    const uint64_t pairs = (longest + p.chunk - 1) / p.chunk;
-    if (pairs > MAX_PAIRS_PER_SET) return refuse(ctx, call, "blocks_per_workgroup leaves more than 2^22 chunks in one set");
+    const RunPlan plan = run_plan(place, first_block, n_blocks, blocks_per_workgroup);
+    if (!plan.fits()) return refuse(ctx, call, "blocks_per_workgroup leaves more than 2^22 chunks in one set");
+    p.run = plan.run;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     const int rc = ensure_table(ctx, &p.table);
     if (rc != AESW_OK) return rc;
-    const dim3 grid((unsigned)(2 * pairs), set1 - p.set0 + 1);
+    const dim3 grid((unsigned)(2 * plan.pairs), plan.pieces);
     hipLaunchKernelGGL(vacc_count_kernel, grid, dim3(WAVES * LANES), 0, reinterpret_cast<hipStream_t>(stream), p);
     HIP_TRY(ctx, hipGetLastError());
     return AESW_OK;
@@ -259,7 +204,7 @@ int aesw_vacc_add_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_t fi
 }
 
 uint32_t aesw_vacc_default_chunk(uint32_t /*k*/, uint32_t /*n_sets*/, uint64_t /*first_block*/, uint64_t n_blocks) {
-    return aesw_vacc::default_chunk(n_blocks);
+    return aesw::run_default_chunk(n_blocks);
 }
 
 int aesw_vacc_prepare(aesw_ctx *ctx) {
