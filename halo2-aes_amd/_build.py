@@ -11,6 +11,8 @@
                                   them, include/aesw_perm.h): its
                                   own gfx950 kernels and entry point (hipcc), linked against libaesw.so, whose context it
                                   takes.  All are built by build_satellite() alike.
+  halo2-aes_amd/libaesw_theta.so  the one entry of FIELD_LIBRARIES: the lookup arguments compressed under theta
+                                  (include/aesw_theta.h), built by build_satellite() as well
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -122,11 +124,21 @@ SATELLITES = {
 }
 CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, PERM_LIB, VACC_LIB, MULT_LIB = (PKG / ("libaesw_%s.so" % name) for name in SATELLITES)
 
+# The libraries that do field arithmetic (csrc/aesw_fr.h), entries of the same shape.  A table of their own: SATELLITES is the
+# seven libraries that move bytes and row indices and never touch Fr -- its length, its order and the tuple unpacked below it
+# are held by the library tests of its entries -- while what follows theta (the compression here, the grand product next)
+# shares the field header and grows here.  build_satellite() looks a name up in either; __graft_entry__.build() walks both.
+FIELD_LIBRARIES = {
+    "theta": ([CSRC / "theta" / "aesw_theta.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_theta.h", CSRC / "aesw_mult.h", INCLUDE / "aesw_mult.h"],
+              INCLUDE / "aesw_theta.h"),
+}
+THETA_LIB = PKG / "libaesw_theta.so"
+
 
 def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
-    """libaesw_<name>.so: a checker's kernels and its entry point (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
+    """libaesw_<name>.so of an entry of SATELLITES or FIELD_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
     A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are.  With `extra_flags` and
     another `out` (a file name next to libaesw.so) a measurement variant of it (tools/vacc_bench.py: -DAESW_VACC_WAVES=16)."""
-    sources, headers, public = SATELLITES[name]
+    sources, headers, public = SATELLITES[name] if name in SATELLITES else FIELD_LIBRARIES[name]
     return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
                   lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)

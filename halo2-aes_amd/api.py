@@ -25,6 +25,7 @@ MULT_LIB_PATH = _PKG / "libaesw_mult.so"  # the lookup multiplicities of a many-
 ACC_LIB_PATH = _PKG / "libaesw_acc.so"    # the lookup multiplicities of one circuit, accumulated chunk by chunk (include/aesw_acc.h)
 VACC_LIB_PATH = _PKG / "libaesw_vacc.so"  # the same accumulated from a VALUES witness (include/aesw_vacc.h)
 PERM_LIB_PATH = _PKG / "libaesw_perm.so"  # plookup's permuted columns arranged from the multiplicities (include/aesw_perm.h)
+THETA_LIB_PATH = _PKG / "libaesw_theta.so"  # the lookup arguments compressed under theta (include/aesw_theta.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -236,6 +237,15 @@ PERM_SYMBOLS = {
     "aesw_perm_gather_fr_device": (_I, [_P, _U64, _P, _P, _P, _P]),
 }
 
+# include/aesw_theta.h
+THETA_SYMBOLS = {
+    "aesw_theta_compress_table_device": (_I, [_P, _P, _P, _P, _P]),
+    "aesw_theta_inputs_device": (_I, [_P, _U32, _U32, _U64, _I, _P, _P, _P, C.POINTER(KeySlab), _P, _P, _P]),
+    "aesw_theta_prepare": (_I, [_P, _U32, _U32, _P]),
+    "aesw_theta_columns_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _P]),
+}
+FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
+
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 _NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
 # the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT)
@@ -249,6 +259,7 @@ _LIBRARIES = {
     "acc": (ACC_LIB_PATH, ACC_SYMBOLS, _NO_FALLBACK),
     "vacc": (VACC_LIB_PATH, VACC_SYMBOLS, _NO_FALLBACK),
     "perm": (PERM_LIB_PATH, PERM_SYMBOLS, _NO_FALLBACK),
+    "theta": (THETA_LIB_PATH, THETA_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -329,6 +340,17 @@ def load_perm_library(path: Path | None = None) -> C.CDLL:
     return _load("perm", path)
 
 
+def load_theta_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_theta.so (in-tree): the compression under theta behind Context.compress_table, Context.lookup_inputs and
+    Context.argument_columns."""
+    return _load("theta", path)
+
+
+def fr_cell(value: int) -> np.ndarray:
+    """uint8[32]: the Fr cell of `value` (any int, reduced mod r) -- value * 2^256 mod r, little-endian."""
+    return np.frombuffer(((int(value) % FR_MODULUS << 256) % FR_MODULUS).to_bytes(32, "little"), np.uint8).copy()
+
+
 def mult_bin(tag: int, x: int, y: int = 0):
     """aesw_mult_bin: the table row the input operands of a lookup name (None for tag 0 and for anything that is no tag)."""
     b = int(load_mult_library().aesw_mult_bin(tag, x, y))
@@ -395,6 +417,12 @@ def mult_report_dict(rep) -> dict:
     v = _words(rep)
     first = None if v[2] == _NONE else (v[2] >> 20, bool((v[2] >> 19) & 1), v[2] & 0xFFFF)
     return {"lookups": v[0], "misses": v[1], "first_miss": first}
+
+
+def theta_report_dict(rep) -> dict:
+    """The uint64[2] report tensor of Context.compress_table(sync=False), read back, as the dict sync=True returns."""
+    v = _words(rep)
+    return {"cells": v[0], "noncanonical": bool(v[1])}
 
 
 def perm_report_dict(rep) -> dict:
@@ -1106,6 +1134,93 @@ class Context:
         self._check(rc, "aesw_perm_gather_fr_device")
         return out
 
+    def compress_table(self, theta, sync: bool = True, _out=None):
+        """The three compressed tables under theta (aesw_theta_compress_table_device, libaesw_theta.so): (table_fr, report) with
+        table_fr a uint8 [3, 66561, 32] tensor -- table j compresses the first j + 2 of (tag, a, b, c) of every row of
+        lookup_table(), acc = acc * theta + e -- and report the dict of theta_report_dict after synchronising the stream, or with
+        sync=False the uint64[2] device tensor.  theta: an int (reduced mod r and put into Montgomery form here), or a uint8[32]
+        tensor on the device holding the cell as it lies, which is read when the kernel runs; if it is not canonical every cell
+        is zero and the report says so.  _out is a tensor to write into (tests, tools)."""
+        lib = load_theta_library()
+        torch = self._torch()
+        if isinstance(theta, int):
+            theta = torch.from_numpy(fr_cell(theta)).to(self._dev())
+        if tuple(self._u8(theta, "theta").shape) != (32,):
+            raise ValueError("theta must be an int or a uint8[32] tensor")
+        shape = (3, K.TABLE_ROWS, 32)
+        if _out is None:
+            _out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(_out, "_out").shape) != shape:
+            raise ValueError("_out must be a uint8 tensor of shape %r" % (shape,))
+        rep = torch.empty(2, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_theta_compress_table_device(self._h, theta.data_ptr(), _out.data_ptr(), rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_theta_compress_table_device")
+        return _out, self._report(rep, sync, theta_report_dict)
+
+    def lookup_inputs(self, k: int, n_sets: int, witness: Witness, key_witness: KeyWitness | None, n_blocks: int | None = None,
+                      layout: int = K.LAYOUT_PACKED, sync: bool = True, _out=None):
+        """The compressed input columns of one circuit in row order, as table-row indices (aesw_theta_inputs_device): (index,
+        report) with index an int32 [n_sets, 5, 2^k] tensor -- argument (set, tag) at [set, tag - 1]; the bin of the row's lookup,
+        -1 (0xffffffff) for a miss, 66560 (the all-zero row) wherever the argument's selector is off -- and report the dict of
+        mult_report_dict after synchronising the stream, or with sync=False the uint64[3] device tensor.  The circuit is the first
+        n_blocks blocks of `witness` (default: all it holds) and the key slab `key_witness` (None: no key lookups).  _out is a
+        tensor to write into (tests, tools).  Under torch.cuda.graph the library cannot allocate the report's workspace: call
+        prepare_lookup_inputs(k, n_sets, stream) with the capturing stream first."""
+        lib = load_theta_library()
+        torch = self._torch()
+        k, n_sets = int(k), int(n_sets)
+        stride = column_stride(layout, 1)
+        if n_blocks is None:
+            n_blocks = int(witness.y.numel()) // stride if stride else 0
+        for i, t in enumerate(witness[:3]):
+            if int(self._u8(t, "witness").numel()) < n_blocks * column_stride(layout, i):
+                raise ValueError("witness holds fewer than n_blocks blocks")
+        ks = self._key_slabs(key_witness, 1) if key_witness is not None else None
+        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 and 0 < n_sets <= 1024 else (0,)
+        if _out is None:
+            _out = torch.empty(shape, dtype=torch.int32, device=self._dev())
+        elif tuple(_out.shape) != shape or _out.dtype != torch.int32 or not _out.is_contiguous():
+            raise ValueError("_out must be a contiguous int32 tensor of shape %r" % (shape,))
+        if not torch.cuda.is_current_stream_capturing():  # the report's workspace: a capture needs it in place already
+            self._check(lib.aesw_theta_prepare(self._h, k, n_sets, self._stream()), "aesw_theta_prepare")
+        rep = torch.empty(3, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_theta_inputs_device(self._h, k, n_sets, int(n_blocks), layout, *[t.data_ptr() if n_blocks else None for t in witness[:3]],
+                                          _ptr(ks), _out.data_ptr(), rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_theta_inputs_device")
+        return _out, self._report(rep, sync, mult_report_dict)
+
+    def prepare_lookup_inputs(self, k: int, n_sets: int, stream=None):
+        """aesw_theta_prepare: the workspace lookup_inputs needs for a circuit of (k, n_sets) on `stream` (a torch stream; default
+        the current one), made ahead of a capture on that stream.  It is never freed or moved afterwards."""
+        handle = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._check(load_theta_library().aesw_theta_prepare(self._h, int(k), int(n_sets), handle), "aesw_theta_prepare")
+
+    def argument_columns(self, index, table_fr, k: int, n_sets: int, n_rows: int | None = None, pad_row: int = 0, out=None):
+        """A column of all 5 * n_sets lookup arguments as Fr cells (aesw_theta_columns_device): uint8 [n_sets, 5, 2^k, 32] with
+        out[s, t - 1, i] = table_fr[j(t)][index[s, t - 1, i]] for i < n_rows (default 2^k; the rest is not written), j the table
+        of the argument's arity.  index: an int32 [n_sets, 5, 2^k] tensor -- lookup_inputs, or a or s of permuted_columns; an
+        index outside the table gives a cell of zeros -- or None for the table column in row order: row i for i < 66561, pad_row
+        behind it.  table_fr: what compress_table returns."""
+        lib = load_theta_library()
+        torch = self._torch()
+        k, n_sets = int(k), int(n_sets)
+        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 and 0 < n_sets <= 1024 else (0,)
+        if index is not None:
+            if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or not index.is_cuda or index.device.index != self.device:
+                raise TypeError("index must be None or an int32 tensor on cuda:%d" % self.device)
+            if tuple(index.shape) != shape or not index.is_contiguous():
+                raise ValueError("index must be a contiguous int32 tensor of shape %r" % (shape,))
+        if tuple(self._u8(table_fr, "table_fr").shape) != (3, K.TABLE_ROWS, 32):
+            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((3, K.TABLE_ROWS, 32),))
+        if out is None:
+            out = torch.empty(shape + (32,), dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(out, "out").shape) != shape + (32,):
+            raise ValueError("out must be a uint8 tensor of shape %r" % (shape + (32,),))
+        rc = lib.aesw_theta_columns_device(self._h, k, n_sets, (1 << k) if n_rows is None else int(n_rows), int(pad_row),
+                                           None if index is None else index.data_ptr(), table_fr.data_ptr(), out.data_ptr(), self._stream())
+        self._check(rc, "aesw_theta_columns_device")
+        return out
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1438,7 +1553,8 @@ class Group(Context):
 for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", "encrypt_witness", "encrypt_witness_batches",
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
               "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values",
-              "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr"):
+              "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr",
+              "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
