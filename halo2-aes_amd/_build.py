@@ -89,7 +89,7 @@ def build_host(force: bool = False) -> Path:
 PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_keyring.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp",
                                       "aesw_comm.cpp", "aesw_group.cpp", "aesw_circuits.cpp")]
 PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_flush.h", "aesw_slabmap.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h",
-                                      "aesw_keyring.h", "aesw_options.h", "aesw_placement.h")] + \
+                                      "aesw_keyring.h", "aesw_options.h", "aesw_placement.h", "aesw_align.h", "aesw_store.h", "aesw_report_dev.h", "aesw_fr.h")] + \
     [INCLUDE / "aesw.h"]
 
 
@@ -107,13 +107,16 @@ def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_so
 
 # The checker libraries next to libaesw.so.  csrc/ itself holds exactly the sources of libaesw.so (PRODUCT_SOURCES); a
 # satellite's live one level down, in csrc/<name>/.  Each entry: its sources, the headers it depends on beyond
-# SATELLITE_HEADERS, its public header.  (The order is no build order -- each depends on libaesw.so alone -- but "mult" stays
+# SATELLITE_HEADERS, its public header.  SATELLITE_HEADERS is what every one of them may include: the context, the checker
+# core, what an entry point says before it launches (aesw_entry.h; aesw_entry_rules.h, whose bounds are aesw_mult.h's), the
+# store flavour (aesw_store.h), the report's reset and fold (aesw_report_dev.h).  (The order is no build order -- each depends on libaesw.so alone -- but "mult" stays
 # the last entry: tests/test_mult_library.py holds it there.)
 SATELLITE_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_check.h", "aesw_layout.h", "aesw_slabmap.h", "aesw_internal.h", "aesw_ctx.h",
-                                        "aesw_keyring.h", "aesw_options.h", "aesw_placement.h")] + [INCLUDE / "aesw.h"]
+                                        "aesw_keyring.h", "aesw_options.h", "aesw_placement.h", "aesw_align.h", "aesw_entry.h", "aesw_entry_rules.h", "aesw_mult.h",
+                                        "aesw_store.h", "aesw_report_dev.h")] + [INCLUDE / "aesw.h", INCLUDE / "aesw_mult.h"]
 SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
-    "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_cols.h"),
+    "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h", CSRC / "aesw_fr.h"], INCLUDE / "aesw_cols.h"),
     "vals": ([CSRC / "vals" / "aesw_vals_check.hip"], [CSRC / "aesw_vals_check.h"], INCLUDE / "aesw_vals.h"),
     "acc": ([CSRC / "acc" / "aesw_acc.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_mult_dev.h", CSRC / "aesw_run.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_acc.h"),
     "perm": ([CSRC / "perm" / "aesw_perm.hip"], [CSRC / "aesw_mult.h", CSRC / "aesw_perm.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_perm.h"),

@@ -12,12 +12,12 @@
 //     commute, so the histograms do not depend on how the run was cut, on the order of the calls or on which workgroup arrives
 //     first;
 //   * acc_key_kernel<LAYOUT>: the 400 rows of one key slab by one wave, one global add per hit (not a hot path);
-// and the entry points: their checks and the launches.
+// and the entry points: the checks that are theirs alone (the preamble and the shared rules are aesw_entry.h's) and the launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../../include/aesw_acc.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
 #include "../aesw_mult_dev.h"
 #include "../aesw_run.h"
 
@@ -115,9 +115,9 @@ extern "C" {
 int aesw_acc_reset_device(aesw_ctx *ctx, uint32_t n_sets, uint32_t *d_mult, aesw_mult_report *d_report, void *stream) {
     using namespace aesw_acc;
     static_assert(sizeof(aesw_mult_report) == 3 * sizeof(uint64_t), "the kernels address the report as three u64");
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_acc_reset_device");
-    if (!ctx) return AESW_ERR_INVALID_ARG;
-    if (const char *why = bad_outputs(0, false, n_sets, d_mult, d_report)) return refuse(ctx, "aesw_acc_reset_device", why);
+    const char *const call = "aesw_acc_reset_device";
+    if (int rc = entry_refused(ctx, call)) return rc;
+    if (const char *why = bad_outputs(0, false, n_sets, d_mult, d_report)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     const uint64_t words = (uint64_t)n_sets * MULT_BINS, groups = (words / 4 + 1023) / 1024;  // four 16-byte stores per lane
@@ -132,17 +132,15 @@ int aesw_acc_add_device_chunk(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64
                               void *stream, uint32_t blocks_per_workgroup) {
     using namespace aesw_acc;
     const char *const call = "aesw_acc_add_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
-    if (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED) return refuse(ctx, call, "the layout must be DENSE or PACKED (a VALUES witness has no x)");
+    if (int rc = entry_refused(ctx, call)) return rc;
+    if (const char *why = bad_layout(layout)) return refuse(ctx, call, why);
     if (const char *why = bad_outputs(k, true, n_sets, d_mult, d_report)) return refuse(ctx, call, why);
     const Placement place(k);
     const uint64_t cap = place.total(n_sets);
     if (first_block > cap || n_blocks > cap - first_block)
         return refuse(ctx, call, "first_block + n_blocks is more than aesw_block_capacity(k, n_sets)", AESW_ERR_CAPACITY);
     if (n_blocks == 0) return AESW_OK;
-    if (!d_x || !d_y || !d_z || !aligned_to(d_x, 16) || !aligned_to(d_y, 16) || !aligned_to(d_z, 16))
-        return refuse(ctx, call, "d_x, d_y and d_z must be there and 16-byte aligned");
+    if (const char *why = bad_slabs(d_x, d_y, d_z)) return refuse(ctx, call, why);
     RunParams p{};
     p.x = d_x; p.y = d_y; p.z = d_z;
     p.table = ctx->d_chktab[layout == AESW_LAYOUT_DENSE ? 0 : 1];  // uploaded by aesw_create(): nothing is allocated here
@@ -171,9 +169,8 @@ int aesw_acc_add_key_device(aesw_ctx *ctx, uint32_t k, int layout, const aesw_ke
                             void *stream) {
     using namespace aesw_acc;
     const char *const call = "aesw_acc_add_key_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
-    if (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED) return refuse(ctx, call, "the layout must be DENSE or PACKED (a VALUES witness has no x)");
+    if (int rc = entry_refused(ctx, call)) return rc;
+    if (const char *why = bad_layout(layout)) return refuse(ctx, call, why);
     if (const char *why = bad_outputs(k, true, 1, d_mult, d_report)) return refuse(ctx, call, why);
     const aesw_key_slab *ks = d_key_slab;
     if (!ks || !ks->kx || !ks->ky || !ks->kz || !aligned_to(ks->kx, 16) || !aligned_to(ks->ky, 16) || !aligned_to(ks->kz, 16))

@@ -16,6 +16,7 @@
 #include "../../include/aesw.h"
 #include "aesw_internal.h"
 #include "aesw_check.h"
+#include "aesw_fr.h"
 
 using namespace aesw;
 
@@ -38,42 +39,10 @@ uint8_t xtime(uint8_t a) { return (uint8_t)((a << 1) ^ ((a & 0x80) ? 0x1b : 0));
 // ---- bn256::Fr Montgomery table: v -> v * 2^256 mod r, 32 B little-endian ----
 // r = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 // (halo2curves 0.6.1 bn256::Fr, Cargo.lock:779-781).
-struct U256 { uint64_t l[4]; };
-const U256 FR_MOD = {{0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}};
-
-bool geq(const U256 &a, const U256 &b) {
-    for (int i = 3; i >= 0; --i) {
-        if (a.l[i] != b.l[i]) return a.l[i] > b.l[i];
-    }
-    return true;
-}
-// (a + b) mod r for a, b < r  (r < 2^254 so the sum fits in 256 bits)
-U256 add_mod(const U256 &a, const U256 &b) {
-    U256 s;
-    unsigned __int128 c = 0;
-    for (int i = 0; i < 4; ++i) {
-        c += (unsigned __int128)a.l[i] + b.l[i];
-        s.l[i] = (uint64_t)c;
-        c >>= 64;
-    }
-    if (geq(s, FR_MOD)) {
-        unsigned __int128 br = 0;
-        for (int i = 0; i < 4; ++i) {
-            unsigned __int128 d = (unsigned __int128)s.l[i] - FR_MOD.l[i] - (uint64_t)br;
-            s.l[i] = (uint64_t)d;
-            br = (d >> 64) & 1;
-        }
-    }
-    return s;
-}
+// The field is aesw_fr.h's.
 void build_fr_lut(uint8_t out[256 * 32]) {
-    U256 R = {{1, 0, 0, 0}};
-    for (int i = 0; i < 256; ++i) R = add_mod(R, R);  // 2^256 mod r
-    U256 acc = {{0, 0, 0, 0}};
-    for (int v = 0; v < 256; ++v) {
-        std::memcpy(out + 32 * v, acc.l, 32);  // little-endian limbs
-        acc = add_mod(acc, R);
-    }
+    const FrByteTable t = fr_byte_table();
+    std::memcpy(out, t.cell, sizeof t.cell);  // little-endian limbs
 }
 
 }  // namespace

@@ -4,7 +4,7 @@
 // this header holds what decides on the device whether a staged unit passes: the wave's LDS synchronisation, the register
 // staging of a unit's column ranges, the fast path's form of the check table and its branch-free walk, the verdict of a staged
 // block and of a staged key unit (block_unit_check, key_unit_check), the validation of circuit offsets (offsets_bad) and the
-// flush of a lane's counts into the report (flush_acc).  A kernel adds its prologue and its staging loop: how a unit and its
+// flush of a lane's counts into the report (flush_acc; the report's reset is aesw_report_dev.h's).  A kernel adds its prologue and its staging loop: how a unit and its
 // literal bytes get into the image and into registers.  The launch geometry the three launchers share is host code and lives
 // in aesw_internal.h.  Device code only: include from a HIP translation unit.
 #pragma once
@@ -15,12 +15,10 @@
 
 #include "aesw_internal.h"
 #include "aesw_check.h"
+#include "aesw_report_dev.h"  // LANES, report_reset
+#include "aesw_store.h"       // u32x4, u32x2
 
 namespace aesw {
-
-constexpr int LANES = 64;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // a value every lane of the wave holds alike, said so to the compiler: what is derived from it stays in scalar registers
 __device__ __forceinline__ uint64_t uni64(uint64_t v) {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/aesw.h"
+#include "aesw_align.h"
 #include "aesw_keyring.h"
 #include "aesw_options.h"
 
@@ -108,7 +109,6 @@ struct DeviceGuard {
 
 void aesw_arena_cache_trim(aesw_ctx *ctx, uint64_t keep_bytes);  // aesw_arena.cpp: release cached arenas, oldest first, until keep_bytes stay
 
-inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }  // a: a power of two
 // a key slab a checker library reads 16 bytes at a time: all four columns there and 16-byte aligned
 inline bool key_slab_ok(const aesw_key_slab *ks) {
     return ks && ks->w && ks->kx && ks->ky && ks->kz && aligned_to(ks->w, 16) && aligned_to(ks->kx, 16) && aligned_to(ks->ky, 16) && aligned_to(ks->kz, 16);

@@ -113,4 +113,24 @@ constexpr Fr FR_ONE = {{0x4ffffffbu, 0xac96341cu, 0x9f60cd29u, 0x36fc7695u, 0x78
 static_assert(fr_is_canonical(FR_ONE) && fr_mul(FR_ONE, FR_ONE).l[0] == FR_ONE.l[0] && fr_mul(FR_ONE, FR_ONE).l[7] == FR_ONE.l[7],
               "the Montgomery form of 1 is the identity of fr_mul");
 
+// The 256 byte values as cells, cell v = v * 2^256 mod r: what d_fr_lut (aesw_ctx.h) holds on the device and what the columns
+// checker inverts (aesw_cols_fr_table).  Little-endian limbs: on the hosts the project builds for, the table's bytes as they lie.
+struct FrByteTable {
+    Fr cell[256];
+};
+constexpr FrByteTable fr_byte_table() {
+    FrByteTable t{};
+    Fr acc = FR_ZERO;
+    for (int v = 0; v < 256; ++v) {
+        t.cell[v] = acc;
+        acc = fr_add(acc, FR_ONE);
+    }
+    return t;
+}
+static_assert(fr_byte_table().cell[0].l[0] == 0 && fr_byte_table().cell[0].l[7] == 0 && fr_byte_table().cell[1].l[0] == FR_ONE.l[0] &&
+                  fr_byte_table().cell[1].l[7] == FR_ONE.l[7],
+              "cells 0 and 1 are the Montgomery forms of 0 and 1");
+static_assert(fr_byte_table().cell[255].l[0] == 0x3ffffabcu && fr_byte_table().cell[255].l[3] == 0x4eace25fu && fr_byte_table().cell[255].l[7] == 0x2fd2eb16u,
+              "cell 255 is 255 * 2^256 mod r");
+
 }  // namespace aesw

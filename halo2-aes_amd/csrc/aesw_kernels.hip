@@ -29,6 +29,7 @@
 #include "aesw_lane.h"
 #include "aesw_check.h"
 #include "aesw_check_dev.h"
+#include "aesw_store.h"
 
 namespace aesw {
 
@@ -121,30 +122,7 @@ template <> struct PieceT<16> { using type = u32x4; };
 template <> struct PieceT<8> { using type = u32x2; };
 template <> struct PieceT<4> { using type = uint32_t; };
 
-// Store flavours: 0 plain, 1 nontemporal (nt), 2 write-through at agent scope
-// (sc1).  Plain / nt lines stay dirty in the XCD's L2 and are written back at
-// the kernel boundary (that costs dirty bytes / ~6 TB/s after the last wave has
-// finished); sc1 stores leave L2 as they are issued, so a launch ends with
-// nothing left to flush (MI355X_MICROARCH.md, "stores of each flavour").
-// Modes 3..5 (tools/ only) exist in -DAESW_DIAGNOSTIC builds alone: 3 = leave the flush out (compute + staging only),
-// 4 = flush only (no AES work, no staging writes: the store schedule fed from whatever LDS holds), 5 = as 4 without the
-// LDS reads.  Their output is garbage; they price the parts of a launch.
-template <int MODE>
-__device__ __forceinline__ void gstore(u32x4 *p, const u32x4 &v) {
-    if (MODE == 3) return;
-    // hipcc neither counts nor pads an asm store: the trailing s_nop 1 covers the ">64-bit store data
-    // overwritten by the next instruction" hazard (cdna guide 5.7 item 1); nothing ever waits on these stores.
-    if (MODE == 2 || MODE >= 4) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-    else if (MODE == 1) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-template <int MODE>
-__device__ __forceinline__ void gstore(u32x2 *p, const u32x2 &v) {
-    if (MODE == 3) return;
-    if (MODE == 2 || MODE >= 4) asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 0" : : "v"(p), "v"(v) : "memory");
-    else if (MODE == 1) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+// The store flavours (0 plain, 1 nontemporal, 2 write-through at agent scope; 3 ... 5 diagnostic) and gstore<MODE>: aesw_store.h.
 // wave-uniform base (SGPR pair) + 32-bit byte offset per lane: no 64-bit address arithmetic per piece
 // All three flavours go through the same asm form (SGPR base + VGPR offset), so that they differ in the cache-policy
 // bits and in nothing else: written as C++ stores the plain and nontemporal variants needed 60 more VGPRs for 64-bit
@@ -975,16 +953,7 @@ static hipError_t allow_large_lds(const void *fn, size_t lds) {
 // Which encrypt_kernel / key_kernel instantiations exist is said once, by the two visitors below: a handful of branches turn the
 // runtime tuple into a tag type for a functor.  Launching and warming are two functors over one visitor, so neither can name an
 // instantiation the other lacks (tests/kernel_cases.py restates the set for the sweep).
-template <int N> using Int = std::integral_constant<int, N>;
-#define AESW_V(c) decltype(c)::value  // the value of an Int<N> argument, as a constant expression
-// f(Int<v>{}) for v among the listed values; the last one also takes every other v
-template <int A, int... Rest, class F>
-static auto with_value(int v, F &&f) {
-    if constexpr (sizeof...(Rest) == 0) return f(Int<A>{});
-    else return v == A ? f(Int<A>{}) : with_value<Rest...>(v, f);
-}
-// the store flavour: 0 plain, 1 nontemporal, 2 write-through ("store_mode" / "key_store_mode" / "fr_store_mode")
-template <class F> static auto with_nt(int nt, F &&f) { return with_value<2, 1, 0>(nt, f); }
+// with_value / with_nt, the visitors' one building block, are aesw_store.h's.
 #ifdef AESW_DIAGNOSTIC  // 3 ... 5: "leave the flush out" and its kin (tools/parts.py): launchable, never warmed
 #define AESW_ENC_FLAVOURS 5, 4, 3, 2, 1, 0
 #else

@@ -7,12 +7,11 @@
 // the wave count that fits next to the counters; the add flush of both accumulators (flush_add, flush_pair_add); and the body
 // that zeroes histograms and resets a report (zero_and_reset: a library's kernel of its own name wraps it; a __global__ here
 // would be a kernel of every library that includes this).  A kernel adds its prologue and its staging loop -- which blocks,
-// which unit numbers: that loop stays in the kernels ("Shared machinery").  Device code, and behind it the host
-// lines the entry points of the two accumulators share (refuse, bad_outputs): include from a HIP translation unit.
+// which unit numbers: that loop stays in the kernels ("Shared machinery").  Device code only (what the entry
+// points share is aesw_entry.h's): include from a HIP translation unit.
 #pragma once
 #include "../../include/aesw_mult.h"
 #include "aesw_check_dev.h"
-#include "aesw_ctx.h"
 #include "aesw_mult.h"
 
 namespace aesw {
@@ -170,24 +169,10 @@ __device__ __forceinline__ void flush_pair_add(uint32_t *out, const uint32_t *cn
 // not memset nodes, so that a captured graph replays it as it runs eagerly.
 __device__ __forceinline__ void zero_and_reset(uint32_t *mult, uint64_t words, uint64_t *report, uint32_t threads) {
     const uint64_t tid = (uint64_t)blockIdx.x * threads + threadIdx.x, n = (uint64_t)gridDim.x * threads;
-    if (tid < 3) report[tid] = tid == 2 ? ~0ull : 0ull;
+    report_reset(report, 3, 1u << 2, tid);
     const u32x4 zero = {0, 0, 0, 0};
     for (uint64_t i = tid; i < words / 4; i += n) reinterpret_cast<u32x4 *>(mult)[i] = zero;
     if (tid < words % 4) mult[words - 1 - tid] = 0;
-}
-
-// Host: what the entry points of the two accumulators share.
-inline int refuse(aesw_ctx *ctx, const char *call, const char *why, int status = AESW_ERR_INVALID_ARG) {
-    if (ctx) ctx->last_error = std::string(call) + ": " + why;
-    return status;
-}
-// what every call checks of its outputs and of the circuit's shape (with_k: the call takes a k)
-inline const char *bad_outputs(uint32_t k, bool with_k, uint32_t n_sets, const uint32_t *d_mult, const aesw_mult_report *d_report) {
-    if (with_k && !mult_k_ok(k)) return "k must be 2 ... 30";
-    if (!mult_sets_ok(n_sets)) return "n_sets must be 1 ... 1024";
-    if (!d_report || !aligned_to(d_report, 8)) return "d_report must be there and 8-byte aligned";
-    if (!d_mult || !aligned_to(d_mult, 16)) return "d_mult must be there and 16-byte aligned";
-    return nullptr;
 }
 
 }  // namespace multdev

@@ -16,7 +16,7 @@
 #include "../../../include/aesw_circ.h"
 #include "../aesw_check_dev.h"
 #include "../aesw_circ_search.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
 
 namespace aesw_circ {
 using namespace aesw;
@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(256) circ_check_kernel(const CircCheckParams p
 // check instead of launch_check's two memsets.  One thing less to enqueue per call, and a kernel node replays the same in a
 // captured graph as it runs eagerly; the 64-byte memset node this replaced left stale words behind on replay.
 __global__ void __launch_bounds__(64) circ_report_init_kernel(uint64_t *report) {
-    if (threadIdx.x < 8) report[threadIdx.x] = threadIdx.x == 6 ? ~0ull : 0ull;
+    report_reset(report, 8, 1u << 6, threadIdx.x);
 }
 
 static hipError_t launch_circ_check(const CircCheckParams &p, bool dense, hipStream_t s) {
@@ -117,8 +117,8 @@ int aesw_circ_check_witness_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, u
                                    const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *d_key_slabs,
                                    aesw_circ_check_report *d_report, void *stream) {
     static_assert(sizeof(aesw_circ_check_report) == 8 * sizeof(uint64_t), "the kernel addresses the report as eight u64");
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_circ_check_witness_device");
-    if (!ctx || (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED) || k < 2 || k > 30 || n_sets == 0 || n_sets > 1024 ||
+    if (int rc = aesw::entry_refused(ctx, "aesw_circ_check_witness_device")) return rc;
+    if ((layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED) || k < 2 || k > 30 || n_sets == 0 || n_sets > 1024 ||
         n_circuits == 0 || !d_offsets || !aligned_to(d_offsets, 8) || !d_report || !aligned_to(d_report, 8))
         return AESW_ERR_INVALID_ARG;
     const aesw_key_slab *ks = d_key_slabs;

@@ -23,7 +23,8 @@
 #include "../../../include/aesw_cols.h"
 #include "../aesw_check_dev.h"
 #include "../aesw_circ_search.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
+#include "../aesw_fr.h"
 #include "../aesw_placement.h"
 
 namespace aesw_cols {
@@ -327,6 +328,7 @@ __global__ void __launch_bounds__(256) cols_check_kernel(const ColsParams p) {
 // The report starts as (0 units, no failures, first = first_cell = none, 0 cells): a kernel node, not a memset node, so a
 // captured graph replays it as it runs eagerly.
 __global__ void __launch_bounds__(64) cols_report_init_kernel(uint64_t *report) {
+    // its own line, not aesw_report_dev.h's report_reset: with two "none" words the shared form compiles to another register count
     if (threadIdx.x < 12) report[threadIdx.x] = (threadIdx.x == 6 || threadIdx.x == 10) ? ~0ull : 0ull;
 }
 
@@ -348,39 +350,9 @@ static hipError_t launch_cols_check(ColsParams &p, bool as_fr, hipStream_t s) {
 }
 
 // ---- host: the Fr table and the hash ------------------------------------------------------------------------------
-struct U256 { uint64_t l[4]; };
-const U256 FR_MOD = {{0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}};  // bn256::Fr
-static bool geq(const U256 &a, const U256 &b) {
-    for (int i = 3; i >= 0; --i)
-        if (a.l[i] != b.l[i]) return a.l[i] > b.l[i];
-    return true;
-}
-static U256 add_mod(const U256 &a, const U256 &b) {  // a, b < r < 2^254: the sum does not carry out
-    U256 s;
-    unsigned __int128 cy = 0;
-    for (int i = 0; i < 4; ++i) {
-        cy += (unsigned __int128)a.l[i] + b.l[i];
-        s.l[i] = (uint64_t)cy;
-        cy >>= 64;
-    }
-    if (geq(s, FR_MOD)) {
-        unsigned __int128 br = 0;
-        for (int i = 0; i < 4; ++i) {
-            const unsigned __int128 d = (unsigned __int128)s.l[i] - FR_MOD.l[i] - (uint64_t)br;
-            s.l[i] = (uint64_t)d;
-            br = (d >> 64) & 1;
-        }
-    }
-    return s;
-}
 static void fr_table(uint8_t out[256 * 32]) {
-    U256 R = {{1, 0, 0, 0}};
-    for (int i = 0; i < 256; ++i) R = add_mod(R, R);  // 2^256 mod r
-    U256 acc = {{0, 0, 0, 0}};
-    for (int v = 0; v < 256; ++v) {
-        std::memcpy(out + 32 * v, acc.l, 32);  // little-endian limbs
-        acc = add_mod(acc, R);
-    }
+    const FrByteTable t = fr_byte_table();  // aesw_fr.h: cell v is v * 2^256 mod r, little-endian limbs
+    std::memcpy(out, t.cell, sizeof t.cell);
 }
 
 static uint32_t low_dword(const uint8_t *cell) {
@@ -443,8 +415,8 @@ int aesw_cols_check_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32_t 
                            const uint8_t *d_pt, const uint8_t *d_keys, const uint8_t *d_ct, int as_fr, const uint8_t *d_cols,
                            aesw_cols_check_report *d_report, void *stream) {
     static_assert(sizeof(aesw_cols_check_report) == 12 * sizeof(uint64_t), "the kernel addresses the report as twelve u64");
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_cols_check_device");
-    if (!ctx || k < 9 || k > 30 || n_sets == 0 || n_sets > 1024 || n_circuits == 0 || !d_offsets || !aligned_to(d_offsets, 8) ||
+    if (int rc = aesw::entry_refused(ctx, "aesw_cols_check_device")) return rc;
+    if (k < 9 || k > 30 || n_sets == 0 || n_sets > 1024 || n_circuits == 0 || !d_offsets || !aligned_to(d_offsets, 8) ||
         !d_report || !aligned_to(d_report, 8) || !d_cols || !aligned_to(d_cols, 16) || (as_fr != 0 && as_fr != 1) ||
         !aligned_to(d_keys, 4) || !aligned_to(d_ct, 4) || !aligned_to(d_pt, 4) || (n && !d_pt) ||
         (uint64_t)n_circuits * (3 * n_sets + 1) > 0xffffffffull)

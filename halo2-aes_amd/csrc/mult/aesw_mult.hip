@@ -10,12 +10,13 @@
 //   * PRIVATE: two workgroups own one (circuit, set).  Both walk every block of the set, each counts the bins of its half in
 //     LDS and stores them once, with plain contiguous stores: no global atomic touches d_mult, and nothing has to zero it
 //     first;
-// and the entry points: their checks, the choice of the form, the launches.
+// and the entry points: the checks that are theirs alone (the preamble and the shared rules are aesw_entry.h's), the choice of
+// the form, the launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../../include/aesw_mult.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
 #include "../aesw_mult_dev.h"
 
 namespace aesw_mult {
@@ -180,11 +181,6 @@ static int default_form(uint32_t /*k*/, uint32_t n_sets, uint32_t n_circuits) {
     return 2 * (uint64_t)n_circuits * n_sets >= PRIVATE_MIN_WORKGROUPS ? AESW_MULT_FORM_PRIVATE : AESW_MULT_FORM_DIRECT;
 }
 
-static int refuse(aesw_ctx *ctx, const char *why) {
-    if (ctx) ctx->last_error = std::string("aesw_mult_count_device: ") + why;
-    return AESW_ERR_INVALID_ARG;
-}
-
 }  // namespace aesw_mult
 
 extern "C" {
@@ -192,28 +188,26 @@ extern "C" {
 int aesw_mult_count_device_form(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32_t n_circuits, const uint64_t *d_offsets, int layout,
                                 const uint8_t *d_x, const uint8_t *d_y, const uint8_t *d_z, const aesw_key_slab *d_key_slabs, uint32_t *d_mult,
                                 aesw_mult_report *d_report, void *stream, int form) {
-    using aesw_mult::refuse;
+    using namespace aesw;
     static_assert(sizeof(aesw_mult_report) == 3 * sizeof(uint64_t), "the kernels address the report as three u64");
     constexpr uint32_t MAX_UNITS = 1u << 24;
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_mult_count_device");
-    if (!ctx) return AESW_ERR_INVALID_ARG;
-    if (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED) return refuse(ctx, "the layout must be DENSE or PACKED (a VALUES witness has no x)");
-    if (!aesw::mult_k_ok(k)) return refuse(ctx, "k must be 2 ... 30");
-    if (!aesw::mult_sets_ok(n_sets) || n_circuits == 0 || (uint64_t)n_circuits * n_sets > MAX_UNITS)
-        return refuse(ctx, "n_sets must be 1 ... 1024, n_circuits >= 1 and n_circuits * n_sets <= 2^24");
-    if (form != AESW_MULT_FORM_AUTO && form != AESW_MULT_FORM_DIRECT && form != AESW_MULT_FORM_PRIVATE) return refuse(ctx, "no such form");
-    if (!d_offsets || !aligned_to(d_offsets, 8) || !d_report || !aligned_to(d_report, 8)) return refuse(ctx, "d_offsets and d_report must be there and 8-byte aligned");
-    if (!d_mult || !aligned_to(d_mult, 16)) return refuse(ctx, "d_mult must be there and 16-byte aligned");
-    if (!d_x || !d_y || !d_z || !aligned_to(d_x, 16) || !aligned_to(d_y, 16) || !aligned_to(d_z, 16))
-        return refuse(ctx, "d_x, d_y and d_z must be there and 16-byte aligned");
+    const char *const call = "aesw_mult_count_device";  // the public name, whichever of the two was called
+    if (int rc = entry_refused(ctx, call)) return rc;
+    if (const char *why = bad_layout(layout)) return refuse(ctx, call, why);
+    if (const char *why = bad_k(k)) return refuse(ctx, call, why);
+    if (!mult_sets_ok(n_sets) || n_circuits == 0 || (uint64_t)n_circuits * n_sets > MAX_UNITS)
+        return refuse(ctx, call, "n_sets must be 1 ... 1024, n_circuits >= 1 and n_circuits * n_sets <= 2^24");
+    if (form != AESW_MULT_FORM_AUTO && form != AESW_MULT_FORM_DIRECT && form != AESW_MULT_FORM_PRIVATE) return refuse(ctx, call, "no such form");
+    if (!d_offsets || !aligned_to(d_offsets, 8) || !d_report || !aligned_to(d_report, 8)) return refuse(ctx, call, "d_offsets and d_report must be there and 8-byte aligned");
+    if (!d_mult || !aligned_to(d_mult, 16)) return refuse(ctx, call, "d_mult must be there and 16-byte aligned");
+    if (const char *why = bad_slabs(d_x, d_y, d_z)) return refuse(ctx, call, why);
     const aesw_key_slab *ks = d_key_slabs;
-    const bool with_keys = ks && ks->kx && ks->ky && ks->kz && aesw::mult_has_key_rows(k);
-    if (with_keys && (!aligned_to(ks->kx, 16) || !aligned_to(ks->ky, 16) || !aligned_to(ks->kz, 16))) return refuse(ctx, "the key columns must be 16-byte aligned");
+    if (const char *why = bad_key_columns(ks, k)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     aesw_mult::MultParams p{};
     p.x = d_x; p.y = d_y; p.z = d_z;
-    if (with_keys) { p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
+    if (with_keys(ks, k)) { p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
     p.table = ctx->d_chktab[layout == AESW_LAYOUT_DENSE ? 0 : 1];  // uploaded by aesw_create(): nothing is allocated here
     p.tab768 = ctx->d_tables;
     p.offsets = d_offsets;

@@ -8,23 +8,22 @@
 //   * perm_expand_kernel: driven by position.  A lane owns four consecutive positions of one argument: it searches the starts
 //     for its first and its last position, the two between them inside that range, and stores 16 bytes of A' and 16 of S'.
 //     One-shot workgroups of 4 KiB per column, in address order.  Workgroup (0, 0) also writes the report, from the overflow
-//     flags of the workspace: plain stores, no atomic, nothing to reset;
-//   * perm_gather_fr_kernel: expand_fr_kernel's one-shot geometry over the caller's 66 561-cell table;
-//   * the entry points and their checks.
+//     flags of the workspace (the fold is aesw_report_dev.h's): plain stores, no atomic, nothing to reset;
+//   * perm_gather_fr_kernel<NT>: expand_fr_kernel's one-shot geometry over the caller's 66 561-cell table, the store flavour
+//     aesw_store.h's;
+//   * the entry points and the checks that are theirs alone (the preamble and the shared rules are aesw_entry.h's).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../../include/aesw_perm.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
 #include "../aesw_perm.h"
+#include "../aesw_report_dev.h"
+#include "../aesw_store.h"
 
 namespace aesw_perm {
 using namespace aesw;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-constexpr int LANES = 64;
 constexpr int SCAN_WAVES = 16, SCAN_THREADS = SCAN_WAVES * LANES, PER_THREAD = 4, TILE = SCAN_THREADS * PER_THREAD;
 constexpr int EXPAND_THREADS = 256, POSITIONS = 4;  // a workgroup writes 4 KiB of A' and 4 KiB of S'
 static_assert(mult_section_rows(1) % PER_THREAD == 0 && mult_section_rows(2) % TILE == 0, "a thread's four bins lie in one section");
@@ -125,33 +124,20 @@ __global__ void __launch_bounds__(SCAN_THREADS) perm_scan_kernel(const BuildPara
 // The report, by one workgroup of EXPAND_THREADS threads, all of them here: how many arguments overflowed and the smallest of them.
 __device__ __forceinline__ void write_report(const BuildParams &p) {
     __shared__ unsigned long long s_first[EXPAND_THREADS / LANES];
-    __shared__ uint32_t s_count[EXPAND_THREADS / LANES];
+    __shared__ uint32_t s_count[1][EXPAND_THREADS / LANES];
     const uint32_t n_args = p.n_sets * PERM_TAGS;
-    uint32_t count = 0;
+    uint32_t count[1] = {0};
     unsigned long long firstv = ~0ull;
     for (uint32_t i = threadIdx.x; i < n_args; i += EXPAND_THREADS) {
         const uint32_t set = i / PERM_TAGS, tag = i % PERM_TAGS + 1;
         if (p.ws[(uint64_t)set * PERM_WS_WORDS + perm_ws_scalars(tag) + 3]) {
-            ++count;
+            ++count[0];
             const unsigned long long id = (unsigned long long)set * 8 + tag;
             firstv = id < firstv ? id : firstv;
         }
     }
-#pragma unroll
-    for (int o = LANES / 2; o; o >>= 1) {
-        count += __shfl_xor(count, o, LANES);
-        const unsigned long long other = __shfl_xor(firstv, o, LANES);
-        firstv = other < firstv ? other : firstv;
-    }
-    if (threadIdx.x % LANES == 0) { s_count[threadIdx.x / LANES] = count; s_first[threadIdx.x / LANES] = firstv; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < EXPAND_THREADS / LANES; ++w) {
-            count += s_count[w];
-            firstv = s_first[w] < firstv ? s_first[w] : firstv;
-        }
-        p.report[0] = n_args; p.report[1] = count; p.report[2] = firstv;
-    }
+    workgroup_fold(count, firstv, s_count, s_first, threadIdx.x);
+    if (threadIdx.x == 0) { p.report[0] = n_args; p.report[1] = count[0]; p.report[2] = firstv; }
 }
 
 // grid: x = 1 024 positions of an argument, y = the argument
@@ -195,14 +181,6 @@ __global__ void __launch_bounds__(EXPAND_THREADS) perm_expand_kernel(const Build
     }
 }
 
-// Store flavours as aesw_kernels.hip's gstore: 0 plain, 1 nontemporal, 2 write-through at agent scope.
-template <int NT>
-__device__ __forceinline__ void store_piece(u32x4 *dst, const u32x4 &v) {
-    if (NT == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-    else if (NT == 1) __builtin_nontemporal_store(v, dst);
-    else *dst = v;
-}
-
 // One lane writes one 16-byte half cell; a workgroup writes 4 KiB and exits.
 template <int NT>
 __global__ void __launch_bounds__(256) perm_gather_fr_kernel(const uint32_t *__restrict__ index, uint64_t n_cells, const u32x4 *__restrict__ table, u32x4 *__restrict__ out) {
@@ -211,15 +189,10 @@ __global__ void __launch_bounds__(256) perm_gather_fr_kernel(const uint32_t *__r
     const uint32_t r = index[i >> 1];
     u32x4 v = {0, 0, 0, 0};
     if (r < MULT_BINS) v = table[(uint64_t)r * 2 + (uint32_t)(i & 1)];
-    store_piece<NT>(out + i, v);
+    gstore<NT>(out + i, v);
 }
 
 constexpr uint64_t MAX_GATHER_CELLS = 1ull << 36;
-
-static int refuse(aesw_ctx *ctx, const char *call, const char *why) {
-    ctx->last_error = std::string(call) + ": " + why;
-    return AESW_ERR_INVALID_ARG;
-}
 
 }  // namespace aesw_perm
 
@@ -235,16 +208,15 @@ int aesw_perm_build_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32_t 
     static_assert(sizeof(aesw_perm_report) == 3 * sizeof(uint64_t), "the kernel addresses the report as three u64");
     static_assert(AESW_PERM_ARGUMENTS == PERM_TAGS, "one argument per tag");
     const char *const call = "aesw_perm_build_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
+    if (int rc = entry_refused(ctx, call)) return rc;
     if (!perm_k_ok(k)) return refuse(ctx, call, "k must be 17 ... 30 (2^k rows hold the table)");
-    if (!mult_sets_ok(n_sets)) return refuse(ctx, call, "n_sets must be 1 ... 1024");
+    if (const char *why = bad_sets(n_sets)) return refuse(ctx, call, why);
     if (!perm_rows_ok(k, n_rows)) return refuse(ctx, call, "n_rows must be 66561 ... 2^k");
     if (pad_row >= MULT_BINS) return refuse(ctx, call, "pad_row must be a table row, 0 ... 66560");
     if (!d_mult || !aligned_to(d_mult, 16)) return refuse(ctx, call, "d_mult must be there and 16-byte aligned");
     if (!d_a || !d_s || !aligned_to(d_a, 16) || !aligned_to(d_s, 16)) return refuse(ctx, call, "d_a and d_s must be there and 16-byte aligned");
     if (!d_workspace || !aligned_to(d_workspace, 16)) return refuse(ctx, call, "d_workspace must be there and 16-byte aligned");
-    if (!d_report || !aligned_to(d_report, 8)) return refuse(ctx, call, "d_report must be there and 8-byte aligned");
+    if (const char *why = bad_report(d_report)) return refuse(ctx, call, why);
     BuildParams p{};
     p.mult = d_mult; p.a = d_a; p.s = d_s;
     p.ws = static_cast<uint32_t *>(d_workspace);
@@ -264,8 +236,7 @@ int aesw_perm_build_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32_t 
 int aesw_perm_gather_fr_device(aesw_ctx *ctx, uint64_t n_cells, const uint32_t *d_index, const uint8_t *d_table_fr, uint8_t *d_out_fr, void *stream) {
     using namespace aesw_perm;
     const char *const call = "aesw_perm_gather_fr_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
+    if (int rc = entry_refused(ctx, call)) return rc;
     if (n_cells > MAX_GATHER_CELLS) return refuse(ctx, call, "n_cells must be at most 2^36");
     if (n_cells == 0) return AESW_OK;
     if (!d_index || !aligned_to(d_index, 4)) return refuse(ctx, call, "d_index must be there and 4-byte aligned");
@@ -277,10 +248,7 @@ int aesw_perm_gather_fr_device(aesw_ctx *ctx, uint64_t n_cells, const uint32_t *
     const dim3 grid((unsigned)((n_cells * 2 + 255) / 256));
     const u32x4 *table = reinterpret_cast<const u32x4 *>(d_table_fr);
     u32x4 *out = reinterpret_cast<u32x4 *>(d_out_fr);
-    const int64_t nt = ctx->opt.fr_nt;
-    if (nt == 2) hipLaunchKernelGGL(perm_gather_fr_kernel<2>, grid, dim3(256), 0, s, d_index, n_cells, table, out);
-    else if (nt == 1) hipLaunchKernelGGL(perm_gather_fr_kernel<1>, grid, dim3(256), 0, s, d_index, n_cells, table, out);
-    else hipLaunchKernelGGL(perm_gather_fr_kernel<0>, grid, dim3(256), 0, s, d_index, n_cells, table, out);
+    with_nt((int)ctx->opt.fr_nt, [&](auto n) { hipLaunchKernelGGL(perm_gather_fr_kernel<AESW_V(n)>, grid, dim3(256), 0, s, d_index, n_cells, table, out); });
     HIP_TRY(ctx, hipGetLastError());
     return AESW_OK;
 }

@@ -4,28 +4,28 @@
 //   * theta_table_kernel: one lane per (arity, table row) compresses the row under a theta every lane loads from one address;
 //   * theta_inputs_kernel: a lane owns four consecutive rows of one set, resolves each row's tag and bin once and stores one
 //     16-byte piece into each of the set's five arguments.  One-shot workgroups of five 4 KiB pieces, in address order.  The
-//     workgroup's part of the report goes to the workspace with one plain store;
-//   * theta_report_kernel: one workgroup folds those parts into the report: plain stores, no atomic, nothing to reset;
+//     workgroup's part of the report (folded by aesw_report_dev.h's workgroup_fold) goes to the workspace with one plain store;
+//   * theta_report_kernel: one workgroup folds those parts into the report, by the same fold: plain stores, no atomic,
+//     nothing to reset;
 //   * theta_columns_kernel<NT>: the one-shot gather of the permuted-columns library over all arguments of a column at once,
-//     the table chosen per workgroup;
-//   * the entry points, their checks and the workspace.
+//     the table chosen per workgroup, the store flavour aesw_store.h's;
+//   * the entry points, the checks that are theirs alone (the preamble and the shared rules are aesw_entry.h's) and the workspace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <map>
 #include <mutex>
-#include <string>
 #include <tuple>
 
 #include "../../../include/aesw_theta.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
+#include "../aesw_report_dev.h"
+#include "../aesw_store.h"
 #include "../aesw_theta.h"
 
 namespace aesw_theta {
 using namespace aesw;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-constexpr int LANES = 64;
 constexpr int THREADS = 256, ROWS_PER_LANE = 4, ROWS_PER_GROUP = THREADS * ROWS_PER_LANE;  // a workgroup writes 4 KiB per argument
 static_assert(sizeof(Fr) == 32 && sizeof(aesw_theta_report) == 2 * sizeof(uint64_t) && sizeof(aesw_mult_report) == 3 * sizeof(uint64_t),
               "a cell is two 16-byte pieces; the kernels address the reports as u64 words");
@@ -72,7 +72,7 @@ struct InputParams {
 
 // grid: x = 1 024 rows of a set, y = the set
 __global__ void __launch_bounds__(THREADS) theta_inputs_kernel(const InputParams p) {
-    __shared__ uint32_t s_lookups[THREADS / LANES], s_misses[THREADS / LANES];
+    __shared__ uint32_t s_sums[2][THREADS / LANES];
     __shared__ unsigned long long s_first[THREADS / LANES];
     const uint32_t set = blockIdx.y, rows = 1u << p.k;
     const ColumnSource cs[3] = {column_source(p.place, 3 * set, p.n_sets, p.kx, p.ky, p.kz, p.x, p.y, p.z, p.sx, p.sy, p.sz),
@@ -103,64 +103,25 @@ __global__ void __launch_bounds__(THREADS) theta_inputs_kernel(const InputParams
         }
     }
     // the workgroup's part of the report: every thread is here
-#pragma unroll
-    for (int o = LANES / 2; o; o >>= 1) {
-        lookups += __shfl_xor(lookups, o, LANES);
-        misses += __shfl_xor(misses, o, LANES);
-        const unsigned long long other = __shfl_xor(first, o, LANES);
-        first = other < first ? other : first;
-    }
-    const uint32_t wave = threadIdx.x / LANES;
-    if (threadIdx.x % LANES == 0) { s_lookups[wave] = lookups; s_misses[wave] = misses; s_first[wave] = first; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < THREADS / LANES; ++w) {
-            lookups += s_lookups[w];
-            misses += s_misses[w];
-            first = s_first[w] < first ? s_first[w] : first;
-        }
-        p.parts[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = u32x4{lookups, misses, (uint32_t)first, (uint32_t)(first >> 32)};
-    }
+    uint32_t sums[2] = {lookups, misses};  // made here: counted in the array, the kernel allocates its registers differently
+    workgroup_fold(sums, first, s_sums, s_first, threadIdx.x);
+    if (threadIdx.x == 0) p.parts[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = u32x4{sums[0], sums[1], (uint32_t)first, (uint32_t)(first >> 32)};
 }
 
 // one workgroup: the parts of the workspace into the report
 constexpr int REPORT_THREADS = 1024;
 __global__ void __launch_bounds__(REPORT_THREADS) theta_report_kernel(const u32x4 *__restrict__ parts, uint32_t n_parts, uint64_t *__restrict__ report) {
-    __shared__ unsigned long long s_lookups[REPORT_THREADS / LANES], s_misses[REPORT_THREADS / LANES], s_first[REPORT_THREADS / LANES];
-    unsigned long long lookups = 0, misses = 0, first = ~0ull;
+    __shared__ unsigned long long s_sums[2][REPORT_THREADS / LANES], s_first[REPORT_THREADS / LANES];
+    unsigned long long sums[2] = {0, 0}, first = ~0ull;  // lookups, misses
     for (uint32_t i = threadIdx.x; i < n_parts; i += REPORT_THREADS) {
         const u32x4 v = parts[i];
         const unsigned long long f = (unsigned long long)v[3] << 32 | v[2];
-        lookups += v[0];
-        misses += v[1];
+        sums[0] += v[0];
+        sums[1] += v[1];
         first = f < first ? f : first;
     }
-#pragma unroll
-    for (int o = LANES / 2; o; o >>= 1) {
-        lookups += __shfl_xor(lookups, o, LANES);
-        misses += __shfl_xor(misses, o, LANES);
-        const unsigned long long other = __shfl_xor(first, o, LANES);
-        first = other < first ? other : first;
-    }
-    const uint32_t wave = threadIdx.x / LANES;
-    if (threadIdx.x % LANES == 0) { s_lookups[wave] = lookups; s_misses[wave] = misses; s_first[wave] = first; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < REPORT_THREADS / LANES; ++w) {
-            lookups += s_lookups[w];
-            misses += s_misses[w];
-            first = s_first[w] < first ? s_first[w] : first;
-        }
-        report[0] = lookups; report[1] = misses; report[2] = first;
-    }
-}
-
-// Store flavours as aesw_kernels.hip's gstore: 0 plain, 1 nontemporal, 2 write-through at agent scope.
-template <int NT>
-__device__ __forceinline__ void store_piece(u32x4 *dst, const u32x4 &v) {
-    if (NT == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-    else if (NT == 1) __builtin_nontemporal_store(v, dst);
-    else *dst = v;
+    workgroup_fold(sums, first, s_sums, s_first, threadIdx.x);
+    if (threadIdx.x == 0) { report[0] = sums[0]; report[1] = sums[1]; report[2] = first; }
 }
 
 // One lane writes one 16-byte half cell; a workgroup writes 4 KiB of one argument and exits.  grid: x = 128 rows, y = the argument
@@ -174,12 +135,7 @@ __global__ void __launch_bounds__(THREADS) theta_columns_kernel(const uint32_t *
     const uint32_t r = index ? index[at] : theta_table_index(row, pad_row);
     u32x4 v = {0, 0, 0, 0};
     if (r < MULT_BINS) v = tables[((uint64_t)table * MULT_BINS + r) * 2 + (i & 1u)];
-    store_piece<NT>(out + at * 2 + (i & 1u), v);
-}
-
-static int refuse(aesw_ctx *ctx, const char *call, const char *why, int status = AESW_ERR_INVALID_ARG) {
-    ctx->last_error = std::string(call) + ": " + why;
-    return status;
+    gstore<NT>(out + at * 2 + (i & 1u), v);
 }
 
 // The workspaces of the inputs call: one per (device, context, stream), so that calls on different contexts or streams never
@@ -227,11 +183,10 @@ extern "C" {
 int aesw_theta_compress_table_device(aesw_ctx *ctx, const uint8_t *d_theta, uint8_t *d_table_fr, aesw_theta_report *d_report, void *stream) {
     using namespace aesw_theta;
     const char *const call = "aesw_theta_compress_table_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
+    if (int rc = entry_refused(ctx, call)) return rc;
     if (!d_theta || !aligned_to(d_theta, 16)) return refuse(ctx, call, "d_theta must be there and 16-byte aligned");
     if (!d_table_fr || !aligned_to(d_table_fr, 16)) return refuse(ctx, call, "d_table_fr must be there and 16-byte aligned");
-    if (!d_report || !aligned_to(d_report, 8)) return refuse(ctx, call, "d_report must be there and 8-byte aligned");
+    if (const char *why = bad_report(d_report)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     hipLaunchKernelGGL(theta_table_kernel, dim3((MULT_BINS + THREADS - 1) / THREADS, THETA_TABLES), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
@@ -244,10 +199,9 @@ int aesw_theta_compress_table_device(aesw_ctx *ctx, const uint8_t *d_theta, uint
 int aesw_theta_prepare(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, void *stream) {
     using namespace aesw_theta;
     const char *const call = "aesw_theta_prepare";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
-    if (!mult_k_ok(k)) return refuse(ctx, call, "k must be 2 ... 30");
-    if (!mult_sets_ok(n_sets)) return refuse(ctx, call, "n_sets must be 1 ... 1024");
+    if (int rc = entry_refused(ctx, call)) return rc;
+    if (const char *why = bad_k(k)) return refuse(ctx, call, why);
+    if (const char *why = bad_sets(n_sets)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     void *ws = nullptr;
@@ -258,20 +212,18 @@ int aesw_theta_inputs_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_
                              const uint8_t *d_z, const aesw_key_slab *d_key_slab, uint32_t *d_in, aesw_mult_report *d_report, void *stream) {
     using namespace aesw_theta;
     const char *const call = "aesw_theta_inputs_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
-    if (layout != AESW_LAYOUT_DENSE && layout != AESW_LAYOUT_PACKED) return refuse(ctx, call, "the layout must be DENSE or PACKED (a VALUES witness has no x)");
-    if (!mult_k_ok(k)) return refuse(ctx, call, "k must be 2 ... 30");
-    if (!mult_sets_ok(n_sets)) return refuse(ctx, call, "n_sets must be 1 ... 1024");
+    if (int rc = entry_refused(ctx, call)) return rc;
+    if (const char *why = bad_layout(layout)) return refuse(ctx, call, why);
+    if (const char *why = bad_k(k)) return refuse(ctx, call, why);
+    if (const char *why = bad_sets(n_sets)) return refuse(ctx, call, why);
     const Placement place(k);
     if (n_blocks > place.total(n_sets)) return refuse(ctx, call, "n_blocks is more than the circuit holds", AESW_ERR_CAPACITY);
     if (!d_in || !aligned_to(d_in, 16)) return refuse(ctx, call, "d_in must be there and 16-byte aligned");
-    if (!d_report || !aligned_to(d_report, 8)) return refuse(ctx, call, "d_report must be there and 8-byte aligned");
+    if (const char *why = bad_report(d_report)) return refuse(ctx, call, why);
     if (n_blocks && (!d_x || !d_y || !d_z)) return refuse(ctx, call, "d_x, d_y and d_z must be there");
     if (!aligned_to(d_x, 16) || !aligned_to(d_y, 16) || !aligned_to(d_z, 16)) return refuse(ctx, call, "d_x, d_y and d_z must be 16-byte aligned");
     const aesw_key_slab *ks = d_key_slab;
-    const bool with_keys = ks && ks->kx && ks->ky && ks->kz && mult_has_key_rows(k);
-    if (with_keys && (!aligned_to(ks->kx, 16) || !aligned_to(ks->ky, 16) || !aligned_to(ks->kz, 16))) return refuse(ctx, call, "the key columns must be 16-byte aligned");
+    if (const char *why = bad_key_columns(ks, k)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -283,7 +235,7 @@ int aesw_theta_inputs_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint64_
     if (rc != AESW_OK) return rc;
     InputParams p{};
     p.x = d_x; p.y = d_y; p.z = d_z;
-    if (with_keys) { p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
+    if (with_keys(ks, k)) { p.kx = ks->kx; p.ky = ks->ky; p.kz = ks->kz; }
     p.tab768 = ctx->d_tables;
     p.in = d_in;
     p.parts = static_cast<u32x4 *>(ws);
@@ -304,10 +256,9 @@ int aesw_theta_columns_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32
                               const uint8_t *d_table_fr, uint8_t *d_out_fr, void *stream) {
     using namespace aesw_theta;
     const char *const call = "aesw_theta_columns_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
+    if (int rc = entry_refused(ctx, call)) return rc;
     if (k < 17 || k > MULT_MAX_K) return refuse(ctx, call, "k must be 17 ... 30 (2^k rows hold the table)");
-    if (!mult_sets_ok(n_sets)) return refuse(ctx, call, "n_sets must be 1 ... 1024");
+    if (const char *why = bad_sets(n_sets)) return refuse(ctx, call, why);
     if (n_rows < MULT_BINS || n_rows > (1u << k)) return refuse(ctx, call, "n_rows must be 66561 ... 2^k");
     if (pad_row >= MULT_BINS) return refuse(ctx, call, "pad_row must be a table row, 0 ... 66560");
     if (!aligned_to(d_index, 4)) return refuse(ctx, call, "d_index must be 4-byte aligned");
@@ -319,10 +270,7 @@ int aesw_theta_columns_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32
     const dim3 grid((unsigned)(((uint64_t)n_rows * 2 + THREADS - 1) / THREADS), n_sets * THETA_TAGS);
     const u32x4 *tables = reinterpret_cast<const u32x4 *>(d_table_fr);
     u32x4 *out = reinterpret_cast<u32x4 *>(d_out_fr);
-    const int64_t nt = ctx->opt.fr_nt;
-    if (nt == 2) hipLaunchKernelGGL(theta_columns_kernel<2>, grid, dim3(THREADS), 0, s, d_index, tables, out, k, n_rows, pad_row);
-    else if (nt == 1) hipLaunchKernelGGL(theta_columns_kernel<1>, grid, dim3(THREADS), 0, s, d_index, tables, out, k, n_rows, pad_row);
-    else hipLaunchKernelGGL(theta_columns_kernel<0>, grid, dim3(THREADS), 0, s, d_index, tables, out, k, n_rows, pad_row);
+    with_nt((int)ctx->opt.fr_nt, [&](auto n) { hipLaunchKernelGGL(theta_columns_kernel<AESW_V(n)>, grid, dim3(THREADS), 0, s, d_index, tables, out, k, n_rows, pad_row); });
     HIP_TRY(ctx, hipGetLastError());
     return AESW_OK;
 }

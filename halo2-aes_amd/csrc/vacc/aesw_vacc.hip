@@ -7,7 +7,7 @@
 //     pair of workgroups per chunk, each counting the bins of its half in LDS and ADDING them to the histogram of the set -- over
 //     a block's 448 y + 608 z + 16 plaintext bytes and the circuit's 176 round-key cells: 17 row steps per lane, no x column;
 //   * the table, in the code object's own storage, filled once per device;
-//   * the entry points: their checks and the launch.
+//   * the entry points: the checks that are theirs alone (the preamble and the shared rules are aesw_entry.h's) and the launch.
 // The reset and the key slab's own 400 rows are libaesw_acc.so's (the key slabs of VALUES are the packed ones): nothing of them
 // is restated here.
 #include <hip/hip_runtime.h>
@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../../include/aesw_vacc.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
 #include "../aesw_mult_dev.h"
 #include "../aesw_run.h"
 #include "../aesw_vacc.h"
@@ -166,8 +166,7 @@ int aesw_vacc_add_device_chunk(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint6
     using namespace aesw_vacc;
     static_assert(sizeof(aesw_mult_report) == 3 * sizeof(uint64_t), "the kernel addresses the report as three u64");
     const char *const call = "aesw_vacc_add_device";
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, call);
-    if (!ctx) return AESW_ERR_INVALID_ARG;
+    if (int rc = entry_refused(ctx, call)) return rc;
     if (const char *why = bad_outputs(k, true, n_sets, d_mult, d_report)) return refuse(ctx, call, why);
     const Placement place(k);
     const uint64_t cap = place.total(n_sets);
@@ -208,8 +207,7 @@ uint32_t aesw_vacc_default_chunk(uint32_t /*k*/, uint32_t /*n_sets*/, uint64_t /
 }
 
 int aesw_vacc_prepare(aesw_ctx *ctx) {
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_vacc_prepare");
-    if (!ctx) return AESW_ERR_INVALID_ARG;
+    if (int rc = aesw::entry_refused(ctx, "aesw_vacc_prepare")) return rc;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     const uint32_t *t = nullptr;

@@ -20,7 +20,7 @@
 
 #include "../../../include/aesw_vals.h"
 #include "../aesw_check_dev.h"
-#include "../aesw_ctx.h"
+#include "../aesw_entry.h"
 #include "../aesw_vals_check.h"
 
 namespace aesw_vals {
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(256) vals_check_kernel(const CheckParams a) {
 // The report starts as (0 blocks, 0 keys, no failures, first = none): a kernel node, not memset nodes, so a captured graph
 // replays it as it runs eagerly.
 __global__ void __launch_bounds__(64) vals_report_init_kernel(uint64_t *report) {
-    if (threadIdx.x < 7) report[threadIdx.x] = threadIdx.x == 6 ? ~0ull : 0ull;
+    report_reset(report, 7, 1u << 6, threadIdx.x);
 }
 
 static hipError_t launch_vals_check(const CheckParams &p, hipStream_t s) {
@@ -152,8 +152,8 @@ int aesw_vals_check_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_
                            const uint8_t *d_z, const uint8_t *d_ct, const aesw_key_slab *d_key_slab, aesw_check_report *d_report,
                            void *stream) {
     static_assert(sizeof(aesw_check_report) == 7 * sizeof(uint64_t), "the kernel addresses the report as seven u64");
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_vals_check_device");
-    if (!ctx || !d_report || !aligned_to(d_report, 8)) return AESW_ERR_INVALID_ARG;
+    if (int rc = aesw::entry_refused(ctx, "aesw_vals_check_device")) return rc;
+    if (!d_report || !aligned_to(d_report, 8)) return AESW_ERR_INVALID_ARG;
     const aesw_key_slab *ks = d_key_slab;
     if (!key_slab_ok(ks) || !aligned_to(d_keys, 4)) return AESW_ERR_INVALID_ARG;
     if (per_block_keys && n && !d_keys) return AESW_ERR_INVALID_ARG;
@@ -177,8 +177,7 @@ int aesw_vals_check_device(aesw_ctx *ctx, const uint8_t *d_pt, const uint8_t *d_
 }
 
 int aesw_vals_prepare(aesw_ctx *ctx) {
-    if (aesw_is_group(ctx)) return aesw_group_refuse(ctx, "aesw_vals_prepare");
-    if (!ctx) return AESW_ERR_INVALID_ARG;
+    if (int rc = aesw::entry_refused(ctx, "aesw_vals_prepare")) return rc;
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;
     const uint32_t *t = nullptr;

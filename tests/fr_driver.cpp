@@ -2,6 +2,7 @@
 //   fr_driver IN OUT   IN: n records of two cells (64 bytes); OUT: per record fr_mul | fr_add (64 bytes) and, after all records,
 //                      n bytes: bit 0 / bit 1 = fr_is_canonical of the first / the second cell.
 // fr_mul and fr_add are only called on canonical pairs; the other records get zero cells.
+//   fr_driver --byte-table OUT   OUT: the 256 cells of fr_byte_table(), 8 192 bytes
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -11,6 +12,13 @@
 int main(int argc, char **argv) {
     using namespace aesw;
     if (argc != 3) return 2;
+    if (!std::strcmp(argv[1], "--byte-table")) {
+        const FrByteTable t = fr_byte_table();
+        FILE *o = std::fopen(argv[2], "wb");
+        if (!o || std::fwrite(t.cell, 1, sizeof t.cell, o) != sizeof t.cell) return 2;
+        std::fclose(o);
+        return 0;
+    }
     FILE *f = std::fopen(argv[1], "rb");
     if (!f) return 2;
     std::vector<unsigned char> in;

@@ -2,7 +2,9 @@
 against Python integers.  A cell holds v * 2^256 mod r; fr_mul(a, b) is a * b / 2^256 mod r on the cells' integers, fr_add their
 sum mod r.  Every pair of {0, 1, 2, r - 1, r - 2, 2^253, (r - 1) / 2, the Montgomery form of 1, 2 000 seeded random canonical
 values}; operands whose limbs are all 0xffffffff below the top, so that every carry runs; r, r + 1 and 2^256 - 1 are not
-canonical; the same driver once more as a stand-alone program under AddressSanitizer and UBSan."""
+canonical; the same driver once more as a stand-alone program under AddressSanitizer and UBSan.  The byte table
+(fr_byte_table: cell v = v * 2^256 mod r) cell for cell, and through the built columns checker, which fills its table from it."""
+import ctypes
 import subprocess
 from pathlib import Path
 
@@ -98,6 +100,24 @@ def test_what_is_not_below_r_is_not_canonical(driver, tmp):
     assert [int(f) & 1 for f in flags] == [0, 0, 0, 1, 1, 0, 0] and all(int(f) >> 1 == 1 for f in flags)
     _mul, _add, flags = run(driver, tmp, [0] * len(probes), probes)
     assert [int(f) >> 1 for f in flags] == [0, 0, 0, 1, 1, 0, 0]
+
+
+def test_the_byte_table_is_every_byte_value_in_montgomery_form(driver, tmp, pkg):
+    want = b"".join(((v << 256) % R).to_bytes(32, "little") for v in range(256))
+    subprocess.run([str(driver), "--byte-table", str(tmp / "table.bin")], check=True)
+    got = (tmp / "table.bin").read_bytes()
+    assert len(got) == 256 * 32
+    for v in range(256):
+        assert got[32 * v:32 * v + 32] == want[32 * v:32 * v + 32], v
+    # the built library fills its table from the header: the same bytes, and the hash the search found over them before
+    lib = pkg.api.load_cols_library()
+    table, inv = (ctypes.c_uint8 * 8192)(), (ctypes.c_uint8 * 4096)()
+    lib.aesw_cols_fr_table(table)
+    assert bytes(table) == want
+    mul, bits = ctypes.c_uint32(), ctypes.c_uint32()
+    assert lib.aesw_cols_hash_search(table, ctypes.byref(mul), ctypes.byref(bits), inv) == 0
+    assert (mul.value, bits.value) == (0x309119E3, 8)  # read once from the library as it was built with its own U256 copy
+    assert sorted(inv[((int.from_bytes(want[32 * v:32 * v + 4], "little") * mul.value) & 0xFFFFFFFF) >> (32 - bits.value)] for v in range(256)) == list(range(256))
 
 
 def test_the_driver_runs_clean_under_address_and_ub_sanitizers(tmp, values):

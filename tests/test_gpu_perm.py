@@ -199,6 +199,19 @@ def test_an_overflowing_section_is_clamped_and_reported(pkg, ctx):
     assert q.report() == {"arguments": 10, "overflowed": 0, "first_overflow": None}
 
 
+def test_the_report_over_more_arguments_than_its_workgroup_has_threads(pkg, ctx):
+    """52 sets are 260 arguments: the 256 threads that write the report walk the overflow flags in two turns, and the one
+    overflow there is arrives through an argument with an index of 256 or more."""
+    u, n_sets = 1 << 17, 52
+    plain = composite("random", u, seed=31)
+    hists = np.stack([plain] * (n_sets - 1) + [composite({4: "over1"}, u, seed=32)])
+    p = Perm(pkg, ctx, G.DeviceArena(), 17, n_sets)
+    p.build(upload(hists), u, 0)
+    verify(p, hists, u, 0, "260 arguments", only={(st, tag) for st in (0, n_sets - 1) for tag in pm.TAGS})
+    assert (n_sets - 1) * 5 + 4 - 1 >= 256
+    assert p.report() == {"arguments": 260, "overflowed": 1, "first_overflow": (n_sets - 1, 4)}
+
+
 def test_a_pad_row_inside_the_section(pkg, ctx):
     u = 66564 + 1000
     hist = composite("random", u, seed=31)

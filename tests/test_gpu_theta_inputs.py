@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 OK, INVALID, CAPACITY = 0, 1, 5
 DENSE, PACKED, VALUES = 0, 1, 2
 AES_ROWS, KEY_ROWS = 1360, 400
+ORACLE_MAX_SETS = 64  # oracle/aesw_oracle.c: MAX_SETS
 
 
 class World:
@@ -33,7 +34,9 @@ class World:
         self.w = {l: ctx.encrypt_witness(d_pt, d_key, l) if n else pkg.Witness(empty(), empty(), empty(), None, None) for l in (DENSE, PACKED)}
         self.kw = {l: ctx.key_schedule_witness(d_key.reshape(1, 16), l, want_rk=False) for l in (DENSE, PACKED)}
         torch.cuda.synchronize()
-        if k >= 11:
+        if k >= 11 and n_sets > ORACLE_MAX_SETS:
+            self.advice, self.sel = self.from_slabs(oracle, key, pt), pkg.assemble_selectors(k, n_sets, n)[0]
+        elif k >= 11:
             with oracle.circuit(k, n_sets, key, pt, record_copies=False) as c:
                 assert c.status == 0
                 self.advice = np.stack([c.advice(i) for i in range(3 * n_sets + 1)])
@@ -46,6 +49,20 @@ class World:
                     self.advice[c, :KEY_ROWS] = self.kw[DENSE][1 + c].cpu().numpy()
             self.sel = pkg.assemble_selectors(k, n_sets, 0)[0]
         self.tables = oracle.tables()
+
+    def from_slabs(self, oracle, key, pt):
+        """The advice matrix without the oracle's circuit (which holds at most ORACLE_MAX_SETS sets): the oracle's DENSE slabs, the
+        key slab at the key rows and block b at block_placement(b).  The model reads no cell of the words column."""
+        k, n_sets, n = self.k, self.n_sets, self.n
+        advice = np.zeros((3 * n_sets + 1, 1 << k), np.uint8)
+        w, kw = oracle.encrypt_witness(pt, key, layout=DENSE), oracle.key_schedule_witness(key, layout=DENSE)
+        for c, name in enumerate(("kx", "ky", "kz")):
+            advice[c, :KEY_ROWS] = getattr(kw, name)[:KEY_ROWS]
+        for b in range(n):
+            st, first = self.pkg.block_placement(k, n_sets, b)
+            for c, name in enumerate("xyz"):
+                advice[3 * st + c, first:first + AES_ROWS] = getattr(w, name)[b * AES_ROWS:(b + 1) * AES_ROWS]
+        return advice
 
     def expected(self, keyed=True, advice=None):
         sel = self.sel.copy()
@@ -189,6 +206,41 @@ def test_planted_misses_mark_their_cell_and_nothing_else(pkg, ctx, oracle, layou
         assert all(got[at] == tm.MISS for at in cells)
         first = min(keys)
         assert rep == {"lookups": lookups, "misses": len(case), "first_miss": (first >> 20, bool(first >> 19 & 1), first & 0xFFFF)}, rep
+
+
+def test_a_report_folded_from_more_parts_than_its_workgroup_has_threads(pkg, ctx, oracle):
+    """k = 14 with 65 sets: 16 workgroups x 65 sets = 1 040 parts, so the 1 024 threads of theta_report_kernel walk the parts in two
+    turns.  Blocks fill the sets in order, so a block of the last set needs every set in front of it full: all 778 blocks.  One
+    miss in the last block, whose set's parts have indices 1 024 ... 1 039: the report's misses and first_miss arrive through
+    one of them.  The oracle builds no circuit of 65 sets; the advice comes from its slabs (World.from_slabs), which is held
+    against its circuit where it builds one."""
+    small = world(pkg, ctx, oracle, 12, 3, pkg.block_capacity(12, 3))
+    rng = np.random.default_rng(1000 * 12 + 10 * 3 + small.n)  # World's own key and plaintexts
+    key, pt = rng.integers(0, 256, 16, dtype=np.uint8), rng.integers(0, 256, (small.n, 16), dtype=np.uint8)
+    assert np.array_equal(small.from_slabs(oracle, key, pt)[:9], small.advice[:9])
+    assert np.array_equal(pkg.assemble_selectors(12, 3, small.n)[0], small.sel)
+
+    k, n_sets = 14, 65
+    n = pkg.block_capacity(k, n_sets)
+    assert n == 778 and -(-(1 << k) // 1024) * n_sets == 1040
+    w = world(pkg, ctx, oracle, k, n_sets, n)
+    clean, lookups, none = w.expected()
+    assert none == 0 and lookups == 1056 * n + 400
+    st, first = pkg.block_placement(k, n_sets, n - 1)
+    assert st == n_sets - 1 and st * 16 >= 1024
+    r = 1344  # an xor row: z
+    for layout in (PACKED, DENSE):
+        at = r if layout == DENSE else int(oracle.packed_index(2)[r])
+        slabs, advice = [t.clone() for t in w.w[layout][:3]], w.advice.copy()
+        slabs[2][(n - 1) * pkg.column_stride(layout, 2) + at] ^= 0x21
+        advice[3 * st + 2, first + r] ^= 0x21
+        c = Call(w, G.DeviceArena(G.CANARIES[layout]))
+        c.run(layout, slabs=slabs)
+        got, rep = c.result()
+        exp, _, misses = w.expected(advice=advice)
+        same(got, exp, (k, n_sets, layout))
+        assert misses == 1 and [tuple(x) for x in np.argwhere(got != clean)] == [(st, 1, first + r)] and got[st, 1, first + r] == tm.MISS
+        assert rep == {"lookups": lookups, "misses": 1, "first_miss": (n - 1, False, r)}, rep
 
 
 def test_identical_blocks(pkg, ctx, oracle):

@@ -95,7 +95,9 @@ def test_the_other_libraries_are_left_alone(pkg):
             assert "aesw_vacc" not in header.read_text(), header.name
     # every refusal of VALUES stays, by name
     acc = (cl.ROOT / "halo2-aes_amd" / "csrc" / "acc" / "aesw_acc.hip").read_text()
-    assert acc.count("the layout must be DENSE or PACKED (a VALUES witness has no x)") == 2
+    rules = (cl.ROOT / "halo2-aes_amd" / "csrc" / "aesw_entry_rules.h").read_text()
+    said = "the layout must be DENSE or PACKED (a VALUES witness has no x)"
+    assert acc.count("bad_layout(layout)") == 2 and rules.count(said) == 1  # both entry points that take a layout; the text, once
 
 
 def test_a_group_refuses(pkg):
