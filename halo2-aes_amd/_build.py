@@ -13,6 +13,8 @@
                                   takes.  All are built by build_satellite() alike.
   halo2-aes_amd/libaesw_theta.so  the one entry of FIELD_LIBRARIES: the lookup arguments compressed under theta
                                   (include/aesw_theta.h), built by build_satellite() as well
+  halo2-aes_amd/libaesw_grand.so  the first entry of ARGUMENT_LIBRARIES: the grand product Z of every lookup argument from
+                                  beta and gamma (include/aesw_grand.h), built by build_satellite() as well
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -129,19 +131,41 @@ CIRC_LIB, COLS_LIB, VALS_LIB, ACC_LIB, PERM_LIB, VACC_LIB, MULT_LIB = (PKG / ("l
 
 # The libraries that do field arithmetic (csrc/aesw_fr.h), entries of the same shape.  A table of their own: SATELLITES is the
 # seven libraries that move bytes and row indices and never touch Fr -- its length, its order and the tuple unpacked below it
-# are held by the library tests of its entries -- while what follows theta (the compression here, the grand product next)
-# shares the field header and grows here.  build_satellite() looks a name up in either; __graft_entry__.build() walks both.
+# are held by the library tests of its entries.  This table is the compression under theta alone -- the test of its entry holds
+# it at that -- and what needs the later challenges lives in ARGUMENT_LIBRARIES below.  build_satellite() looks a name up in
+# all three tables (library_entry); __graft_entry__.build() walks library_names().
 FIELD_LIBRARIES = {
     "theta": ([CSRC / "theta" / "aesw_theta.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_theta.h", CSRC / "aesw_mult.h", INCLUDE / "aesw_mult.h"],
               INCLUDE / "aesw_theta.h"),
 }
 THETA_LIB = PKG / "libaesw_theta.so"
 
+# What needs beta and gamma: the libraries that work on the lookup arguments once those challenges are known, entries of the
+# same shape.  They share the field header and the rules of theta (which table an argument reads, the row-order table index).
+ARGUMENT_LIBRARIES = {
+    "grand": ([CSRC / "grand" / "aesw_grand.hip"],
+              [CSRC / "aesw_fr.h", CSRC / "aesw_grand.h", CSRC / "aesw_theta.h", CSRC / "aesw_mult.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_grand.h"),
+}
+GRAND_LIB = PKG / "libaesw_grand.so"
+
+
+def library_names() -> list:
+    """Every library build_satellite() builds, in the order of the three tables."""
+    return list(SATELLITES) + list(FIELD_LIBRARIES) + list(ARGUMENT_LIBRARIES)
+
+
+def library_entry(name: str):
+    """(sources, headers beyond SATELLITE_HEADERS, public header) of `name`, whichever of the three tables holds it."""
+    for table in (SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
+
 
 def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
-    """libaesw_<name>.so of an entry of SATELLITES or FIELD_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
+    """libaesw_<name>.so of an entry of SATELLITES, FIELD_LIBRARIES or ARGUMENT_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
     A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are.  With `extra_flags` and
     another `out` (a file name next to libaesw.so) a measurement variant of it (tools/vacc_bench.py: -DAESW_VACC_WAVES=16)."""
-    sources, headers, public = SATELLITES[name] if name in SATELLITES else FIELD_LIBRARIES[name]
+    sources, headers, public = library_entry(name)
     return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
                   lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)

@@ -26,6 +26,7 @@ ACC_LIB_PATH = _PKG / "libaesw_acc.so"    # the lookup multiplicities of one cir
 VACC_LIB_PATH = _PKG / "libaesw_vacc.so"  # the same accumulated from a VALUES witness (include/aesw_vacc.h)
 PERM_LIB_PATH = _PKG / "libaesw_perm.so"  # plookup's permuted columns arranged from the multiplicities (include/aesw_perm.h)
 THETA_LIB_PATH = _PKG / "libaesw_theta.so"  # the lookup arguments compressed under theta (include/aesw_theta.h)
+GRAND_LIB_PATH = _PKG / "libaesw_grand.so"  # the grand product Z of every lookup argument from beta and gamma (include/aesw_grand.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -244,6 +245,13 @@ THETA_SYMBOLS = {
     "aesw_theta_prepare": (_I, [_P, _U32, _U32, _P]),
     "aesw_theta_columns_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _P]),
 }
+
+# include/aesw_grand.h
+GRAND_SYMBOLS = {
+    "aesw_grand_invert_table_device": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "aesw_grand_workspace_bytes": (C.c_size_t, [_U32, _U32]),
+    "aesw_grand_product_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
 
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
@@ -260,6 +268,7 @@ _LIBRARIES = {
     "vacc": (VACC_LIB_PATH, VACC_SYMBOLS, _NO_FALLBACK),
     "perm": (PERM_LIB_PATH, PERM_SYMBOLS, _NO_FALLBACK),
     "theta": (THETA_LIB_PATH, THETA_SYMBOLS, _NO_FALLBACK),
+    "grand": (GRAND_LIB_PATH, GRAND_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -346,6 +355,11 @@ def load_theta_library(path: Path | None = None) -> C.CDLL:
     return _load("theta", path)
 
 
+def load_grand_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_grand.so (in-tree): the lookup grand product behind Context.invert_table and Context.grand_product."""
+    return _load("grand", path)
+
+
 def fr_cell(value: int) -> np.ndarray:
     """uint8[32]: the Fr cell of `value` (any int, reduced mod r) -- value * 2^256 mod r, little-endian."""
     return np.frombuffer(((int(value) % FR_MODULUS << 256) % FR_MODULUS).to_bytes(32, "little"), np.uint8).copy()
@@ -423,6 +437,19 @@ def theta_report_dict(rep) -> dict:
     """The uint64[2] report tensor of Context.compress_table(sync=False), read back, as the dict sync=True returns."""
     v = _words(rep)
     return {"cells": v[0], "noncanonical": bool(v[1])}
+
+
+def grand_invert_report_dict(rep) -> dict:
+    """The uint64[3] report tensor of Context.invert_table(sync=False), read back, as the dict sync=True returns."""
+    v = _words(rep)
+    return {"cells": v[0], "noncanonical": bool(v[1]), "zero_terms": v[2]}
+
+
+def grand_report_dict(rep) -> dict:
+    """The uint64[3] report tensor of Context.grand_product(sync=False), read back, as the dict sync=True returns: arguments,
+    open and first_open = None or (set, tag)."""
+    v = _words(rep)
+    return {"arguments": v[0], "open": v[1], "first_open": None if v[2] == _NONE else (v[2] >> 3, v[2] & 7)}
 
 
 def perm_report_dict(rep) -> dict:
@@ -1143,10 +1170,7 @@ class Context:
         is zero and the report says so.  _out is a tensor to write into (tests, tools)."""
         lib = load_theta_library()
         torch = self._torch()
-        if isinstance(theta, int):
-            theta = torch.from_numpy(fr_cell(theta)).to(self._dev())
-        if tuple(self._u8(theta, "theta").shape) != (32,):
-            raise ValueError("theta must be an int or a uint8[32] tensor")
+        theta = self._challenge(theta, "theta")
         shape = (3, K.TABLE_ROWS, 32)
         if _out is None:
             _out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
@@ -1220,6 +1244,80 @@ class Context:
                                            None if index is None else index.data_ptr(), table_fr.data_ptr(), out.data_ptr(), self._stream())
         self._check(rc, "aesw_theta_columns_device")
         return out
+
+    def _challenge(self, value, name):
+        """theta, beta or gamma as the calls that read a challenge take it: an int (Python's or numpy's; reduced mod r and put into
+        Montgomery form, one 32-byte upload per call) becomes its cell on the device, a uint8[32] tensor stays."""
+        if isinstance(value, (int, np.integer)):
+            value = self._torch().from_numpy(fr_cell(value)).to(self._dev())
+        if tuple(self._u8(value, name).shape) != (32,):
+            raise ValueError("%s must be an int or a uint8[32] tensor" % name)
+        return value
+
+    def invert_table(self, table_fr, beta, gamma, sync: bool = True, _out=None):
+        """The inverse table of the lookup grand product (aesw_grand_invert_table_device, libaesw_grand.so): (inv_fr, report) with
+        inv_fr a uint8 [2, 3, 66561, 32] tensor -- plane 0 inv(table_fr[j][r] + beta), plane 1 inv(table_fr[j][r] + gamma), inv(0)
+        = 0 -- and report the dict of grand_invert_report_dict after synchronising the stream, or with sync=False the uint64[3]
+        device tensor.  table_fr: what compress_table returns.  beta, gamma: ints (reduced mod r and put into Montgomery form
+        here), or uint8[32] tensors on the device holding the cells as they lie, read when the kernel runs; if one is not
+        canonical every cell is zero and the report says so.  _out is a tensor to write into (tests, tools)."""
+        lib = load_grand_library()
+        torch = self._torch()
+        if tuple(self._u8(table_fr, "table_fr").shape) != (3, K.TABLE_ROWS, 32):
+            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((3, K.TABLE_ROWS, 32),))
+        beta, gamma = self._challenge(beta, "beta"), self._challenge(gamma, "gamma")
+        shape = (2, 3, K.TABLE_ROWS, 32)
+        if _out is None:
+            _out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(_out, "_out").shape) != shape:
+            raise ValueError("_out must be a uint8 tensor of shape %r" % (shape,))
+        rep = torch.empty(3, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_grand_invert_table_device(self._h, table_fr.data_ptr(), beta.data_ptr(), gamma.data_ptr(), _out.data_ptr(), rep.data_ptr(),
+                                                self._stream())
+        self._check(rc, "aesw_grand_invert_table_device")
+        return _out, self._report(rep, sync, grand_invert_report_dict)
+
+    def grand_product(self, k: int, n_sets: int, inputs, a, s, table_fr, inv_fr, beta, gamma, n_rows: int | None = None, pad_row: int = 0,
+                      sync: bool = True, _out=None, _workspace=None):
+        """The grand product Z of all 5 * n_sets lookup arguments of one circuit (aesw_grand_product_device): (z, closing, report)
+        with z a uint8 [n_sets, 5, 2^k, 32] tensor of which rows 0 ... min(n_rows, 2^k - 1) are written (n_rows: the usable rows,
+        default 2^k; row n_rows holds the closing product, the rest is the host's blinding rows), closing the uint8 [n_sets, 5, 32]
+        closing products and report the dict of grand_report_dict after synchronising the stream, or with sync=False the
+        uint64[3] device tensor.  inputs: the int32 [n_sets, 5, 2^k] index column of lookup_inputs; a, s: those of
+        permuted_columns; table_fr: what compress_table returns; inv_fr: what invert_table returns for the same beta and gamma
+        (ints, or uint8[32] device tensors read when the kernels run).  The workspace is allocated per call and handed back to
+        the caching allocator in stream order; _workspace is a uint8 tensor of workspace_bytes to use instead (a capture that
+        prepares it beforehand), _out a (z, closing) pair to write into (tests, tools)."""
+        lib = load_grand_library()
+        torch = self._torch()
+        k, n_sets = int(k), int(n_sets)
+        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 and 0 < n_sets <= 1024 else (0,)
+        for name, t in (("inputs", inputs), ("a", a), ("s", s)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.device.index != self.device:
+                raise TypeError("%s must be an int32 tensor on cuda:%d" % (name, self.device))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous int32 tensor of shape %r" % (name, shape))
+        if tuple(self._u8(table_fr, "table_fr").shape) != (3, K.TABLE_ROWS, 32):
+            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((3, K.TABLE_ROWS, 32),))
+        if tuple(self._u8(inv_fr, "inv_fr").shape) != (2, 3, K.TABLE_ROWS, 32):
+            raise ValueError("inv_fr must be a uint8 tensor of shape %r" % ((2, 3, K.TABLE_ROWS, 32),))
+        beta, gamma = self._challenge(beta, "beta"), self._challenge(gamma, "gamma")
+        if _out is None:
+            _out = (torch.empty(shape + (32,), dtype=torch.uint8, device=self._dev()), torch.empty(shape[:2] + (32,), dtype=torch.uint8, device=self._dev()))
+        if tuple(self._u8(_out[0], "_out").shape) != shape + (32,) or tuple(self._u8(_out[1], "_out").shape) != shape[:2] + (32,):
+            raise ValueError("_out must be uint8 tensors of shapes %r and %r" % (shape + (32,), shape[:2] + (32,)))
+        need = int(lib.aesw_grand_workspace_bytes(k, n_sets))
+        if _workspace is None:
+            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
+            _workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=self._dev())
+        elif self._u8(_workspace, "_workspace").numel() < need:
+            raise ValueError("_workspace must hold %d bytes" % need)
+        rep = torch.empty(3, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_grand_product_device(self._h, k, n_sets, (1 << k) if n_rows is None else int(n_rows), int(pad_row), inputs.data_ptr(), a.data_ptr(),
+                                           s.data_ptr(), table_fr.data_ptr(), inv_fr.data_ptr(), beta.data_ptr(), gamma.data_ptr(), _out[0].data_ptr(),
+                                           _out[1].data_ptr(), _workspace.data_ptr(), rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_grand_product_device")
+        return _out[0], _out[1], self._report(rep, sync, grand_report_dict)
 
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
@@ -1554,7 +1652,7 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
               "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values",
               "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr",
-              "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns"):
+              "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 

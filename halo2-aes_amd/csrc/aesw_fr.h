@@ -1,5 +1,5 @@
 // aesw_fr.h -- bn256's scalar field Fr in Montgomery form, once, for host and device: the arithmetic behind the compression of
-// the lookup arguments under theta (theta/aesw_theta.hip) and what a grand product will need next.
+// the lookup arguments under theta (theta/aesw_theta.hip) and the lookup grand product (grand/aesw_grand.hip, 4.20).
 // A cell is 32 bytes: eight little-endian 32-bit limbs of v * 2^256 mod r -- the encoding of every Fr cell the project writes
 // (d_fr_lut of aesw_ctx.h holds the 256 byte values in this form), so a cell is loaded and stored as it lies.
 // fr_mul is the Montgomery product a * b / 2^256 mod r, CIOS over 32-bit limbs: every step is a uint64_t accumulation of
@@ -112,6 +112,42 @@ AESW_FR_HD constexpr Fr fr_mul(const Fr &a, const Fr &b) {
 constexpr Fr FR_ONE = {{0x4ffffffbu, 0xac96341cu, 0x9f60cd29u, 0x36fc7695u, 0x7879462eu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u}};
 static_assert(fr_is_canonical(FR_ONE) && fr_mul(FR_ONE, FR_ONE).l[0] == FR_ONE.l[0] && fr_mul(FR_ONE, FR_ONE).l[7] == FR_ONE.l[7],
               "the Montgomery form of 1 is the identity of fr_mul");
+
+AESW_FR_HD constexpr bool fr_is_zero(const Fr &a) {
+    uint32_t any = 0;
+    AESW_FR_UNROLL
+    for (int i = 0; i < FR_LIMBS; ++i) any |= a.l[i];
+    return any == 0;
+}
+// limb for limb: canonical cells are equal as field elements exactly when they are
+AESW_FR_HD constexpr bool fr_eq(const Fr &a, const Fr &b) {
+    uint32_t any = 0;
+    AESW_FR_UNROLL
+    for (int i = 0; i < FR_LIMBS; ++i) any |= a.l[i] ^ b.l[i];
+    return any == 0;
+}
+
+// a^(r - 2): the inverse of a canonical a in Montgomery form (Fermat), and 0 for 0 -- the convention of ff's batch_invert.
+// A fixed square-and-multiply over the constant exponent, highest bit first, by loops that stay loops (two products of code; 256
+// squarings and one product per set bit of time); the limb of the exponent is chosen among constants, not read from an array.
+// One call per batch of a Montgomery inversion (aesw_grand.h), never one per cell.
+AESW_FR_HD constexpr uint32_t fr_inv_exponent_limb(int i) {  // limb i of r - 2: the lowest limb of r is above 2, nothing borrows
+    return i == 0 ? FR_MODULUS.l[0] - 2u : i == 1 ? FR_MODULUS.l[1] : i == 2 ? FR_MODULUS.l[2] : i == 3 ? FR_MODULUS.l[3] : i == 4 ? FR_MODULUS.l[4]
+         : i == 5 ? FR_MODULUS.l[5] : i == 6 ? FR_MODULUS.l[6] : FR_MODULUS.l[7];
+}
+AESW_FR_HD constexpr Fr fr_inv(const Fr &a) {
+    Fr acc = FR_ONE;
+    for (int i = FR_LIMBS - 1; i >= 0; --i) {
+        const uint32_t e = fr_inv_exponent_limb(i);
+        for (int b = 31; b >= 0; --b) {
+            acc = fr_mul(acc, acc);
+            if (e >> b & 1u) acc = fr_mul(acc, a);
+        }
+    }
+    return acc;
+}
+// one evaluation at compile time (380 products); fr_inv(0) == 0 and the rest are tests/test_fr_inverse.py's
+static_assert(FR_MODULUS.l[0] >= 2u && fr_eq(fr_mul(fr_inv(fr_add(FR_ONE, FR_ONE)), fr_add(FR_ONE, FR_ONE)), FR_ONE), "fr_inv(2) * 2 is 1");
 
 // The 256 byte values as cells, cell v = v * 2^256 mod r: what d_fr_lut (aesw_ctx.h) holds on the device and what the columns
 // checker inverts (aesw_cols_fr_table).  Little-endian limbs: on the hosts the project builds for, the table's bytes as they lie.
