@@ -15,6 +15,8 @@
                                   (include/aesw_theta.h), built by build_satellite() as well
   halo2-aes_amd/libaesw_grand.so  the first entry of ARGUMENT_LIBRARIES: the grand product Z of every lookup argument from
                                   beta and gamma (include/aesw_grand.h), built by build_satellite() as well
+  halo2-aes_amd/libaesw_sigma.so  the second entry of ARGUMENT_LIBRARIES: the grand products of the permutation argument from
+                                  beta and gamma, sigma as a column of cell indices (include/aesw_sigma.h), built alike
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -140,13 +142,16 @@ FIELD_LIBRARIES = {
 }
 THETA_LIB = PKG / "libaesw_theta.so"
 
-# What needs beta and gamma: the libraries that work on the lookup arguments once those challenges are known, entries of the
-# same shape.  They share the field header and the rules of theta (which table an argument reads, the row-order table index).
+# What needs beta and gamma: the libraries that build halo2's grand products once those challenges are known, entries of the
+# same shape.  "grand" (the lookup arguments) shares the field header and the rules of theta (which table an argument reads, the
+# row-order table index); "sigma" (the permutation argument) needs the field header and its own rules alone.
 ARGUMENT_LIBRARIES = {
     "grand": ([CSRC / "grand" / "aesw_grand.hip"],
               [CSRC / "aesw_fr.h", CSRC / "aesw_grand.h", CSRC / "aesw_theta.h", CSRC / "aesw_mult.h", INCLUDE / "aesw_mult.h"], INCLUDE / "aesw_grand.h"),
+    "sigma": ([CSRC / "sigma" / "aesw_sigma.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_sigma.h"], INCLUDE / "aesw_sigma.h"),
 }
 GRAND_LIB = PKG / "libaesw_grand.so"
+SIGMA_LIB = PKG / "libaesw_sigma.so"
 
 
 def library_names() -> list:

@@ -26,6 +26,7 @@ ACC_LIB_PATH = _PKG / "libaesw_acc.so"    # the lookup multiplicities of one cir
 VACC_LIB_PATH = _PKG / "libaesw_vacc.so"  # the same accumulated from a VALUES witness (include/aesw_vacc.h)
 PERM_LIB_PATH = _PKG / "libaesw_perm.so"  # plookup's permuted columns arranged from the multiplicities (include/aesw_perm.h)
 THETA_LIB_PATH = _PKG / "libaesw_theta.so"  # the lookup arguments compressed under theta (include/aesw_theta.h)
+SIGMA_LIB_PATH = _PKG / "libaesw_sigma.so"  # the grand products of the permutation argument from beta and gamma (include/aesw_sigma.h)
 GRAND_LIB_PATH = _PKG / "libaesw_grand.so"  # the grand product Z of every lookup argument from beta and gamma (include/aesw_grand.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
@@ -252,6 +253,16 @@ GRAND_SYMBOLS = {
     "aesw_grand_workspace_bytes": (C.c_size_t, [_U32, _U32]),
     "aesw_grand_product_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
+# include/aesw_sigma.h
+SIGMA_SYMBOLS = {
+    "aesw_sigma_columns": (_U32, [_U32]),
+    "aesw_sigma_sources_host": (_I, [_U32, _P]),
+    "aesw_sigma_mapping_host": (_I, [_U32, _U32, _U32, _P]),
+    "aesw_sigma_tables_bytes": (C.c_size_t, [_U32, _U32]),
+    "aesw_sigma_workspace_bytes": (C.c_size_t, [_U32, _U32, _U32]),
+    "aesw_sigma_tables_device": (_I, [_P, _U32, _U32, _P, _P]),
+    "aesw_sigma_product_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
 
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
@@ -269,6 +280,7 @@ _LIBRARIES = {
     "perm": (PERM_LIB_PATH, PERM_SYMBOLS, _NO_FALLBACK),
     "theta": (THETA_LIB_PATH, THETA_SYMBOLS, _NO_FALLBACK),
     "grand": (GRAND_LIB_PATH, GRAND_SYMBOLS, _NO_FALLBACK),
+    "sigma": (SIGMA_LIB_PATH, SIGMA_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -358,6 +370,40 @@ def load_theta_library(path: Path | None = None) -> C.CDLL:
 def load_grand_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_grand.so (in-tree): the lookup grand product behind Context.invert_table and Context.grand_product."""
     return _load("grand", path)
+
+
+def load_sigma_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_sigma.so (in-tree): the permutation argument's grand products behind Context.permutation_tables and
+    Context.permutation_product, and the host functions behind permutation_columns, permutation_sources and permutation_mapping."""
+    return _load("sigma", path)
+
+
+def permutation_columns(n_sets: int) -> int:
+    """aesw_sigma_columns: the columns of the permutation argument of a FixedAes128Config<k, n_sets> circuit, 3 * n_sets + 2."""
+    return int(load_sigma_library().aesw_sigma_columns(int(n_sets)))
+
+
+def permutation_sources(n_sets: int) -> np.ndarray:
+    """aesw_sigma_sources_host: uint32[3 * n_sets + 2] -- for each permutation column in halo2's order (x0 y0 z0 words rcon x1 ...)
+    the assembled advice column it is, or 3 * n_sets + 1 for the fixed round_constants column."""
+    out = np.zeros(3 * int(n_sets) + 2, np.uint32)
+    rc = load_sigma_library().aesw_sigma_sources_host(int(n_sets), _np_ptr(out))
+    if rc:
+        raise AeswError(rc, "aesw_sigma_sources_host")
+    return out
+
+
+def permutation_mapping(k: int, n_sets: int, n_blocks: int) -> np.ndarray:
+    """aesw_sigma_mapping_host: uint32[3 * n_sets + 2, 2^k] -- sigma of a circuit with one schedule_key and n_blocks encrypt calls
+    as cell indices, map[c][i] = c' * 2^k + i' (halo2's Assembly::copy over the copy graphs, include/aesw_sigma.h)."""
+    k, n_sets = int(k), int(n_sets)
+    if not (10 <= k <= 28 and 1 <= n_sets <= 1024 and (3 * n_sets + 2) << k <= 1 << 32):
+        raise AeswError(ERR_INVALID_ARG, "aesw_sigma_mapping_host")
+    out = np.zeros((3 * n_sets + 2, 1 << k), np.uint32)
+    rc = load_sigma_library().aesw_sigma_mapping_host(k, n_sets, int(n_blocks), _np_ptr(out))
+    if rc:
+        raise AeswError(rc, "aesw_sigma_mapping_host")
+    return out
 
 
 def fr_cell(value: int) -> np.ndarray:
@@ -450,6 +496,15 @@ def grand_report_dict(rep) -> dict:
     open and first_open = None or (set, tag)."""
     v = _words(rep)
     return {"arguments": v[0], "open": v[1], "first_open": None if v[2] == _NONE else (v[2] >> 3, v[2] & 7)}
+
+
+def sigma_report_dict(rep) -> dict:
+    """The uint64[6] report tensor of Context.permutation_product(sync=False), read back, as the dict sync=True returns: sets,
+    open, zero_terms, first_zero = None or (set, row), out_of_range, noncanonical.  (set, row) needs k: first_zero is left as the
+    word set * 2^k + row."""
+    v = _words(rep)
+    return {"sets": v[0], "open": bool(v[1]), "zero_terms": v[2], "first_zero": None if v[3] == _NONE else v[3], "out_of_range": v[4],
+            "noncanonical": bool(v[5])}
 
 
 def perm_report_dict(rep) -> dict:
@@ -1319,6 +1374,79 @@ class Context:
         self._check(rc, "aesw_grand_product_device")
         return _out[0], _out[1], self._report(rep, sync, grand_report_dict)
 
+    def permutation_tables(self, k: int, n_cols: int, _out=None):
+        """The power tables of the permutation argument (aesw_sigma_tables_device, libaesw_sigma.so), challenge free, once per
+        (k, n_cols): a uint8 [2^min(k, 14) + 2^max(k - 14, 0) + n_cols, 32] tensor -- omega^j, omega^(j * 2^14), delta^c."""
+        lib = load_sigma_library()
+        torch = self._torch()
+        k, n_cols = int(k), int(n_cols)
+        need = int(lib.aesw_sigma_tables_bytes(k, n_cols)) if 0 <= k < 2 ** 32 and 0 <= n_cols < 2 ** 32 else 0
+        if _out is None:
+            _out = torch.empty((max(need, 32) // 32, 32), dtype=torch.uint8, device=self._dev())
+        elif self._u8(_out, "_out").numel() < need:
+            raise ValueError("_out must hold %d bytes" % need)
+        rc = lib.aesw_sigma_tables_device(self._h, k, n_cols, _out.data_ptr(), self._stream())
+        self._check(rc, "aesw_sigma_tables_device")
+        return _out
+
+    def permutation_product(self, k: int, n_cols: int, chunk_len: int, advice_bytes, fixed_bytes, source, mapping, tables, beta, gamma,
+                            n_rows: int | None = None, sync: bool = True, _out=None, _workspace=None):
+        """The grand products Z of the permutation argument (aesw_sigma_product_device): (z, closing, report) with z a uint8
+        [S, 2^k, 32] tensor, S = ceil(n_cols / chunk_len), of which rows 0 ... min(n_rows, 2^k - 1) are written (n_rows: the usable
+        rows, default 2^k), closing the uint8 [S, 32] cells Z_s[n_rows] and report the dict of sigma_report_dict after
+        synchronising the stream, or with sync=False the uint64[6] device tensor.  advice_bytes: uint8 [n_advice, 2^k], what
+        assemble_advice gives with as_fr=False; fixed_bytes: uint8 [n_fixed, 2^k] or None; source: the uint32 [n_cols] column
+        choice (permutation_sources; a numpy array or an int32 device tensor); mapping: the [n_cols, 2^k] cell indices
+        (permutation_mapping; a numpy array is uploaded, an int32 device tensor stays); tables: what permutation_tables returns;
+        beta, gamma: ints, or uint8[32] device tensors read when the kernels run.  _workspace: a uint8 tensor of
+        aesw_sigma_workspace_bytes to use (a capture), _out a (z, closing) pair to write into (tests, tools)."""
+        lib = load_sigma_library()
+        torch = self._torch()
+        k, n_cols, chunk_len = int(k), int(n_cols), int(chunk_len)
+        rows = 1 << k if 0 <= k <= 28 else 0
+
+        def words(t, name, shape):
+            if isinstance(t, np.ndarray):
+                t = torch.from_numpy(np.ascontiguousarray(t, np.uint32).view(np.int32)).to(self._dev())
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.device.index != self.device:
+                raise TypeError("%s must be a numpy array or an int32 tensor on cuda:%d" % (name, self.device))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be contiguous and of shape %r" % (name, shape))
+            return t
+        source, mapping = words(source, "source", (n_cols,)), words(mapping, "mapping", (n_cols, rows))
+        n_advice = n_fixed = 0
+        if advice_bytes is not None:
+            if self._u8(advice_bytes, "advice_bytes").dim() != 2 or advice_bytes.shape[1] != rows:
+                raise ValueError("advice_bytes must be a uint8 tensor of shape [n_advice, %d]" % rows)
+            n_advice = advice_bytes.shape[0]
+        if fixed_bytes is not None:
+            if self._u8(fixed_bytes, "fixed_bytes").dim() != 2 or fixed_bytes.shape[1] != rows:
+                raise ValueError("fixed_bytes must be a uint8 tensor of shape [n_fixed, %d]" % rows)
+            n_fixed = fixed_bytes.shape[0]
+        need_tables = int(lib.aesw_sigma_tables_bytes(k, n_cols)) if k >= 0 and n_cols >= 0 else 0
+        if self._u8(tables, "tables").numel() < need_tables:
+            raise ValueError("tables must hold %d bytes" % need_tables)
+        beta, gamma = self._challenge(beta, "beta"), self._challenge(gamma, "gamma")
+        sets = -(-n_cols // chunk_len) if 1 <= chunk_len <= 8 and n_cols > 0 else 0
+        if _out is None:
+            _out = (torch.empty((sets, rows, 32), dtype=torch.uint8, device=self._dev()), torch.empty((sets, 32), dtype=torch.uint8, device=self._dev()))
+        if tuple(self._u8(_out[0], "_out").shape) != (sets, rows, 32) or tuple(self._u8(_out[1], "_out").shape) != (sets, 32):
+            raise ValueError("_out must be uint8 tensors of shapes %r and %r" % ((sets, rows, 32), (sets, 32)))
+        need = int(lib.aesw_sigma_workspace_bytes(k, n_cols, chunk_len)) if k >= 0 and n_cols >= 0 and chunk_len >= 0 else 0
+        if _workspace is None:
+            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
+            _workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=self._dev())
+        elif self._u8(_workspace, "_workspace").numel() < need:
+            raise ValueError("_workspace must hold %d bytes" % need)
+        rep = torch.empty(6, dtype=torch.int64, device=self._dev())
+        rc = lib.aesw_sigma_product_device(self._h, k, n_cols, chunk_len, rows if n_rows is None else int(n_rows),
+                                           None if advice_bytes is None else advice_bytes.data_ptr(), n_advice,
+                                           None if fixed_bytes is None else fixed_bytes.data_ptr(), n_fixed, source.data_ptr(), mapping.data_ptr(),
+                                           tables.data_ptr(), beta.data_ptr(), gamma.data_ptr(), _out[0].data_ptr(), _out[1].data_ptr(), _workspace.data_ptr(),
+                                           rep.data_ptr(), self._stream())
+        self._check(rc, "aesw_sigma_product_device")
+        return _out[0], _out[1], self._report(rep, sync, sigma_report_dict)
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1652,7 +1780,8 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "key_schedule_witness", "lookup_table", "expand_fr", "check_witness", "assemble_advice", "assemble_advice_stream",
               "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values",
               "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr",
-              "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product"):
+              "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
+              "permutation_tables", "permutation_product"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
