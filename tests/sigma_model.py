@@ -104,6 +104,64 @@ def product(k, columns, mapping, beta, gamma, chunk_len, n_rows):
                "noncanonical": False}
 
 
+def product_batched(k, columns, mapping, beta, gamma, chunk_len, n_rows):
+    """product() for the shapes it is too slow for (tests/test_sigma_model.py holds the two equal): the same arguments, the same
+    return value.  The powers of omega and of delta are running products, and a set's denominators are inverted together by
+    Montgomery's trick -- the prefix products of the non-zero ones, one pow, one walk back; a zero denominator is left out of
+    the prefixes and gets the inverse 0."""
+    n_cols, n = len(columns), 1 << k
+    sets = sets_of(n_cols, chunk_len)
+    here = np.arange(n_rows, dtype=np.int64)
+    images, out_of_range = [], 0
+    for c in range(n_cols):
+        m = np.asarray(mapping[c][:n_rows]).astype(np.int64) & 0xFFFFFFFF
+        outside = m >= n_cols * n
+        out_of_range += int(outside.sum())
+        images.append(np.where(outside, c * n + here, m))
+    if not (0 <= beta < R and 0 <= gamma < R):
+        return [[0] * (n_rows + 1) for _ in sets], {"sets": len(sets), "open": True, "zero_terms": 0, "first_zero": None, "out_of_range": out_of_range,
+                                                    "noncanonical": True}
+    w, w_pows, acc = omega(k), [], 1
+    for _ in range(n):
+        w_pows.append(acc)
+        acc = acc * w % R
+    bd, acc = [], beta
+    for _ in range(n_cols):
+        bd.append(acc)
+        acc = acc * DELTA % R
+    z, last, zeros = [], 1, []
+    for s, (first, end) in enumerate(sets):
+        nums, dens = [1] * n_rows, [1] * n_rows
+        for c in range(first, end):
+            v = np.asarray(columns[c][:n_rows]).astype(np.int64).tolist() if columns[c] is not None else [0] * n_rows
+            m_col, m_row = (images[c] >> k).tolist(), (images[c] & (n - 1)).tolist()
+            b = bd[c]
+            for i in range(n_rows):
+                vg = v[i] + gamma
+                nums[i] = nums[i] * (vg + b * w_pows[i]) % R
+                dens[i] = dens[i] * (vg + bd[m_col[i]] * w_pows[m_row[i]]) % R
+        prefix, acc = [], 1  # prefix[i]: the product of the non-zero denominators below row i
+        for d in dens:
+            prefix.append(acc)
+            if d:
+                acc = acc * d % R
+        back = pow(acc, R - 2, R)  # the inverse of the product of the non-zero denominators at and above the row the walk is at
+        inverses = [0] * n_rows
+        for i in range(n_rows - 1, -1, -1):
+            if dens[i]:
+                inverses[i] = back * prefix[i] % R
+                back = back * dens[i] % R
+            else:
+                zeros.append(s * n + i)
+        col = [last]
+        for num, inverse in zip(nums, inverses):
+            last = last * num % R * inverse % R
+            col.append(last)
+        z.append(col)
+    return z, {"sets": len(sets), "open": last != 1, "zero_terms": len(zeros), "first_zero": min(zeros) if zeros else None, "out_of_range": out_of_range,
+               "noncanonical": False}
+
+
 def z_cells(z, n_rows, k):
     """(uint8[S, last + 1, 32], uint8[S, 32]): the rows the device writes and the closing cells"""
     last = min(n_rows, (1 << k) - 1)

@@ -30,29 +30,35 @@ def cell(value):
     return torch.from_numpy(np.frombuffer(int(value * gm.M % gm.R).to_bytes(32, "little"), np.uint8).copy()).cuda()
 
 
-def columns(n_sets, seed):
-    """(inputs, a, s) int64 [n_sets, 5, 2^k]: inputs over the whole table, a and s from a pool of 3 000 rows per argument; planted in
+def columns(n_sets, seed, rows=ROWS):
+    """(inputs, a, s) int64 [n_sets, 5, rows]: inputs over the whole table, a and s from a pool of 3 000 rows per argument; planted in
     each: an index at the table's end, a large one and the miss marker (which read the all-zero row)."""
     rng = np.random.default_rng(seed)
-    inputs = rng.integers(0, gm.BINS, (n_sets, 5, ROWS))
+    inputs = rng.integers(0, gm.BINS, (n_sets, 5, rows))
     a, s = np.empty_like(inputs), np.empty_like(inputs)
     for st in range(n_sets):
         for t in range(5):
             pool = rng.choice(gm.BINS, 3000, replace=False)
-            a[st, t], s[st, t] = pool[rng.integers(0, 3000, ROWS)], pool[rng.integers(0, 3000, ROWS)]
+            a[st, t], s[st, t] = pool[rng.integers(0, 3000, rows)], pool[rng.integers(0, 3000, rows)]
             for col in (inputs, a, s):
                 at = rng.integers(0, gm.BINS, 6)  # below every n_rows
                 col[st, t, at[:2]], col[st, t, at[2:4]], col[st, t, at[4:]] = gm.BINS, 1 << 20, 0xFFFFFFFF
     return inputs, a, s
 
 
-def world(pkg, ctx, oracle, name):
-    """The columns of `name` on the device, the device's inverse table for their beta, and the model's Z per pad_row."""
+def compressed_table(oracle):
+    """(host, device): the oracle's lookup table compressed under THETA, made once"""
     import torch
     if "table" not in _worlds:
         table = tm.compressed_tables(oracle.lookup_table(), THETA)
         _worlds["table"] = (table, torch.from_numpy(table).cuda())
-    table, d_table = _worlds["table"]
+    return _worlds["table"]
+
+
+def world(pkg, ctx, oracle, name):
+    """The columns of `name` on the device, the device's inverse table for their beta, and the model's Z per pad_row."""
+    import torch
+    table, d_table = compressed_table(oracle)
     if name not in _worlds:
         n_sets = 2 if name == "two_sets" else 1
         inputs, a, s = columns(n_sets, {"one_set": 0x6731, "two_sets": 0x6732, "zero": 0x6731}[name])
@@ -79,15 +85,15 @@ def model(w, pad):
     return w["z"][pad]
 
 
-def product(pkg, ctx, arena, w, n_rows, pad, expect=OK, over=None):
+def product(pkg, ctx, arena, w, n_rows, pad, expect=OK, over=None, k=K):
     import torch
     n_sets = w["n_sets"]
     lib = pkg.api.load_grand_library()
-    z = arena.out("z", (n_sets * 5 * 32) << K, (n_sets, 5, ROWS, 32))
+    z = arena.out("z", (n_sets * 5 * 32) << k, (n_sets, 5, 1 << k, 32))
     closing = arena.out("closing", n_sets * 5 * 32, (n_sets, 5, 32))
     rep = arena.out("report", 24)
-    ws = arena.out("workspace", int(lib.aesw_grand_workspace_bytes(K, n_sets)))
-    args = dict(h=ctx._h, k=K, n_sets=n_sets, u=n_rows, pad=pad, inputs=w["dev"][0].data_ptr(), a=w["dev"][1].data_ptr(), s=w["dev"][2].data_ptr(),
+    ws = arena.out("workspace", int(lib.aesw_grand_workspace_bytes(k, n_sets)))
+    args = dict(h=ctx._h, k=k, n_sets=n_sets, u=n_rows, pad=pad, inputs=w["dev"][0].data_ptr(), a=w["dev"][1].data_ptr(), s=w["dev"][2].data_ptr(),
                 table=w["d_table"].data_ptr(), inv=w["inv"].data_ptr(), beta=w["d_beta"].data_ptr(), gamma=w["d_gamma"].data_ptr(), z=z.data_ptr(),
                 closing=closing.data_ptr(), ws=ws.data_ptr(), rep=rep.data_ptr())
     args.update(over or {})

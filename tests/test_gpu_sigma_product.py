@@ -19,29 +19,7 @@ BETA, GAMMA = (sc.seeded(s) for s in sc.CHALLENGE_SEEDS)
 _tables = {}
 
 
-def world(k, n_cols, n_rows, seed):
-    """(buffers uint8 [n_cols, 2^k] in buffer order, source, columns in permutation order, mapping uint32 [n_cols, 2^k])"""
-    rng = np.random.default_rng(seed)
-    n = 1 << k
-    cells = (np.arange(n_cols)[:, None] * n + np.arange(n_rows)[None, :]).reshape(-1)
-    perm = rng.permutation(cells)
-    starts = rng.random(len(perm)) < 0.4
-    starts[0] = True
-    at = np.arange(len(perm))
-    seg_start = np.maximum.accumulate(np.where(starts, at, 0))
-    nxt = at + 1
-    last = np.append(starts[1:], True)
-    nxt[last] = seg_start[last]
-    mapping = np.arange(n_cols * n, dtype=np.uint32)
-    mapping[perm] = perm[nxt]
-    seg_bytes = rng.integers(0, 256, len(perm), dtype=np.uint8)
-    columns = rng.integers(0, 256, n_cols * n, dtype=np.uint8)
-    columns[perm] = seg_bytes[seg_start]
-    columns, mapping = columns.reshape(n_cols, n), mapping.reshape(n_cols, n)
-    source = rng.permutation(n_cols).astype(np.uint32)
-    buffers = np.empty_like(columns)
-    buffers[source] = columns  # permutation column c lies in buffer source[c]
-    return buffers, source, columns, mapping
+world = sc.world  # the synthetic columns and mappings, shared with tests/test_gpu_sigma_reach.py and tests/test_sigma_model.py
 
 
 def tables(ctx, k, n_cols):

@@ -6,13 +6,15 @@ held against tests/sigma_model.py.  The host mapping code runs in a process of i
 plain and once under -fsanitize=address,undefined: its mapping equals the model's word for word, is a permutation whose cycles
 are exactly the connected components of the placed copy edges (a union-find of the test's own), and maps every other cell to
 itself.  The model itself is held against halo2's statement: over the oracle's circuit bytes the closing product is 1, and it
-is not after one planted change in a copied cell."""
+is not after one planted change in a copied cell.  The model's fast form, product_batched, is held equal to the literal product
+over every shape of sc.PRODUCTS, planted zero terms, entries out of range and challenges that are not canonical."""
 import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import sigma_cases as sc
 import sigma_model as sm
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -195,6 +197,55 @@ def test_assembly_copy_keeps_the_larger_cycle_left_and_the_calls_left_on_equal_s
         seen.add(at)
         at = a.mapping[at]
     assert seen == {0, 1, 2, 4, 5}
+
+
+# ---- the batched model ---------------------------------------------------------------------------------------------------------------
+# product_batched is the yardstick of tests/test_gpu_sigma_reach.py, whose shapes product() is too slow for: here the two are held
+# equal -- every Z of every set and the report -- which is what lets those tests use it.
+
+CHALLENGES = tuple(sc.seeded(s) for s in sc.CHALLENGE_SEEDS)
+
+
+@pytest.mark.parametrize("shape", sc.PRODUCTS, ids=lambda s: "k%d-c%d-l%d-u%d" % s)
+def test_the_batched_product_is_the_literal_one(shape):
+    k, n_cols, chunk_len, n_rows = shape
+    _buffers, _source, columns, mapping = sc.world(k, n_cols, n_rows, 0x7369 + sc.PRODUCTS.index(shape))
+    literal = sm.product(k, list(columns), mapping, *CHALLENGES, chunk_len, n_rows)
+    assert not literal[1]["open"] and literal[1]["zero_terms"] == 0
+    assert sm.product_batched(k, list(columns), mapping, *CHALLENGES, chunk_len, n_rows) == literal
+
+
+def test_the_batched_product_is_the_literal_one_over_planted_zero_terms():
+    k, n_cols, chunk_len, n_rows = 10, 7, 3, 1018
+    cells = ((4, 301), (5, 303), (3, 304), (1, 0), (6, 1017), (6, 500))  # in one lane's rows, at a lane's first row, the first and the last row
+    *_, columns, mapping, gamma = sc.planted_zeros(k, sc.world(k, n_cols, n_rows, 0x737a), cells, (0, 700), CHALLENGES[0])
+    literal = sm.product(k, list(columns), mapping, CHALLENGES[0], gamma, chunk_len, n_rows)
+    assert literal[1]["zero_terms"] == len(cells) and literal[1]["first_zero"] == 0 and literal[1]["open"]
+    assert literal[0][0][0] == 1 and not any(literal[0][0][1:]) and not any(literal[0][1]) and not any(literal[0][2])
+    assert sm.product_batched(k, list(columns), mapping, CHALLENGES[0], gamma, chunk_len, n_rows) == literal
+    # without the zero at row 0 the sets in front of the first zero keep their values
+    *_, columns, mapping, gamma = sc.planted_zeros(k, sc.world(k, n_cols, n_rows, 0x737a), cells[:3], (0, 700), CHALLENGES[0])
+    literal = sm.product(k, list(columns), mapping, CHALLENGES[0], gamma, chunk_len, n_rows)
+    assert literal[1]["zero_terms"] == 3 and literal[1]["first_zero"] == (1 << k) + 301 and all(literal[0][0]) and all(literal[0][1][:302]) and not any(literal[0][1][302:])
+    assert sm.product_batched(k, list(columns), mapping, CHALLENGES[0], gamma, chunk_len, n_rows) == literal
+
+
+def test_the_batched_product_is_the_literal_one_over_entries_out_of_range_and_challenges_that_are_not_canonical():
+    k, n_cols, chunk_len, n_rows = 10, 5, 2, 1018
+    _buffers, _source, columns, mapping = sc.world(k, n_cols, n_rows, 0x736f)
+    mapping = mapping.copy()
+    mapping[3, 500] = n_cols * (1 << k) + 5
+    mapping[0, 0] = 0xFFFFFFFF
+    mapping[4, 1020] = 0xFFFFFFFF  # at a row behind n_rows: neither read nor counted
+    cols = list(columns)
+    cols[2] = None  # a column that reads as zero bytes
+    literal = sm.product(k, cols, mapping, *CHALLENGES, chunk_len, n_rows)
+    assert literal[1]["out_of_range"] == 2 and not literal[1]["noncanonical"]
+    assert sm.product_batched(k, cols, mapping, *CHALLENGES, chunk_len, n_rows) == literal
+    for beta, gamma in ((sc.NONCANONICAL[0], CHALLENGES[1]), (CHALLENGES[0], sc.NONCANONICAL[1])):
+        literal = sm.product(k, cols, mapping, beta, gamma, chunk_len, n_rows)
+        assert literal[1]["noncanonical"] and literal[1]["out_of_range"] == 2
+        assert sm.product_batched(k, cols, mapping, beta, gamma, chunk_len, n_rows) == literal
 
 
 def test_the_models_closing_product_is_one_over_the_oracles_circuit_and_not_after_a_change(pkg, oracle):
