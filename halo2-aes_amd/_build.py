@@ -17,6 +17,8 @@
                                   beta and gamma (include/aesw_grand.h), built by build_satellite() as well
   halo2-aes_amd/libaesw_sigma.so  the second entry of ARGUMENT_LIBRARIES: the grand products of the permutation argument from
                                   beta and gamma, sigma as a column of cell indices (include/aesw_sigma.h), built alike
+  halo2-aes_amd/libaesw_ntt.so    the one entry of DOMAIN_LIBRARIES: columns of Fr cells between Lagrange, coefficient and
+                                  extended-coset form (include/aesw_ntt.h), built alike
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -154,21 +156,35 @@ GRAND_LIB = PKG / "libaesw_grand.so"
 SIGMA_LIB = PKG / "libaesw_sigma.so"
 
 
+# What changes the domain a column is given on: the number-theoretic transform.  It needs the field header, omega_k of the
+# permutation argument's rules and its own rules.  A fourth table: the tests of the three above hold library_names() at what it is,
+# so the entries of this one are named by domain_library_names() and __graft_entry__.build() walks them behind the others.
+DOMAIN_LIBRARIES = {
+    "ntt": ([CSRC / "ntt" / "aesw_ntt.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_sigma.h", CSRC / "aesw_ntt.h"], INCLUDE / "aesw_ntt.h"),
+}
+NTT_LIB = PKG / "libaesw_ntt.so"
+
+
 def library_names() -> list:
     """Every library build_satellite() builds, in the order of the three tables."""
     return list(SATELLITES) + list(FIELD_LIBRARIES) + list(ARGUMENT_LIBRARIES)
 
 
+def domain_library_names() -> list:
+    """The entries of DOMAIN_LIBRARIES: built by build_satellite() as well, behind library_names()."""
+    return list(DOMAIN_LIBRARIES)
+
+
 def library_entry(name: str):
-    """(sources, headers beyond SATELLITE_HEADERS, public header) of `name`, whichever of the three tables holds it."""
-    for table in (SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES):
+    """(sources, headers beyond SATELLITE_HEADERS, public header) of `name`, whichever of the four tables holds it."""
+    for table in (SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
 
 
 def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
-    """libaesw_<name>.so of an entry of SATELLITES, FIELD_LIBRARIES or ARGUMENT_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
+    """libaesw_<name>.so of an entry of SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES or DOMAIN_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
     A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are.  With `extra_flags` and
     another `out` (a file name next to libaesw.so) a measurement variant of it (tools/vacc_bench.py: -DAESW_VACC_WAVES=16)."""
     sources, headers, public = library_entry(name)

@@ -28,6 +28,7 @@ PERM_LIB_PATH = _PKG / "libaesw_perm.so"  # plookup's permuted columns arranged 
 THETA_LIB_PATH = _PKG / "libaesw_theta.so"  # the lookup arguments compressed under theta (include/aesw_theta.h)
 SIGMA_LIB_PATH = _PKG / "libaesw_sigma.so"  # the grand products of the permutation argument from beta and gamma (include/aesw_sigma.h)
 GRAND_LIB_PATH = _PKG / "libaesw_grand.so"  # the grand product Z of every lookup argument from beta and gamma (include/aesw_grand.h)
+NTT_LIB_PATH = _PKG / "libaesw_ntt.so"  # columns of Fr cells between Lagrange, coefficient and extended-coset form (include/aesw_ntt.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -263,6 +264,16 @@ SIGMA_SYMBOLS = {
     "aesw_sigma_tables_device": (_I, [_P, _U32, _U32, _P, _P]),
     "aesw_sigma_product_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
+# include/aesw_ntt.h
+NTT_SYMBOLS = {
+    "aesw_ntt_tables_bytes": (C.c_size_t, [_U32]),
+    "aesw_ntt_workspace_bytes": (C.c_size_t, [_U32, _U32]),
+    "aesw_ntt_tables_device": (_I, [_P, _U32, _P, _P]),
+    "aesw_ntt_lagrange_to_coeff_device": (_I, [_P, _U32, _U32, _P, _P, _P, _U32, _P, _P]),
+    "aesw_ntt_coeff_to_lagrange_device": (_I, [_P, _U32, _U32, _P, _P, _P, _U32, _P, _P]),
+    "aesw_ntt_coeff_to_extended_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _U32, _P, _P]),
+    "aesw_ntt_extended_to_coeff_device": (_I, [_P, _U32, _U32, _U32, _P, _P, _P, _U32, _P, _P]),
+}
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
 
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
@@ -281,6 +292,7 @@ _LIBRARIES = {
     "theta": (THETA_LIB_PATH, THETA_SYMBOLS, _NO_FALLBACK),
     "grand": (GRAND_LIB_PATH, GRAND_SYMBOLS, _NO_FALLBACK),
     "sigma": (SIGMA_LIB_PATH, SIGMA_SYMBOLS, _NO_FALLBACK),
+    "ntt": (NTT_LIB_PATH, NTT_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -376,6 +388,12 @@ def load_sigma_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_sigma.so (in-tree): the permutation argument's grand products behind Context.permutation_tables and
     Context.permutation_product, and the host functions behind permutation_columns, permutation_sources and permutation_mapping."""
     return _load("sigma", path)
+
+
+def load_ntt_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_ntt.so (in-tree): the transforms behind Context.ntt_tables, lagrange_to_coeff, coeff_to_lagrange,
+    coeff_to_extended and extended_to_coeff."""
+    return _load("ntt", path)
 
 
 def permutation_columns(n_sets: int) -> int:
@@ -1447,6 +1465,75 @@ class Context:
         self._check(rc, "aesw_sigma_product_device")
         return _out[0], _out[1], self._report(rep, sync, sigma_report_dict)
 
+    def ntt_tables(self, max_k: int, _out=None):
+        """The twiddle tables of the transforms below (aesw_ntt_tables_device, libaesw_ntt.so), once per max_k (10 ... 28): a uint8
+        [cells, 32] tensor that serves every transform of size up to 2^max_k."""
+        lib = load_ntt_library()
+        torch = self._torch()
+        max_k = int(max_k)
+        need = int(lib.aesw_ntt_tables_bytes(max_k)) if 0 <= max_k < 2 ** 32 else 0
+        if not need:
+            raise AeswError(ERR_INVALID_ARG, "aesw_ntt_tables_device: max_k must be 10 ... 28")
+        if _out is None:
+            _out = torch.empty((need // 32, 32), dtype=torch.uint8, device=self._dev())
+        elif self._u8(_out, "_out").numel() != need:
+            raise ValueError("_out must hold %d bytes" % need)
+        rc = lib.aesw_ntt_tables_device(self._h, max_k, _out.data_ptr(), self._stream())
+        self._check(rc, "aesw_ntt_tables_device")
+        return _out
+
+    def _ntt(self, call, leading, cells, k_in, k_out, tables, out, _workspace=None):
+        """One transform, `leading` the call's arguments in front of n_cols: `cells` a uint8 [n_cols, 2^k_in, 32] tensor (or [2^k_in, 32], one column), the result of the same rank with
+        2^k_out rows.  out: the tensor to write into -- `cells` itself for a call in place --, default a new one.  max_k is what
+        `tables` was built for (its size says which).  The workspace of a call in place is allocated here and handed back to the
+        caching allocator in stream order; _workspace is a uint8 tensor to use instead (a capture)."""
+        lib = load_ntt_library()
+        torch = self._torch()
+        k_in, k_out = int(k_in), int(k_out)
+        if not 10 <= k_in <= k_out <= 28:
+            raise AeswError(ERR_INVALID_ARG, call + ": k (and ext_k, no smaller) must be 10 ... 28")
+        if self._u8(cells, "cells").dim() not in (2, 3) or tuple(cells.shape[-2:]) != (1 << k_in, 32):
+            raise ValueError("cells must be a uint8 tensor of shape [n_cols, %d, 32] or [%d, 32]" % (1 << k_in, 1 << k_in))
+        n_cols = cells.shape[0] if cells.dim() == 3 else 1
+        shape = tuple(cells.shape[:-2]) + (1 << k_out, 32)
+        max_k = next((m for m in range(k_out, 29) if int(lib.aesw_ntt_tables_bytes(m)) == self._u8(tables, "tables").numel()), None)
+        if max_k is None:
+            raise ValueError("tables must be what ntt_tables(max_k) returns for a max_k of at least %d" % k_out)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(out, "out").shape) != shape:
+            raise ValueError("out must be a uint8 tensor of shape %r" % (shape,))
+        need = int(lib.aesw_ntt_workspace_bytes(k_out, n_cols)) if out.data_ptr() == cells.data_ptr() else 0
+        if need and _workspace is None:
+            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
+            _workspace = torch.empty(need, dtype=torch.uint8, device=self._dev())
+        elif need and self._u8(_workspace, "_workspace").numel() < need:
+            raise ValueError("_workspace must hold %d bytes" % need)
+        rc = getattr(lib, call)(self._h, *[int(v) for v in leading], n_cols, cells.data_ptr(), out.data_ptr(), tables.data_ptr(), max_k,
+                                None if _workspace is None else _workspace.data_ptr(), self._stream())
+        self._check(rc, call)
+        return out
+
+    def lagrange_to_coeff(self, cells, k: int, tables, out=None, _workspace=None):
+        """aesw_ntt_lagrange_to_coeff_device: the evaluations of a column on {omega_k^i} -> its 2^k coefficients (halo2's
+        lagrange_to_coeff, the 1/2^k included).  cells: uint8 [n_cols, 2^k, 32] or [2^k, 32] Montgomery cells, canonical; tables:
+        what ntt_tables returns; out=cells transforms in place."""
+        return self._ntt("aesw_ntt_lagrange_to_coeff_device", (k,), cells, k, k, tables, out, _workspace)
+
+    def coeff_to_lagrange(self, coeff, k: int, tables, out=None, _workspace=None):
+        """aesw_ntt_coeff_to_lagrange_device: the inverse of lagrange_to_coeff."""
+        return self._ntt("aesw_ntt_coeff_to_lagrange_device", (k,), coeff, k, k, tables, out, _workspace)
+
+    def coeff_to_extended(self, coeff, k: int, ext_k: int, tables, zeta_sel: int = 1, out=None):
+        """aesw_ntt_coeff_to_extended_device: 2^k coefficients -> the 2^ext_k evaluations on zeta * {omega_ext^i} (halo2's
+        coeff_to_extended).  zeta_sel 0: g^((r - 1) / 3), 1: its square -- which of them halo2 uses is not pinned (include/aesw_ntt.h)."""
+        return self._ntt("aesw_ntt_coeff_to_extended_device", (k, ext_k, zeta_sel), coeff, k, ext_k, tables, out)
+
+    def extended_to_coeff(self, ext, ext_k: int, tables, zeta_sel: int = 1, out=None, _workspace=None):
+        """aesw_ntt_extended_to_coeff_device: 2^ext_k evaluations on the coset -> 2^ext_k coefficients (halo2's extended_to_coeff
+        without the truncation); out=ext transforms in place."""
+        return self._ntt("aesw_ntt_extended_to_coeff_device", (ext_k, zeta_sel), ext, ext_k, ext_k, tables, out, _workspace)
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1781,7 +1868,8 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "assemble_advice_host", "assemble_advice_circuits", "circuits", "check_circuits", "check_columns", "check_values",
               "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr",
               "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
-              "permutation_tables", "permutation_product"):
+              "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
+              "extended_to_coeff"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 

@@ -75,6 +75,28 @@ AESW_FR_HD constexpr Fr fr_add(const Fr &a, const Fr &b) {
     return fr_reduce_once(t, (uint32_t)carry);
 }
 
+// a - b mod r, both canonical: the difference, and r added back where it borrowed (the transforms of aesw_ntt.h)
+AESW_FR_HD constexpr Fr fr_sub(const Fr &a, const Fr &b) {
+    Fr d = FR_ZERO;
+    uint64_t borrow = 0;
+    AESW_FR_UNROLL
+    for (int i = 0; i < FR_LIMBS; ++i) {
+        const uint64_t v = (uint64_t)a.l[i] - b.l[i] - borrow;
+        d.l[i] = (uint32_t)v;
+        borrow = (v >> 32) & 1u;
+    }
+    const uint32_t mask = 0u - (uint32_t)borrow;  // all ones where a < b
+    Fr out = FR_ZERO;
+    uint64_t carry = 0;
+    AESW_FR_UNROLL
+    for (int i = 0; i < FR_LIMBS; ++i) {
+        const uint64_t v = (uint64_t)d.l[i] + (FR_MODULUS.l[i] & mask) + carry;
+        out.l[i] = (uint32_t)v;
+        carry = v >> 32;
+    }
+    return out;
+}
+
 // a * b / 2^256 mod r, both canonical: the product of two Montgomery forms is the Montgomery form of the product
 AESW_FR_HD constexpr Fr fr_mul(const Fr &a, const Fr &b) {
     uint32_t t[FR_LIMBS + 2] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
