@@ -19,6 +19,8 @@
                                   beta and gamma, sigma as a column of cell indices (include/aesw_sigma.h), built alike
   halo2-aes_amd/libaesw_ntt.so    the one entry of DOMAIN_LIBRARIES: columns of Fr cells between Lagrange, coefficient and
                                   extended-coset form (include/aesw_ntt.h), built alike
+  halo2-aes_amd/libaesw_quot.so   the one entry of QUOTIENT_LIBRARIES: sigma as Fr columns, for the quotient h(X)
+                                  (include/aesw_quot.h), built alike
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -165,6 +167,17 @@ DOMAIN_LIBRARIES = {
 NTT_LIB = PKG / "libaesw_ntt.so"
 
 
+# What the quotient of the circuit's constraints needs: today sigma as Fr columns, with the rules of the fold.  It needs the field header and the rules of the
+# permutation argument (the column order, delta), of the transforms (zeta, the table split) and of theta (the arity of a tag) next
+# to its own.  A fifth table, named by quotient_library_names(): library_names() and domain_library_names() are held at what they
+# are by the tests of the tables above, and __graft_entry__.build() walks this one last.
+QUOTIENT_LIBRARIES = {
+    "quot": ([CSRC / "quot" / "aesw_quot.hip"],
+             [CSRC / "aesw_fr.h", CSRC / "aesw_sigma.h", CSRC / "aesw_ntt.h", CSRC / "aesw_theta.h", CSRC / "aesw_placement.h", CSRC / "aesw_quot.h"], INCLUDE / "aesw_quot.h"),
+}
+QUOT_LIB = PKG / "libaesw_quot.so"
+
+
 def library_names() -> list:
     """Every library build_satellite() builds, in the order of the three tables."""
     return list(SATELLITES) + list(FIELD_LIBRARIES) + list(ARGUMENT_LIBRARIES)
@@ -175,16 +188,21 @@ def domain_library_names() -> list:
     return list(DOMAIN_LIBRARIES)
 
 
+def quotient_library_names() -> list:
+    """The entries of QUOTIENT_LIBRARIES: built by build_satellite() as well, behind domain_library_names()."""
+    return list(QUOTIENT_LIBRARIES)
+
+
 def library_entry(name: str):
-    """(sources, headers beyond SATELLITE_HEADERS, public header) of `name`, whichever of the four tables holds it."""
-    for table in (SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES):
+    """(sources, headers beyond SATELLITE_HEADERS, public header) of `name`, whichever of the five tables holds it."""
+    for table in (SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES, QUOTIENT_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
 
 
 def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
-    """libaesw_<name>.so of an entry of SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES or DOMAIN_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
+    """libaesw_<name>.so of an entry of SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES or QUOTIENT_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
     A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are.  With `extra_flags` and
     another `out` (a file name next to libaesw.so) a measurement variant of it (tools/vacc_bench.py: -DAESW_VACC_WAVES=16)."""
     sources, headers, public = library_entry(name)

@@ -29,6 +29,7 @@ THETA_LIB_PATH = _PKG / "libaesw_theta.so"  # the lookup arguments compressed un
 SIGMA_LIB_PATH = _PKG / "libaesw_sigma.so"  # the grand products of the permutation argument from beta and gamma (include/aesw_sigma.h)
 GRAND_LIB_PATH = _PKG / "libaesw_grand.so"  # the grand product Z of every lookup argument from beta and gamma (include/aesw_grand.h)
 NTT_LIB_PATH = _PKG / "libaesw_ntt.so"  # columns of Fr cells between Lagrange, coefficient and extended-coset form (include/aesw_ntt.h)
+QUOT_LIB_PATH = _PKG / "libaesw_quot.so"  # sigma of the permutation argument as Fr columns, for the quotient h(X) (include/aesw_quot.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -274,6 +275,10 @@ NTT_SYMBOLS = {
     "aesw_ntt_coeff_to_extended_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _U32, _P, _P]),
     "aesw_ntt_extended_to_coeff_device": (_I, [_P, _U32, _U32, _U32, _P, _P, _P, _U32, _P, _P]),
 }
+# include/aesw_quot.h
+QUOT_SYMBOLS = {
+    "aesw_quot_sigma_fr_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P]),
+}
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
 
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
@@ -293,6 +298,7 @@ _LIBRARIES = {
     "grand": (GRAND_LIB_PATH, GRAND_SYMBOLS, _NO_FALLBACK),
     "sigma": (SIGMA_LIB_PATH, SIGMA_SYMBOLS, _NO_FALLBACK),
     "ntt": (NTT_LIB_PATH, NTT_SYMBOLS, _NO_FALLBACK),
+    "quot": (QUOT_LIB_PATH, QUOT_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -394,6 +400,11 @@ def load_ntt_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_ntt.so (in-tree): the transforms behind Context.ntt_tables, lagrange_to_coeff, coeff_to_lagrange,
     coeff_to_extended and extended_to_coeff."""
     return _load("ntt", path)
+
+
+def load_quot_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_quot.so (in-tree): sigma as Fr columns behind Context.permutation_columns_fr."""
+    return _load("quot", path)
 
 
 def permutation_columns(n_sets: int) -> int:
@@ -1534,6 +1545,34 @@ class Context:
         without the truncation); out=ext transforms in place."""
         return self._ntt("aesw_ntt_extended_to_coeff_device", (ext_k, zeta_sel), ext, ext_k, ext_k, tables, out, _workspace)
 
+    def permutation_columns_fr(self, k: int, n_cols: int, mapping, sigma_tables, _out=None):
+        """Sigma as Fr cells (aesw_quot_sigma_fr_device): a uint8 [n_cols, 2^k, 32] tensor, cell [c][i] the label delta^c' * omega^i'
+        of mapping[c][i] = c' * 2^k + i' -- the Lagrange form of halo2's permutation polynomials; an entry out of range reads as the
+        cell itself.  mapping: the [n_cols, 2^k] cell indices (permutation_mapping; a numpy array is uploaded, an int32 device
+        tensor stays); sigma_tables: what permutation_tables returns for the same (k, n_cols)."""
+        lib = load_quot_library()
+        torch = self._torch()
+        k, n_cols = int(k), int(n_cols)
+        need = int(load_sigma_library().aesw_sigma_tables_bytes(k, n_cols)) if 0 <= k < 2 ** 32 and 0 <= n_cols < 2 ** 32 else 0
+        if not need:
+            raise AeswError(ERR_INVALID_ARG, "aesw_quot_sigma_fr_device: k must be 10 ... 28, n_cols 1 ... 3074 and n_cols * 2^k at most 2^32")
+        if isinstance(mapping, np.ndarray):
+            mapping = torch.from_numpy(np.ascontiguousarray(mapping, np.uint32).view(np.int32)).to(self._dev())
+        if not isinstance(mapping, torch.Tensor) or mapping.dtype != torch.int32 or not mapping.is_cuda or mapping.device.index != self.device:
+            raise TypeError("mapping must be a numpy array or an int32 tensor on cuda:%d" % self.device)
+        if tuple(mapping.shape) != (n_cols, 1 << k) or not mapping.is_contiguous():
+            raise ValueError("mapping must be contiguous and of shape %r" % ((n_cols, 1 << k),))
+        if self._u8(sigma_tables, "sigma_tables").numel() < need:
+            raise ValueError("sigma_tables must hold %d bytes" % need)
+        shape = (n_cols, 1 << k, 32)
+        if _out is None:
+            _out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(_out, "_out").shape) != shape:
+            raise ValueError("_out must be a uint8 tensor of shape %r" % (shape,))
+        rc = lib.aesw_quot_sigma_fr_device(self._h, k, n_cols, mapping.data_ptr(), sigma_tables.data_ptr(), _out.data_ptr(), self._stream())
+        self._check(rc, "aesw_quot_sigma_fr_device")
+        return _out
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1869,7 +1908,7 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr",
               "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
               "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
-              "extended_to_coeff"):
+              "extended_to_coeff", "permutation_columns_fr"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
