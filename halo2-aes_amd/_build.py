@@ -117,11 +117,12 @@ def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_so
 # satellite's live one level down, in csrc/<name>/.  Each entry: its sources, the headers it depends on beyond
 # SATELLITE_HEADERS, its public header.  SATELLITE_HEADERS is what every one of them may include: the context, the checker
 # core, what an entry point says before it launches (aesw_entry.h; aesw_entry_rules.h, whose bounds are aesw_mult.h's), the
-# store flavour (aesw_store.h), the report's reset and fold (aesw_report_dev.h).  (The order is no build order -- each depends on libaesw.so alone -- but "mult" stays
+# store flavour (aesw_store.h), the report's reset and fold (aesw_report_dev.h), what a kernel of the libraries that compute
+# in Fr does to a cell (aesw_fr_dev.h, over the aesw_fr.h each of them lists).  (The order is no build order -- each depends on libaesw.so alone -- but "mult" stays
 # the last entry: tests/test_mult_library.py holds it there.)
 SATELLITE_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_check.h", "aesw_layout.h", "aesw_slabmap.h", "aesw_internal.h", "aesw_ctx.h",
                                         "aesw_keyring.h", "aesw_options.h", "aesw_placement.h", "aesw_align.h", "aesw_entry.h", "aesw_entry_rules.h", "aesw_mult.h",
-                                        "aesw_store.h", "aesw_report_dev.h")] + [INCLUDE / "aesw.h", INCLUDE / "aesw_mult.h"]
+                                        "aesw_store.h", "aesw_report_dev.h", "aesw_fr_dev.h")] + [INCLUDE / "aesw.h", INCLUDE / "aesw_mult.h"]
 SATELLITES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h", CSRC / "aesw_fr.h"], INCLUDE / "aesw_cols.h"),

@@ -22,6 +22,16 @@ inline const char *bad_slabs(const void *d_x, const void *d_y, const void *d_z) 
     return !d_x || !d_y || !d_z || !aligned_to(d_x, 16) || !aligned_to(d_y, 16) || !aligned_to(d_z, 16) ? "d_x, d_y and d_z must be there and 16-byte aligned"
                                                                                                        : nullptr;
 }
+// what the grand-product calls (grand, sigma) take alike: the challenges, Z with its closing cells, the workspace -- Fr cells all
+inline const char *bad_challenges(const void *d_beta, const void *d_gamma) {
+    return !d_beta || !d_gamma || !aligned_to(d_beta, 16) || !aligned_to(d_gamma, 16) ? "d_beta and d_gamma must be there and 16-byte aligned" : nullptr;
+}
+inline const char *bad_product_outputs(const void *d_z_fr, const void *d_closing_fr) {
+    return !d_z_fr || !d_closing_fr || !aligned_to(d_z_fr, 16) || !aligned_to(d_closing_fr, 16) ? "d_z_fr and d_closing_fr must be there and 16-byte aligned" : nullptr;
+}
+inline const char *bad_workspace(const void *d_workspace) {
+    return !d_workspace || !aligned_to(d_workspace, 16) ? "d_workspace must be there and 16-byte aligned" : nullptr;
+}
 
 // The key columns of a call that may go without them: they count where all three are there and the circuit has room for the
 // key schedule; only columns that count are held to their alignment.

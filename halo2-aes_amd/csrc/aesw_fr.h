@@ -4,10 +4,13 @@
 // (d_fr_lut of aesw_ctx.h holds the 256 byte values in this form), so a cell is loaded and stored as it lies.
 // fr_mul is the Montgomery product a * b / 2^256 mod r, CIOS over 32-bit limbs: every step is a uint64_t accumulation of
 // uint32_t products, which hipcc turns into 64-bit multiply-adds (v_mad_u64_u32) without a line of assembly.
+// fr_unrolled<N>(f) is the unroll of every loop over an array of cells, for host and device as well.
 // constexpr, no HIP call, no ROCm include and no other header of the project: tests/test_fr_header.py compiles this header
 // alone with g++ and holds it against Python integers.
 #pragma once
 #include <stdint.h>
+
+#include <utility>
 
 #if defined(__HIPCC__)
 #define AESW_FR_HD __host__ __device__ __forceinline__
@@ -170,6 +173,18 @@ AESW_FR_HD constexpr Fr fr_inv(const Fr &a) {
 }
 // one evaluation at compile time (380 products); fr_inv(0) == 0 and the rest are tests/test_fr_inverse.py's
 static_assert(FR_MODULUS.l[0] >= 2u && fr_eq(fr_mul(fr_inv(fr_add(FR_ONE, FR_ONE)), fr_add(FR_ONE, FR_ONE)), FR_ONE), "fr_inv(2) * 2 is 1");
+
+// f(i) for i = 0 ... N - 1 with i a constant of the type system (decltype(i)::value): a pack expansion, not a loop.  A loop whose
+// body holds field products is too large for the compiler to unroll on request, and a cell array indexed by a loop that
+// stays a loop leaves the registers for scratch memory.
+template <class F, int... I>
+AESW_FR_HD void fr_each(F &&f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+AESW_FR_HD void fr_unrolled(F &&f) {
+    fr_each(f, std::make_integer_sequence<int, N>{});
+}
 
 // The 256 byte values as cells, cell v = v * 2^256 mod r: what d_fr_lut (aesw_ctx.h) holds on the device and what the columns
 // checker inverts (aesw_cols_fr_table).  Little-endian limbs: on the hosts the project builds for, the table's bytes as they lie.

@@ -5,8 +5,6 @@
 // index aesw_theta.h's, the bounds aesw_mult.h's.
 // No HIP call and no ROCm include: tests/test_grand_model.py compiles this header alone with g++.
 #pragma once
-#include <utility>
-
 #include "aesw_theta.h"
 
 namespace aesw {
@@ -29,18 +27,6 @@ AESW_HD constexpr bool grand_k_ok(uint32_t k) { return k >= 17 && k <= MULT_MAX_
 // among them) -- row 66 560 compresses to the zero cell in all three tables, which is the cell the columns call writes there.
 AESW_HD constexpr uint32_t grand_row_of_index(uint32_t x) { return x < MULT_BINS ? x : MULT_ZERO_ROW; }
 
-// f(i) for i = 0 ... N - 1 with i a constant of the type system (decltype(i)::value): a pack expansion, not a loop.  A loop whose
-// body holds field products is too large for the compiler to unroll on request, and a cell array indexed by a loop that
-// stays a loop leaves the registers for scratch memory.
-template <class F, int... I>
-AESW_FR_HD void grand_each(F &&f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-AESW_FR_HD void grand_unrolled(F &&f) {
-    grand_each(f, std::make_integer_sequence<int, N>{});
-}
-
 // Montgomery's trick over B sums sum(0) ... sum(B - 1) (a callable: the sums are made twice, never kept): one fr_inv of the
 // product of the sums that are not zero, out(i, inverse) for every i -- the zero cell for a zero sum, which the running product
 // skips.  Returns how many sums were zero.  B products forwards, 2 B backwards, one inversion.
@@ -48,7 +34,7 @@ template <int B, class Sum, class Out>
 AESW_FR_HD uint32_t grand_batch_invert(Sum &&sum, Out &&out) {
     Fr before[B];  // before[i]: the product of the non-zero sums below i
     Fr acc = FR_ONE;
-    grand_unrolled<B>([&](auto at) {
+    fr_unrolled<B>([&](auto at) {
         constexpr int i = decltype(at)::value;
         before[i] = acc;
         const Fr s = sum(i);
@@ -56,7 +42,7 @@ AESW_FR_HD uint32_t grand_batch_invert(Sum &&sum, Out &&out) {
     });
     Fr inv = fr_inv(acc);  // acc is a product of non-zero values: never 0
     uint32_t zeros = 0;
-    grand_unrolled<B>([&](auto at) {
+    fr_unrolled<B>([&](auto at) {
         constexpr int i = B - 1 - decltype(at)::value;
         const Fr s = sum(i);
         if (fr_is_zero(s)) {

@@ -7,18 +7,18 @@
 //   * grand_carry_kernel: one workgroup per argument turns the argument's chunk products into exclusive prefixes in place,
 //     writes the closing cell and the argument's 16-byte part of the report;
 //   * grand_scan_kernel<NT>: a workgroup makes the factors of its chunk again and scans them from its carry-in: in-lane over the
-//     lane's consecutive rows, lanes joined by __shfl_up, waves through LDS; Z leaves through aesw_store.h's flavour;
+//     lane's consecutive rows, lanes joined by the wave's scan, waves through LDS; Z leaves through aesw_store.h's flavour;
 //   * grand_report_kernel: one workgroup folds the parts into the report (aesw_report_dev.h's workgroup_fold);
 //   * the entry points and the checks that are theirs alone (the preamble and the shared rules are aesw_entry.h's).
+// How a cell lies in memory, moves between lanes and is scanned over a wave is aesw_fr_dev.h's.
 // No atomic, no look-back flag, nothing to reset: every word of every output is stored once per call.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../../include/aesw_grand.h"
 #include "../aesw_entry.h"
+#include "../aesw_fr_dev.h"
 #include "../aesw_grand.h"
-#include "../aesw_report_dev.h"
-#include "../aesw_store.h"
 
 namespace aesw_grand {
 using namespace aesw;
@@ -35,28 +35,6 @@ static_assert(AESW_GRAND_PLANES == GRAND_PLANES, "the header's constant is the r
 #define AESW_GRAND_PASSES 0x3f
 #endif
 constexpr unsigned PASSES = AESW_GRAND_PASSES, PASS_INVERT = 1, PASS_INVERT_REPORT = 2, PASS_CHUNK = 4, PASS_CARRY = 8, PASS_SCAN = 16, PASS_REPORT = 32;
-
-__device__ __forceinline__ Fr load_cell(const u32x4 *p) {
-    const u32x4 lo = p[0], hi = p[1];
-    return Fr{{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}};
-}
-template <int NT>
-__device__ __forceinline__ void store_cell(u32x4 *p, const Fr &v) {
-    gstore<NT>(p, u32x4{v.l[0], v.l[1], v.l[2], v.l[3]});
-    gstore<NT>(p + 1, u32x4{v.l[4], v.l[5], v.l[6], v.l[7]});
-}
-__device__ __forceinline__ Fr shfl_up_cell(const Fr &v, int o) {
-    Fr r = FR_ZERO;
-#pragma unroll
-    for (int i = 0; i < FR_LIMBS; ++i) r.l[i] = __shfl_up(v.l[i], o, LANES);
-    return r;
-}
-__device__ __forceinline__ Fr shfl_xor_cell(const Fr &v, int o) {
-    Fr r = FR_ZERO;
-#pragma unroll
-    for (int i = 0; i < FR_LIMBS; ++i) r.l[i] = __shfl_xor(v.l[i], o, LANES);
-    return r;
-}
 
 // ---- the inverse table ------------------------------------------------------------------------------------------------------
 
@@ -129,7 +107,7 @@ __device__ __forceinline__ void lane_factors(const ProductParams &p, uint32_t ar
     const uint64_t at = ((uint64_t)arg << p.k) + i0;
     const index_vec vin = *reinterpret_cast<const index_vec *>(p.in + at), va = *reinterpret_cast<const index_vec *>(p.a + at),
                     vs = *reinterpret_cast<const index_vec *>(p.s + at);
-    grand_unrolled<ROWS>([&](auto at) {
+    fr_unrolled<ROWS>([&](auto at) {
         constexpr int q = decltype(at)::value;
         if (i0 + q < p.n_rows)
             f[q] = grand_row(load_cell(T + grand_row_of_index(vin[q]) * 2), load_cell(T + theta_table_index(i0 + q, p.pad_row) * 2),
@@ -144,7 +122,7 @@ __global__ void __launch_bounds__(THREADS) grand_chunk_kernel(const ProductParam
     Fr f[ROWS];
     lane_factors(p, arg, blockIdx.x * GRAND_CHUNK + threadIdx.x * ROWS, f);
     Fr t = f[0];
-    grand_unrolled<ROWS - 1>([&](auto at) { t = fr_mul(t, f[decltype(at)::value + 1]); });
+    fr_unrolled<ROWS - 1>([&](auto at) { t = fr_mul(t, f[decltype(at)::value + 1]); });
 #pragma unroll 1
     for (int o = LANES / 2; o; o >>= 1) t = fr_mul(t, shfl_xor_cell(t, o));  // the field is commutative: a butterfly will do
     if (lane == 0) s_wave[wave] = t;
@@ -152,18 +130,8 @@ __global__ void __launch_bounds__(THREADS) grand_chunk_kernel(const ProductParam
     if (threadIdx.x == 0) {
 #pragma unroll 1
         for (int w = 1; w < WAVES; ++w) t = fr_mul(t, s_wave[w]);
-        store_cell<0>(p.carries + ((uint64_t)arg * p.stride + blockIdx.x) * 2, t);
+        store_cell<0>(cell_at(p.carries, (uint64_t)arg * p.stride + blockIdx.x), t);
     }
-}
-
-// The inclusive scan of one cell per lane over a wave: lane l ends with the product of lanes 0 ... l.
-__device__ __forceinline__ Fr wave_scan(Fr v, uint32_t lane) {
-#pragma unroll 1
-    for (int o = 1; o < LANES; o <<= 1) {
-        const Fr up = shfl_up_cell(v, o);  // every lane shuffles; the lanes that have a partner multiply
-        if (lane >= (uint32_t)o) v = fr_mul(up, v);
-    }
-    return v;
 }
 
 // grid: x = the argument.  Its chunk products -> exclusive prefixes, in place, 256 chunks a turn.
@@ -171,11 +139,11 @@ __global__ void __launch_bounds__(THREADS) grand_carry_kernel(u32x4 *__restrict_
                                                               u32x4 *__restrict__ parts) {
     __shared__ Fr s_wave[WAVES];
     const uint32_t arg = blockIdx.x, lane = threadIdx.x % LANES, wave = threadIdx.x / LANES;
-    u32x4 *cells = carries + (uint64_t)arg * stride * 2;
+    u32x4 *cells = cell_at(carries, (uint64_t)arg * stride);
     Fr running = FR_ONE;  // the product of every chunk below this turn's, in every thread
     for (uint32_t first = 0; first < chunks; first += THREADS) {
         const uint32_t i = first + threadIdx.x;
-        const Fr incl = wave_scan(i < chunks ? load_cell(cells + (uint64_t)i * 2) : FR_ONE, lane);
+        const Fr incl = wave_scan_up(i < chunks ? load_cell(cell_at(cells, i)) : FR_ONE, lane);
         Fr excl = shfl_up_cell(incl, 1);
         if (lane == 0) excl = FR_ONE;
         if (lane == LANES - 1) s_wave[wave] = incl;
@@ -186,11 +154,11 @@ __global__ void __launch_bounds__(THREADS) grand_carry_kernel(u32x4 *__restrict_
             if (w == wave) base = running;  // what lies below this wave
             running = fr_mul(running, s_wave[w]);
         }
-        if (i < chunks) store_cell<0>(cells + (uint64_t)i * 2, fr_mul(base, excl));
+        if (i < chunks) store_cell<0>(cell_at(cells, i), fr_mul(base, excl));
         __syncthreads();  // s_wave is written again next turn
     }
     if (threadIdx.x == 0) {
-        store_cell<0>(closing + (uint64_t)arg * 2, running);
+        store_cell<0>(cell_at(closing, arg), running);
         const bool open = !fr_eq(running, FR_ONE);
         const uint64_t key = open ? grand_argument_key(arg) : ~0ull;
         parts[arg] = u32x4{open ? 1u : 0u, 0u, (uint32_t)key, (uint32_t)(key >> 32)};
@@ -205,21 +173,21 @@ __global__ void __launch_bounds__(THREADS) grand_scan_kernel(const ProductParams
     const uint32_t i0 = blockIdx.x * GRAND_CHUNK + threadIdx.x * ROWS;
     Fr f[ROWS];
     lane_factors(p, arg, i0, f);
-    grand_unrolled<ROWS - 1>([&](auto at) { f[decltype(at)::value + 1] = fr_mul(f[decltype(at)::value], f[decltype(at)::value + 1]); });  // inclusive, in the lane
-    const Fr incl = wave_scan(f[ROWS - 1], lane);
+    fr_unrolled<ROWS - 1>([&](auto at) { f[decltype(at)::value + 1] = fr_mul(f[decltype(at)::value], f[decltype(at)::value + 1]); });  // inclusive, in the lane
+    const Fr incl = wave_scan_up(f[ROWS - 1], lane);
     Fr excl = shfl_up_cell(incl, 1);
     if (lane == 0) excl = FR_ONE;
     if (lane == LANES - 1) s_wave[wave] = incl;
     __syncthreads();
-    Fr base = load_cell(p.carries + ((uint64_t)arg * p.stride + blockIdx.x) * 2);  // the carry-in: Z at the chunk's first row
+    Fr base = load_cell(cell_at(p.carries, (uint64_t)arg * p.stride + blockIdx.x));  // the carry-in: Z at the chunk's first row
 #pragma unroll 1
     for (uint32_t w = 0; w < wave; ++w) base = fr_mul(base, s_wave[w]);
     base = fr_mul(base, excl);  // Z[i0]
-    u32x4 *z = p.z + (((uint64_t)arg << p.k) + i0) * 2;
+    u32x4 *z = cell_at(p.z, ((uint64_t)arg << p.k) + i0);
     if (i0 <= p.last_row) store_cell<NT>(z, base);
-    grand_unrolled<ROWS - 1>([&](auto at) {
+    fr_unrolled<ROWS - 1>([&](auto at) {
         constexpr int q = decltype(at)::value + 1;
-        if (i0 + q <= p.last_row) store_cell<NT>(z + q * 2, fr_mul(base, f[q - 1]));
+        if (i0 + q <= p.last_row) store_cell<NT>(cell_at(z, q), fr_mul(base, f[q - 1]));
     });
 }
 
@@ -247,7 +215,7 @@ int aesw_grand_invert_table_device(aesw_ctx *ctx, const uint8_t *d_table_fr, con
     const char *const call = "aesw_grand_invert_table_device";
     if (int rc = entry_refused(ctx, call)) return rc;
     if (!d_table_fr || !aligned_to(d_table_fr, 16)) return refuse(ctx, call, "d_table_fr must be there and 16-byte aligned");
-    if (!d_beta || !d_gamma || !aligned_to(d_beta, 16) || !aligned_to(d_gamma, 16)) return refuse(ctx, call, "d_beta and d_gamma must be there and 16-byte aligned");
+    if (const char *why = bad_challenges(d_beta, d_gamma)) return refuse(ctx, call, why);
     if (!d_inv_fr || !aligned_to(d_inv_fr, 16)) return refuse(ctx, call, "d_inv_fr must be there and 16-byte aligned");
     if (const char *why = bad_report(d_report)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
@@ -281,10 +249,9 @@ int aesw_grand_product_device(aesw_ctx *ctx, uint32_t k, uint32_t n_sets, uint32
         return refuse(ctx, call, "d_in, d_a and d_s must be there and 16-byte aligned");
     if (!d_table_fr || !d_inv_fr || !aligned_to(d_table_fr, 16) || !aligned_to(d_inv_fr, 16))
         return refuse(ctx, call, "d_table_fr and d_inv_fr must be there and 16-byte aligned");
-    if (!d_beta || !d_gamma || !aligned_to(d_beta, 16) || !aligned_to(d_gamma, 16)) return refuse(ctx, call, "d_beta and d_gamma must be there and 16-byte aligned");
-    if (!d_z_fr || !d_closing_fr || !aligned_to(d_z_fr, 16) || !aligned_to(d_closing_fr, 16))
-        return refuse(ctx, call, "d_z_fr and d_closing_fr must be there and 16-byte aligned");
-    if (!d_workspace || !aligned_to(d_workspace, 16)) return refuse(ctx, call, "d_workspace must be there and 16-byte aligned");
+    if (const char *why = bad_challenges(d_beta, d_gamma)) return refuse(ctx, call, why);
+    if (const char *why = bad_product_outputs(d_z_fr, d_closing_fr)) return refuse(ctx, call, why);
+    if (const char *why = bad_workspace(d_workspace)) return refuse(ctx, call, why);
     if (const char *why = bad_report(d_report)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;

@@ -14,8 +14,8 @@
 
 #include "../../../include/aesw_ntt.h"
 #include "../aesw_entry.h"
+#include "../aesw_fr_dev.h"
 #include "../aesw_ntt.h"
-#include "../aesw_store.h"
 
 namespace aesw_ntt {
 using namespace aesw;
@@ -29,18 +29,6 @@ static_assert(sizeof(Fr) == 32, "a cell is two 16-byte pieces");
 #define AESW_NTT_PASSES 0xffffffffu
 #endif
 constexpr uint32_t PASSES = AESW_NTT_PASSES;
-
-__device__ __forceinline__ Fr load_cell(const u32x4 *p) {
-    const u32x4 lo = p[0], hi = p[1];
-    return Fr{{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}};
-}
-template <int NT>
-__device__ __forceinline__ void store_cell(u32x4 *p, const Fr &v) {
-    gstore<NT>(p, u32x4{v.l[0], v.l[1], v.l[2], v.l[3]});
-    gstore<NT>(p + 1, u32x4{v.l[4], v.l[5], v.l[6], v.l[7]});
-}
-__device__ __forceinline__ const u32x4 *cell_at(const u32x4 *base, uint64_t i) { return base + i * 2; }
-__device__ __forceinline__ u32x4 *cell_at(u32x4 *base, uint64_t i) { return base + i * 2; }
 
 typedef uint32_t Tile[FR_LIMBS][NTT_SLOTS];  // limb-planar (aesw_ntt.h, ntt_lds_index)
 __device__ __forceinline__ Fr tile_read(const Tile &tile, uint32_t slot) {

@@ -10,33 +10,22 @@
 
 #include "../../../include/aesw_quot.h"
 #include "../aesw_entry.h"
+#include "../aesw_fr_dev.h"
 #include "../aesw_quot.h"
 
 namespace aesw_quot {
 using namespace aesw;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t THREADS = QUOT_THREADS;
 static_assert(sizeof(Fr) == 32, "a cell is two 16-byte pieces");
 static_assert((1u << SIGMA_MIN_K) % THREADS == 0, "the smallest column is whole workgroups");
-
-__device__ __forceinline__ Fr load_cell(const u32x4 *p) {
-    const u32x4 lo = p[0], hi = p[1];
-    return Fr{{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}};
-}
-__device__ __forceinline__ void store_cell(u32x4 *p, const Fr &v) {
-    p[0] = u32x4{v.l[0], v.l[1], v.l[2], v.l[3]};
-    p[1] = u32x4{v.l[4], v.l[5], v.l[6], v.l[7]};
-}
-__device__ __forceinline__ const u32x4 *cell_at(const u32x4 *base, uint64_t i) { return base + i * 2; }
-__device__ __forceinline__ u32x4 *cell_at(u32x4 *base, uint64_t i) { return base + i * 2; }
 
 // grid: x = 2^k / THREADS, y = the column
 __global__ void __launch_bounds__(THREADS) quot_sigma_kernel(const uint32_t *map, const u32x4 *tables, u32x4 *out, uint32_t k, uint32_t n_cols) {
     const uint32_t i = blockIdx.x * THREADS + threadIdx.x, c = blockIdx.y;
     const uint64_t at = ((uint64_t)c << k) + i;
     const uint32_t image = quot_sigma_image(k, n_cols, c, i, map[at]);
-    store_cell(cell_at(out, at), quot_sigma_label(k, image, [&](uint32_t cell) { return load_cell(cell_at(tables, cell)); }));
+    store_cell<0>(cell_at(out, at), quot_sigma_label(k, image, [&](uint32_t cell) { return load_cell(cell_at(tables, cell)); }));
 }
 
 inline bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {

@@ -14,18 +14,17 @@
 //   * sigma_scan_kernel<NT>: a workgroup makes the terms of its chunk again, scans the numerators upwards and the denominators
 //     downwards -- in the lane, across the wave by shuffles, across waves through LDS -- and stores Z through aesw_store.h's flavour;
 //   * the entry points, the host functions and the checks that are theirs alone.
+// How a cell lies in memory, moves between lanes and is scanned over a wave is aesw_fr_dev.h's.
 // No atomic, no look-back flag, nothing to reset: the passes are ordered by the stream and every output word is stored once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <new>
-#include <utility>
 
 #include "../../../include/aesw_sigma.h"
 #include "../aesw_entry.h"
-#include "../aesw_report_dev.h"
+#include "../aesw_fr_dev.h"
 #include "../aesw_sigma.h"
-#include "../aesw_store.h"
 
 namespace aesw_sigma {
 using namespace aesw;
@@ -40,65 +39,6 @@ static_assert(sizeof(aesw_copy_edge) == 8, "the edges are read as include/aesw.h
 #define AESW_SIGMA_PASSES 0x1f
 #endif
 constexpr unsigned PASSES = AESW_SIGMA_PASSES, PASS_PREPARE = 1, PASS_CHUNK = 2, PASS_CARRY = 4, PASS_CHAIN = 8, PASS_SCAN = 16;
-
-// f(i) for i = 0 ... N - 1 with i a constant of the type system: a pack expansion, not a loop, so that a cell array indexed by it
-// stays in registers (grand_unrolled).
-template <class F, int... I>
-__device__ __forceinline__ void each(F &&f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void unrolled(F &&f) {
-    each(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ Fr load_cell(const u32x4 *p) {
-    const u32x4 lo = p[0], hi = p[1];
-    return Fr{{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}};
-}
-template <int NT>
-__device__ __forceinline__ void store_cell(u32x4 *p, const Fr &v) {
-    gstore<NT>(p, u32x4{v.l[0], v.l[1], v.l[2], v.l[3]});
-    gstore<NT>(p + 1, u32x4{v.l[4], v.l[5], v.l[6], v.l[7]});
-}
-__device__ __forceinline__ const u32x4 *cell_at(const u32x4 *base, uint64_t i) { return base + i * 2; }
-__device__ __forceinline__ u32x4 *cell_at(u32x4 *base, uint64_t i) { return base + i * 2; }
-__device__ __forceinline__ Fr shfl_up_cell(const Fr &v, int o) {
-    Fr r = FR_ZERO;
-#pragma unroll
-    for (int i = 0; i < FR_LIMBS; ++i) r.l[i] = __shfl_up(v.l[i], o, LANES);
-    return r;
-}
-__device__ __forceinline__ Fr shfl_down_cell(const Fr &v, int o) {
-    Fr r = FR_ZERO;
-#pragma unroll
-    for (int i = 0; i < FR_LIMBS; ++i) r.l[i] = __shfl_down(v.l[i], o, LANES);
-    return r;
-}
-__device__ __forceinline__ Fr shfl_xor_cell(const Fr &v, int o) {
-    Fr r = FR_ZERO;
-#pragma unroll
-    for (int i = 0; i < FR_LIMBS; ++i) r.l[i] = __shfl_xor(v.l[i], o, LANES);
-    return r;
-}
-// The inclusive scan of one cell per lane over a wave: upwards lane l ends with the product of lanes 0 ... l, downwards with that
-// of lanes l ... 63.  Every lane shuffles; the lanes that have a partner multiply.
-__device__ __forceinline__ Fr wave_scan_up(Fr v, uint32_t lane) {
-#pragma unroll 1
-    for (int o = 1; o < LANES; o <<= 1) {
-        const Fr other = shfl_up_cell(v, o);
-        if (lane >= (uint32_t)o) v = fr_mul(other, v);
-    }
-    return v;
-}
-__device__ __forceinline__ Fr wave_scan_down(Fr v, uint32_t lane) {
-#pragma unroll 1
-    for (int o = 1; o < LANES; o <<= 1) {
-        const Fr other = shfl_down_cell(v, o);
-        if (lane + (uint32_t)o < (uint32_t)LANES) v = fr_mul(other, v);
-    }
-    return v;
-}
 
 // ---- the power tables ---------------------------------------------------------------------------------------------------------
 
@@ -139,7 +79,7 @@ __device__ __forceinline__ void lane_terms(const ProductParams &p, uint32_t set,
     Fr w[ROWS];  // omega^(i0 + q): the rows of a lane share the high cell
     {
         const Fr high = load_cell(cell_at(p.high, sigma_high_index(i0)));
-        unrolled<ROWS>([&](auto at) {
+        fr_unrolled<ROWS>([&](auto at) {
             constexpr int q = decltype(at)::value;
             w[q] = fr_mul(load_cell(cell_at(p.low, sigma_low_index(i0) + q)), high);
         });
@@ -152,7 +92,7 @@ __device__ __forceinline__ void lane_terms(const ProductParams &p, uint32_t set,
         const uint8_t *col = src < p.n_advice ? p.advice + ((uint64_t)src << p.k) : src - p.n_advice < p.n_fixed ? p.fixed + ((uint64_t)(src - p.n_advice) << p.k) : nullptr;
         const uint32_t bytes = col ? *reinterpret_cast<const uint32_t *>(col + i0) : 0u;
         const u32x4 cells = *reinterpret_cast<const u32x4 *>(p.map + ((uint64_t)c << p.k) + i0);
-        unrolled<ROWS>([&](auto at) {
+        fr_unrolled<ROWS>([&](auto at) {
             constexpr int q = decltype(at)::value;
             if (i0 + q < p.n_rows) {
                 const Fr vg = fr_add(load_cell(cell_at(p.fr_lut, bytes >> (8 * q) & 255u)), gamma);
@@ -171,7 +111,7 @@ __device__ __forceinline__ void lane_terms(const ProductParams &p, uint32_t set,
             }
         });
     }
-    unrolled<ROWS>([&](auto at) {
+    fr_unrolled<ROWS>([&](auto at) {
         constexpr int q = ROWS - 1 - decltype(at)::value;  // downwards: `first` ends as the lowest row
         if (fr_is_zero(den[q])) {
             den[q] = FR_ONE;
@@ -191,7 +131,7 @@ __global__ void __launch_bounds__(THREADS) sigma_chunk_kernel(const ProductParam
     uint32_t sums[2], first_row;
     lane_terms(p, set, blockIdx.x * SIGMA_CHUNK + threadIdx.x * ROWS, num, den, sums[0], first_row, sums[1]);
     Fr n = num[0], d = den[0];
-    unrolled<ROWS - 1>([&](auto at) {
+    fr_unrolled<ROWS - 1>([&](auto at) {
         n = fr_mul(n, num[decltype(at)::value + 1]);
         d = fr_mul(d, den[decltype(at)::value + 1]);
     });
@@ -332,7 +272,7 @@ __global__ void __launch_bounds__(THREADS) sigma_scan_kernel(const ProductParams
     Fr num[ROWS], den[ROWS];
     uint32_t zeros, first_row, out_of_range;  // the chunk kernel's to report
     lane_terms(p, set, i0, num, den, zeros, first_row, out_of_range);
-    unrolled<ROWS - 1>([&](auto at) {
+    fr_unrolled<ROWS - 1>([&](auto at) {
         constexpr int q = decltype(at)::value;
         num[q + 1] = fr_mul(num[q], num[q + 1]);                        // inclusive upwards, in the lane
         den[ROWS - 2 - q] = fr_mul(den[ROWS - 2 - q], den[ROWS - 1 - q]);  // inclusive downwards
@@ -354,7 +294,7 @@ __global__ void __launch_bounds__(THREADS) sigma_scan_kernel(const ProductParams
     const Fr base = fr_mul(fr_mul(below, excl_n), fr_mul(above, excl_d));
     const uint32_t keep = p.set_words[set][3];  // rows below it keep their value, the others are zero
     u32x4 *z = cell_at(p.z, ((uint64_t)set << p.k) + i0);
-    unrolled<ROWS>([&](auto at_q) {
+    fr_unrolled<ROWS>([&](auto at_q) {
         constexpr int q = decltype(at_q)::value;
         if (i0 + q <= p.last_row) {
             Fr v = FR_ZERO;
@@ -441,10 +381,9 @@ int aesw_sigma_product_device(aesw_ctx *ctx, uint32_t k, uint32_t n_cols, uint32
     if (!d_source || !aligned_to(d_source, 4)) return refuse(ctx, call, "d_source must be there and 4-byte aligned");
     if (!d_map || !aligned_to(d_map, 16)) return refuse(ctx, call, "d_map must be there and 16-byte aligned");
     if (!d_tables || !aligned_to(d_tables, 16)) return refuse(ctx, call, "d_tables must be there and 16-byte aligned");
-    if (!d_beta || !d_gamma || !aligned_to(d_beta, 16) || !aligned_to(d_gamma, 16)) return refuse(ctx, call, "d_beta and d_gamma must be there and 16-byte aligned");
-    if (!d_z_fr || !d_closing_fr || !aligned_to(d_z_fr, 16) || !aligned_to(d_closing_fr, 16))
-        return refuse(ctx, call, "d_z_fr and d_closing_fr must be there and 16-byte aligned");
-    if (!d_workspace || !aligned_to(d_workspace, 16)) return refuse(ctx, call, "d_workspace must be there and 16-byte aligned");
+    if (const char *why = bad_challenges(d_beta, d_gamma)) return refuse(ctx, call, why);
+    if (const char *why = bad_product_outputs(d_z_fr, d_closing_fr)) return refuse(ctx, call, why);
+    if (const char *why = bad_workspace(d_workspace)) return refuse(ctx, call, why);
     if (const char *why = bad_report(d_report)) return refuse(ctx, call, why);
     DeviceGuard g(ctx->device);
     if (!g.ok) return AESW_ERR_NO_DEVICE;

@@ -19,8 +19,7 @@
 
 #include "../../../include/aesw_theta.h"
 #include "../aesw_entry.h"
-#include "../aesw_report_dev.h"
-#include "../aesw_store.h"
+#include "../aesw_fr_dev.h"
 #include "../aesw_theta.h"
 
 namespace aesw_theta {
@@ -30,11 +29,6 @@ constexpr int THREADS = 256, ROWS_PER_LANE = 4, ROWS_PER_GROUP = THREADS * ROWS_
 static_assert(sizeof(Fr) == 32 && sizeof(aesw_theta_report) == 2 * sizeof(uint64_t) && sizeof(aesw_mult_report) == 3 * sizeof(uint64_t),
               "a cell is two 16-byte pieces; the kernels address the reports as u64 words");
 static_assert(AESW_THETA_TABLES == THETA_TABLES && AESW_THETA_ARGUMENTS == THETA_TAGS && AESW_THETA_MISS == THETA_MISS, "the header's constants are the rule's");
-
-__device__ __forceinline__ Fr load_cell(const u32x4 *p) {
-    const u32x4 lo = p[0], hi = p[1];
-    return Fr{{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}};
-}
 
 // grid: x = 256 table rows, y = the table
 __global__ void __launch_bounds__(THREADS) theta_table_kernel(const u32x4 *__restrict__ theta_cell, const uint8_t *__restrict__ tab768,

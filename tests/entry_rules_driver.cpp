@@ -8,6 +8,9 @@
 //   slabs <d_x> <d_y> <d_z>
 //   keys <k> <slab: 0 | 1> <kx> <ky> <kz>                 "<with_keys> <text>"
 //   outputs <k> <with_k> <n_sets> <d_mult> <d_report>
+//   challenges <d_beta> <d_gamma>
+//   product_outputs <d_z_fr> <d_closing_fr>
+//   workspace <d_workspace>
 #include "aesw_entry_rules.h"
 
 #include <cinttypes>
@@ -23,7 +26,7 @@ int main() {
     char cmd[16];
     while (std::scanf("%15s", cmd) == 1) {
         uint64_t a[5] = {0, 0, 0, 0, 0};
-        const int want = !std::strcmp(cmd, "slabs") ? 3 : (!std::strcmp(cmd, "keys") || !std::strcmp(cmd, "outputs")) ? 5 : 1;
+        const int want = !std::strcmp(cmd, "slabs") ? 3 : (!std::strcmp(cmd, "keys") || !std::strcmp(cmd, "outputs")) ? 5 : (!std::strcmp(cmd, "challenges") || !std::strcmp(cmd, "product_outputs")) ? 2 : 1;
         for (int i = 0; i < want; ++i)
             if (std::scanf("%" SCNu64, &a[i]) != 1) return 2;
         const char *why = nullptr;
@@ -38,6 +41,9 @@ int main() {
             why = bad_key_columns(p, (uint32_t)a[0]);
             std::printf("%d ", with_keys(p, (uint32_t)a[0]) ? 1 : 0);
         } else if (!std::strcmp(cmd, "outputs")) why = bad_outputs((uint32_t)a[0], a[1] != 0, (uint32_t)a[2], at<uint32_t>(a[3]), at<aesw_mult_report>(a[4]));
+        else if (!std::strcmp(cmd, "challenges")) why = bad_challenges(at(a[0]), at(a[1]));
+        else if (!std::strcmp(cmd, "product_outputs")) why = bad_product_outputs(at(a[0]), at(a[1]));
+        else if (!std::strcmp(cmd, "workspace")) why = bad_workspace(at(a[0]));
         else return 2;
         std::printf("%s\n", why ? why : "-");
     }

@@ -1,6 +1,6 @@
 """The argument rules the libraries next to libaesw.so share (csrc/aesw_entry_rules.h: the DENSE-or-PACKED layout, the bounds of
 k and n_sets, "there and aligned" for a report and for the block slabs, when the key columns count, and what both accumulators
-check of their outputs).  The header is compiled alone with g++ -- no ROCm include, no context, no GPU -- behind
+check of their outputs; the challenges, the outputs and the workspace of the grand-product calls).  The header is compiled alone with g++ -- no ROCm include, no context, no GPU -- behind
 tests/entry_rules_driver.cpp.  Every text is held against MESSAGES, written out here as the entry points said them before the
 rules were stated once; for each rule the smallest accepting argument and the nearest refusing one."""
 import subprocess
@@ -17,6 +17,9 @@ MESSAGES = {
     "slabs": "d_x, d_y and d_z must be there and 16-byte aligned",
     "keys": "the key columns must be 16-byte aligned",
     "mult": "d_mult must be there and 16-byte aligned",
+    "challenges": "d_beta and d_gamma must be there and 16-byte aligned",
+    "product_outputs": "d_z_fr and d_closing_fr must be there and 16-byte aligned",
+    "workspace": "d_workspace must be there and 16-byte aligned",
 }
 OK = "-"
 A = 0x10000  # an address aligned to anything asked here
@@ -90,3 +93,14 @@ def test_what_the_accumulators_check_of_their_outputs_in_their_order(ask):
     assert ask(("outputs", 2, 1, 1, 0, A), ("outputs", 2, 1, 1, A + 8, A)) == [MESSAGES["mult"]] * 2
     # a call that takes no k (the reset) does not look at it
     assert ask(("outputs", 0, 0, 1, A, A), ("outputs", 99, 0, 0, A, A)) == [OK, MESSAGES["sets"]]
+
+
+def test_what_the_grand_product_calls_take_alike(ask):
+    for rule in ("challenges", "product_outputs"):  # a pair of Fr cells or columns: both there, both 16-byte aligned
+        bad = MESSAGES[rule]
+        assert ask((rule, A, A + 32), (rule, A + 16, A)) == [OK, OK]
+        assert ask((rule, 0, 0), (rule, 0, A), (rule, A, 0)) == [bad] * 3
+        assert ask((rule, A + 8, A + 8), (rule, A + 8, A), (rule, A, A + 8), (rule, A + 1, A), (rule, A, A + 4)) == [bad] * 5
+    bad = MESSAGES["workspace"]
+    assert ask(("workspace", A), ("workspace", A + 16)) == [OK, OK]
+    assert ask(("workspace", 0), ("workspace", A + 8), ("workspace", A + 4), ("workspace", A + 1)) == [bad] * 4
