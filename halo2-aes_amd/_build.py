@@ -21,6 +21,8 @@
                                   extended-coset form (include/aesw_ntt.h), built alike
   halo2-aes_amd/libaesw_quot.so   the one entry of QUOTIENT_LIBRARIES: sigma as Fr columns, for the quotient h(X)
                                   (include/aesw_quot.h), built alike
+  halo2-aes_amd/libaesw_open.so   the one entry of OPENING_LIBRARIES: coefficient columns evaluated at points, folded under v and
+                                  divided by (X - z) (include/aesw_open.h), built alike
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The .so is git-ignored
 but travels to the GPU box with the snapshot.  (The test-only artefacts are
@@ -179,6 +181,15 @@ QUOTIENT_LIBRARIES = {
 QUOT_LIB = PKG / "libaesw_quot.so"
 
 
+# What the prover does with coefficient columns after its last challenge: evaluations at points, the fold under v and the division
+# by (X - z).  It needs the field header and its own rules alone.  A sixth table, named by opening_library_names(): the three name
+# functions above are held at what they are by the tests of the tables above, and __graft_entry__.build() walks this one last.
+OPENING_LIBRARIES = {
+    "open": ([CSRC / "open" / "aesw_open.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_open.h"], INCLUDE / "aesw_open.h"),
+}
+OPEN_LIB = PKG / "libaesw_open.so"
+
+
 def library_names() -> list:
     """Every library build_satellite() builds, in the order of the three tables."""
     return list(SATELLITES) + list(FIELD_LIBRARIES) + list(ARGUMENT_LIBRARIES)
@@ -194,16 +205,21 @@ def quotient_library_names() -> list:
     return list(QUOTIENT_LIBRARIES)
 
 
+def opening_library_names() -> list:
+    """The entries of OPENING_LIBRARIES: built by build_satellite() as well, behind quotient_library_names()."""
+    return list(OPENING_LIBRARIES)
+
+
 def library_entry(name: str):
-    """(sources, headers beyond SATELLITE_HEADERS, public header) of `name`, whichever of the five tables holds it."""
-    for table in (SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES, QUOTIENT_LIBRARIES):
+    """(sources, headers beyond SATELLITE_HEADERS, public header) of `name`, whichever of the six tables holds it."""
+    for table in (SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES, QUOTIENT_LIBRARIES, OPENING_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
 
 
 def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
-    """libaesw_<name>.so of an entry of SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES or QUOTIENT_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
+    """libaesw_<name>.so of an entry of SATELLITES, FIELD_LIBRARIES, ARGUMENT_LIBRARIES, DOMAIN_LIBRARIES, QUOTIENT_LIBRARIES or OPENING_LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
     A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are.  With `extra_flags` and
     another `out` (a file name next to libaesw.so) a measurement variant of it (tools/vacc_bench.py: -DAESW_VACC_WAVES=16)."""
     sources, headers, public = library_entry(name)

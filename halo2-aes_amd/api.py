@@ -30,6 +30,7 @@ SIGMA_LIB_PATH = _PKG / "libaesw_sigma.so"  # the grand products of the permutat
 GRAND_LIB_PATH = _PKG / "libaesw_grand.so"  # the grand product Z of every lookup argument from beta and gamma (include/aesw_grand.h)
 NTT_LIB_PATH = _PKG / "libaesw_ntt.so"  # columns of Fr cells between Lagrange, coefficient and extended-coset form (include/aesw_ntt.h)
 QUOT_LIB_PATH = _PKG / "libaesw_quot.so"  # sigma of the permutation argument as Fr columns, for the quotient h(X) (include/aesw_quot.h)
+OPEN_LIB_PATH = _PKG / "libaesw_open.so"  # coefficient columns evaluated at points, folded under v and divided by (X - z) (include/aesw_open.h)
 CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
@@ -279,6 +280,13 @@ NTT_SYMBOLS = {
 QUOT_SYMBOLS = {
     "aesw_quot_sigma_fr_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P]),
 }
+# include/aesw_open.h
+OPEN_SYMBOLS = {
+    "aesw_open_workspace_bytes": (C.c_size_t, [_U32, _U32, _U32]),
+    "aesw_open_evaluate_device": (_I, [_P, _U32, _U32, _U32, _P, _P, _P, _P, _P]),
+    "aesw_open_fold_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P]),
+    "aesw_open_divide_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P]),
+}
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
 
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
@@ -299,6 +307,7 @@ _LIBRARIES = {
     "sigma": (SIGMA_LIB_PATH, SIGMA_SYMBOLS, _NO_FALLBACK),
     "ntt": (NTT_LIB_PATH, NTT_SYMBOLS, _NO_FALLBACK),
     "quot": (QUOT_LIB_PATH, QUOT_SYMBOLS, _NO_FALLBACK),
+    "open": (OPEN_LIB_PATH, OPEN_SYMBOLS, _NO_FALLBACK),
 }
 _loaded = {}  # name -> the CDLL of the default path
 
@@ -407,6 +416,12 @@ def load_quot_library(path: Path | None = None) -> C.CDLL:
     return _load("quot", path)
 
 
+def load_open_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_open.so (in-tree): coefficient columns at points behind Context.evaluate_columns, fold_columns and
+    divide_columns."""
+    return _load("open", path)
+
+
 def permutation_columns(n_sets: int) -> int:
     """aesw_sigma_columns: the columns of the permutation argument of a FixedAes128Config<k, n_sets> circuit, 3 * n_sets + 2."""
     return int(load_sigma_library().aesw_sigma_columns(int(n_sets)))
@@ -438,6 +453,16 @@ def permutation_mapping(k: int, n_sets: int, n_blocks: int) -> np.ndarray:
 def fr_cell(value: int) -> np.ndarray:
     """uint8[32]: the Fr cell of `value` (any int, reduced mod r) -- value * 2^256 mod r, little-endian."""
     return np.frombuffer(((int(value) % FR_MODULUS << 256) % FR_MODULUS).to_bytes(32, "little"), np.uint8).copy()
+
+
+def rotated_points(x: int, k: int, rotations) -> np.ndarray:
+    """uint8 [len(rotations), 32]: the Fr cells of x * omega_k^r for every signed rotation r -- the points halo2 opens a column at
+    for a challenge x --, omega_k = 7^((r - 1) / 2^k) the generator of the 2^k rows (k at most 28).  Pure Python, through fr_cell."""
+    k = int(k)
+    if not 0 <= k <= 28:
+        raise ValueError("k must be 0 ... 28 (the field's 2-adicity)")
+    omega = pow(7, (FR_MODULUS - 1) >> k, FR_MODULUS)
+    return np.array([fr_cell(int(x) * pow(omega, int(r) % (1 << k), FR_MODULUS)) for r in rotations], np.uint8).reshape(-1, 32)
 
 
 def mult_bin(tag: int, x: int, y: int = 0):
@@ -1573,6 +1598,111 @@ class Context:
         self._check(rc, "aesw_quot_sigma_fr_device")
         return _out
 
+    def _open_columns(self, call, coeff, k):
+        """(k, n_cols) of `coeff`, a uint8 [n_cols, 2^k, 32] tensor of coefficient columns (or [2^k, 32], one column)"""
+        k = int(k)
+        if not 10 <= k <= 28:
+            raise AeswError(ERR_INVALID_ARG, call + ": k must be 10 ... 28")
+        if self._u8(coeff, "coeff").dim() not in (2, 3) or tuple(coeff.shape[-2:]) != (1 << k, 32):
+            raise ValueError("coeff must be a uint8 tensor of shape [n_cols, %d, 32] or [%d, 32]" % (1 << k, 1 << k))
+        return k, (coeff.shape[0] if coeff.dim() == 3 else 1)
+
+    def _open_cells(self, value, name):
+        """Points (or v) as the calls of libaesw_open.so read them, a uint8 [n, 32] tensor of cells on the device: an int or a
+        sequence of ints (reduced mod r and put into Montgomery form) and a numpy uint8 [n, 32] array of cells (rotated_points) are
+        uploaded, a uint8 [n, 32] or [32] tensor stays and is read when the kernels run."""
+        torch = self._torch()
+        if isinstance(value, (int, np.integer)):
+            value = [value]
+        if not isinstance(value, (torch.Tensor, np.ndarray)):
+            value = np.array([fr_cell(v) for v in value], np.uint8).reshape(-1, 32)
+        if isinstance(value, np.ndarray):
+            if value.dtype != np.uint8 or value.shape[-1:] != (32,):
+                raise ValueError("%s must be ints, or uint8 cells of shape [n, 32]" % name)
+            value = torch.from_numpy(np.ascontiguousarray(value)).to(self._dev())
+        if self._u8(value, name).dim() not in (1, 2) or value.shape[-1] != 32:
+            raise ValueError("%s must be ints, or uint8 cells of shape [n, 32]" % name)
+        return value.view(-1, 32)
+
+    def _open_workspace(self, k, n_cols, n_points, _workspace):
+        need = int(load_open_library().aesw_open_workspace_bytes(k, n_cols, n_points)) if n_cols < 2 ** 32 else 0
+        if _workspace is None:
+            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
+            return self._torch().empty(max(need, 16), dtype=self._torch().uint8, device=self._dev())
+        if self._u8(_workspace, "_workspace").numel() < need:
+            raise ValueError("_workspace must hold %d bytes" % need)
+        return _workspace
+
+    def evaluate_columns(self, coeff, k: int, points, out=None, _workspace=None):
+        """aesw_open_evaluate_device (libaesw_open.so): every coefficient column at every point, halo2's eval_polynomial -- a uint8
+        [n_cols, n_points, 32] tensor of cells ([n_points, 32] for a coeff of one column, [2^k, 32]), cell [c][p] = sum_i
+        coeff[c][i] * z_p^i.  coeff: uint8 [n_cols, 2^k, 32] Montgomery cells (what lagrange_to_coeff returns); points: 1 ... 16 of
+        them -- ints, the cells rotated_points returns, or a uint8 [n_points, 32] tensor on the device, read when the kernels run.
+        out: the tensor to write into; _workspace: a uint8 tensor to use instead of a fresh one (a capture)."""
+        call = "aesw_open_evaluate_device"
+        lib = load_open_library()
+        torch = self._torch()
+        k, n_cols = self._open_columns(call, coeff, k)
+        points = self._open_cells(points, "points")
+        n_points = points.shape[0]
+        shape = tuple(coeff.shape[:-2]) + (n_points, 32)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(out, "out").shape) != shape:
+            raise ValueError("out must be a uint8 tensor of shape %r" % (shape,))
+        _workspace = self._open_workspace(k, n_cols, n_points, _workspace)
+        rc = lib.aesw_open_evaluate_device(self._h, k, n_cols, n_points, coeff.data_ptr(), points.data_ptr(), out.data_ptr(), _workspace.data_ptr(), self._stream())
+        self._check(rc, call)
+        return out
+
+    def fold_columns(self, coeff, k: int, v, acc=None, out=None):
+        """aesw_open_fold_device: the columns of coeff folded under v, cell by cell -- a uint8 [2^k, 32] tensor, cell i =
+        (...((acc[i] * v + coeff[0][i]) * v + coeff[1][i])...) * v + coeff[n_cols - 1][i]; acc: a uint8 [2^k, 32] tensor, or None
+        for zero; out=acc folds into acc itself, so columns of separate tensors are folded by successive calls.  v: an int or a
+        uint8 [32] tensor on the device, read when the kernel runs.  The order is not pinned against halo2 (include/aesw_open.h)."""
+        call = "aesw_open_fold_device"
+        lib = load_open_library()
+        torch = self._torch()
+        k, n_cols = self._open_columns(call, coeff, k)
+        v = self._open_cells(v, "v")
+        if v.shape[0] != 1:
+            raise ValueError("v must be one int or one cell")
+        shape = (1 << k, 32)
+        if acc is not None and tuple(self._u8(acc, "acc").shape) != shape:
+            raise ValueError("acc must be a uint8 tensor of shape %r" % (shape,))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(out, "out").shape) != shape:
+            raise ValueError("out must be a uint8 tensor of shape %r" % (shape,))
+        rc = lib.aesw_open_fold_device(self._h, k, n_cols, coeff.data_ptr(), v.data_ptr(), None if acc is None else acc.data_ptr(), out.data_ptr(), self._stream())
+        self._check(rc, call)
+        return out
+
+    def divide_columns(self, coeff, k: int, point, out=None, _rem=None, _workspace=None):
+        """aesw_open_divide_device: (quot, rem) -- quot of coeff's shape, the coefficients of (p_c(X) - p_c(z)) / (X - z) for every
+        column c (halo2's kate_division of poly - eval; the last coefficient is 0), and rem a uint8 [n_cols, 32] tensor ([32] for
+        one column), p_c(z).  point: one int or a uint8 [32] tensor on the device.  out=coeff divides in place."""
+        call = "aesw_open_divide_device"
+        lib = load_open_library()
+        torch = self._torch()
+        k, n_cols = self._open_columns(call, coeff, k)
+        point = self._open_cells(point, "point")
+        if point.shape[0] != 1:
+            raise ValueError("point must be one int or one cell")
+        if out is None:
+            out = torch.empty_like(coeff)
+        elif tuple(self._u8(out, "out").shape) != tuple(coeff.shape):
+            raise ValueError("out must be a uint8 tensor of shape %r" % (tuple(coeff.shape),))
+        rem_shape = tuple(coeff.shape[:-2]) + (32,)
+        if _rem is None:
+            _rem = torch.empty(rem_shape, dtype=torch.uint8, device=self._dev())
+        elif tuple(self._u8(_rem, "_rem").shape) != rem_shape:
+            raise ValueError("_rem must be a uint8 tensor of shape %r" % (rem_shape,))
+        _workspace = self._open_workspace(k, n_cols, 1, _workspace)
+        rc = lib.aesw_open_divide_device(self._h, k, n_cols, coeff.data_ptr(), point.data_ptr(), out.data_ptr(), _rem.data_ptr(), _workspace.data_ptr(), self._stream())
+        self._check(rc, call)
+        return out, _rem
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1908,7 +2038,7 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr",
               "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
               "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
-              "extended_to_coeff", "permutation_columns_fr"):
+              "extended_to_coeff", "permutation_columns_fr", "evaluate_columns", "fold_columns", "divide_columns"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
