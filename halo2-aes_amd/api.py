@@ -19,19 +19,19 @@ from . import constants as K
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libaesw.so"            # HIP kernels + the C ABI of include/aesw.h
 HOST_LIB_PATH = _PKG / "libaesw_host.so"  # C++ mirror of the reference's host interface (include/aesw_host.h), above the C ABI
+CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 COLS_LIB_PATH = _PKG / "libaesw_cols.so"  # the checker of the assembled advice columns (include/aesw_cols.h), next to libaesw.so
 VALS_LIB_PATH = _PKG / "libaesw_vals.so"  # the checker of a VALUES witness (include/aesw_vals.h), next to libaesw.so
-MULT_LIB_PATH = _PKG / "libaesw_mult.so"  # the lookup multiplicities of a many-circuit batch (include/aesw_mult.h), next to libaesw.so
 ACC_LIB_PATH = _PKG / "libaesw_acc.so"    # the lookup multiplicities of one circuit, accumulated chunk by chunk (include/aesw_acc.h)
-VACC_LIB_PATH = _PKG / "libaesw_vacc.so"  # the same accumulated from a VALUES witness (include/aesw_vacc.h)
 PERM_LIB_PATH = _PKG / "libaesw_perm.so"  # plookup's permuted columns arranged from the multiplicities (include/aesw_perm.h)
+VACC_LIB_PATH = _PKG / "libaesw_vacc.so"  # the same accumulated from a VALUES witness (include/aesw_vacc.h)
+MULT_LIB_PATH = _PKG / "libaesw_mult.so"  # the lookup multiplicities of a many-circuit batch (include/aesw_mult.h), next to libaesw.so
 THETA_LIB_PATH = _PKG / "libaesw_theta.so"  # the lookup arguments compressed under theta (include/aesw_theta.h)
-SIGMA_LIB_PATH = _PKG / "libaesw_sigma.so"  # the grand products of the permutation argument from beta and gamma (include/aesw_sigma.h)
 GRAND_LIB_PATH = _PKG / "libaesw_grand.so"  # the grand product Z of every lookup argument from beta and gamma (include/aesw_grand.h)
+SIGMA_LIB_PATH = _PKG / "libaesw_sigma.so"  # the grand products of the permutation argument from beta and gamma (include/aesw_sigma.h)
 NTT_LIB_PATH = _PKG / "libaesw_ntt.so"  # columns of Fr cells between Lagrange, coefficient and extended-coset form (include/aesw_ntt.h)
 QUOT_LIB_PATH = _PKG / "libaesw_quot.so"  # sigma of the permutation argument as Fr columns, for the quotient h(X) (include/aesw_quot.h)
 OPEN_LIB_PATH = _PKG / "libaesw_open.so"  # coefficient columns evaluated at points, folded under v and divided by (X - z) (include/aesw_open.h)
-CIRC_LIB_PATH = _PKG / "libaesw_circ.so"  # the many-circuit witness checker (include/aesw_circ.h): one more kernel, next to libaesw.so
 
 STATUS = {
     0: "AESW_OK", 1: "AESW_ERR_INVALID_ARG", 2: "AESW_ERR_NO_DEVICE", 3: "AESW_ERR_HIP", 4: "AESW_ERR_NOMEM",
@@ -291,17 +291,18 @@ FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001 
 
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 _NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
-# the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT)
+# the in-tree libraries: name -> (path, symbols, what the FileNotFoundError adds to _BUILD_IT); behind libaesw.so and the host
+# mirror, one entry per library of _build.library_names(), in its order (tests/test_build_table.py holds the two together)
 _LIBRARIES = {
     "aesw": (LIB_PATH, SYMBOLS, _NO_FALLBACK),
     "host": (HOST_LIB_PATH, HOST_SYMBOLS, ""),
     "circ": (CIRC_LIB_PATH, CIRC_SYMBOLS, _NO_FALLBACK),
     "cols": (COLS_LIB_PATH, COLS_SYMBOLS, _NO_FALLBACK),
     "vals": (VALS_LIB_PATH, VALS_SYMBOLS, _NO_FALLBACK),
-    "mult": (MULT_LIB_PATH, MULT_SYMBOLS, _NO_FALLBACK),
     "acc": (ACC_LIB_PATH, ACC_SYMBOLS, _NO_FALLBACK),
-    "vacc": (VACC_LIB_PATH, VACC_SYMBOLS, _NO_FALLBACK),
     "perm": (PERM_LIB_PATH, PERM_SYMBOLS, _NO_FALLBACK),
+    "vacc": (VACC_LIB_PATH, VACC_SYMBOLS, _NO_FALLBACK),
+    "mult": (MULT_LIB_PATH, MULT_SYMBOLS, _NO_FALLBACK),
     "theta": (THETA_LIB_PATH, THETA_SYMBOLS, _NO_FALLBACK),
     "grand": (GRAND_LIB_PATH, GRAND_SYMBOLS, _NO_FALLBACK),
     "sigma": (SIGMA_LIB_PATH, SIGMA_SYMBOLS, _NO_FALLBACK),

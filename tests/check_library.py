@@ -1,7 +1,8 @@
-"""What the CPU tests of the built libraries share (test_circ_check_library.py, test_cols_check_library.py,
-test_vals_check_library.py, test_circuits_coverage.py, test_isa_lint.py): the kernels and exports `nm` shows, the functions a
-public header declares, and the per-kernel resource table of a code object (isa_extract.py) held against its tracked JSON
+"""What the CPU tests of the built libraries share (the thirteen test_*_library.py, test_build_table.py, test_library_loader.py,
+test_circuits_coverage.py, test_isa_lint.py): the build table, the kernels and exports `nm` shows, the functions a public
+header declares, what every library next to libaesw.so is held to (check_*), and the per-kernel resource table of a code object (isa_extract.py) held against its tracked JSON
 under profiles/.  Regenerate a tracked table on purpose with  AESW_UPDATE_ISA_JSON=1 python -m pytest tests/<the test file>."""
+import importlib.util
 import json
 import os
 import re
@@ -32,25 +33,71 @@ def declared(header, prefix):
     return sorted(set(re.findall(r"\b(%s\w+)\s*\(" % prefix, text)))
 
 
-def check_exports(pkg, name):
-    """libaesw_<name>.so is where build() puts it, exports exactly the aesw_<name>_ functions include/aesw_<name>.h declares,
-    api.py binds exactly those, and it finds libaesw.so (whose contexts it takes) next to itself.  Returns the declared names."""
+_header_declares = declared  # check_exports takes the caller's list under that name
+
+
+def build_module():
+    """halo2-aes_amd/_build.py as a module of its own: the build table, without importing the package."""
+    spec = importlib.util.spec_from_file_location("b", ROOT / "halo2-aes_amd" / "_build.py")
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def check_exports(pkg, name, declared=None):
+    """libaesw_<name>.so is where build() puts it, exports exactly the aesw_<name>_ functions include/aesw_<name>.h declares
+    (`declared`, where the caller lists them) and no other aesw_ symbol, api.py binds exactly those and caches the default
+    load, and its one NEEDED library of the project is libaesw.so (whose contexts it takes), found next to itself.  Returns
+    the declared names."""
     api, prefix = pkg.api, "aesw_%s_" % name
     lib, symbols = getattr(api, name.upper() + "_LIB_PATH"), getattr(api, name.upper() + "_SYMBOLS")
     assert lib.name == "libaesw_%s.so" % name and lib.parent == api.LIB_PATH.parent and lib.exists()
-    decl = declared("aesw_%s.h" % name, prefix)
+    decl = _header_declares("aesw_%s.h" % name, prefix)
+    assert declared is None or decl == declared
     exported = {line.split()[-1] for line in nm(lib, "-D", "--defined-only").splitlines() if " T " in line}
-    assert not [f for f in decl if f not in exported], (decl, sorted(exported)[:20])
-    assert sorted(f for f in exported if f.startswith(prefix)) == decl
-    loaded = getattr(api, "load_%s_library" % name)()
-    for f in decl:
-        assert f in symbols and getattr(loaded, f) is not None, f
-    assert sorted(symbols) == decl
+    assert sorted(f for f in exported if f.startswith("aesw_")) == decl, sorted(exported)[:20]
+    load = getattr(api, "load_%s_library" % name)
+    loaded = load()
+    assert load() is loaded
+    assert sorted(symbols) == decl and all(getattr(loaded, f) is not None for f in decl)
+    assert api._LIBRARIES[name] == (lib, symbols, api._NO_FALLBACK)
     dyn = subprocess.run(["readelf", "-d", str(lib)], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert "libaesw.so" in dyn and "$ORIGIN" in dyn, dyn
+    b = build_module()
+    assert not [n for n in b.library_names() + ["host"] if "libaesw_%s" % n in dyn], dyn
     # the sources live one level below csrc/, which keeps holding exactly the sources of libaesw.so
-    assert (ROOT / "halo2-aes_amd" / "csrc" / name / ("aesw_%s_check.hip" % name)).exists()
+    sources = b.library_entry(name)[0]
+    assert sources and all(s.exists() and s.parent == ROOT / "halo2-aes_amd" / "csrc" / name for s in sources), sources
     return decl
+
+
+def check_others_left_alone(pkg, name, words, named_by=(), symbol=None):
+    """No other library of api._LIBRARIES carries `aesw_<name>` (`symbol`, where the caller narrows it) or one of `words` (its
+    kernels) in `nm -C`, and the public headers that name `aesw_<name>` are its own and exactly `named_by`: the headers of the
+    libraries built over it, which say so."""
+    for other, (path, _symbols, _hint) in pkg.api._LIBRARIES.items():
+        if other != name:
+            text = nm(path, "-C")
+            assert not [w for w in (symbol or "aesw_" + name,) + tuple(words) if w in text], other
+    naming = sorted(h.name for h in (ROOT / "include").glob("*.h") if h.name != "aesw_%s.h" % name and "aesw_" + name in h.read_text())
+    assert naming == sorted(named_by), naming
+
+
+def check_missing_path(pkg, name, tmp_path):
+    """A path that does not exist is a FileNotFoundError that names it and says that nothing stands in for the library."""
+    missing = tmp_path / "nowhere" / getattr(pkg.api, name.upper() + "_LIB_PATH").name
+    with pytest.raises(FileNotFoundError) as e:
+        getattr(pkg.api, "load_%s_library" % name)(missing)
+    assert str(missing) in str(e.value) and "There is no fallback implementation." in str(e.value)
+
+
+def check_group_refuses(pkg, methods):
+    """Each of `methods` exists on Context and is refused by a Group with ERR_INVALID_ARG."""
+    for method in methods:
+        assert callable(getattr(pkg.api.Context, method)), method
+        with pytest.raises(pkg.AeswError) as e:
+            getattr(pkg.Group, method)(None)
+        assert e.value.status == pkg.api.ERR_INVALID_ARG
 
 
 def check_swept(lib, launched):

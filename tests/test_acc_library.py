@@ -1,17 +1,13 @@
 """libaesw_acc.so without a GPU: that build() makes it and what it is made of.
 
   * it exists after build(), exports exactly the aesw_acc_ functions include/aesw_acc.h declares, api.ACC_SYMBOLS binds exactly
-    those, its NEEDED entry is libaesw.so via $ORIGIN (and libaesw_mult.so is none), and the Python face is there;
+    those, its NEEDED entry is libaesw.so via $ORIGIN (and no other library of the project is one), and the Python face is there;
   * every __global__ instantiation in it is launched by the GPU sweep (tests/acc_cases.py), and that list names nothing else;
   * its code object: no scratch, no VGPR spills, at most 256 unified registers, at most 160 KiB of static LDS; compared with the
     tracked table profiles/isa_resources_acc.json (regenerate it on purpose with AESW_UPDATE_ISA_JSON=1 python -m pytest
     tests/test_acc_library.py);
   * aesw_acc_default_chunk is a function of the shape alone and never 0;
-  * the other libraries and their headers carry none of the new symbols."""
-import subprocess
-
-import pytest
-
+  * the other libraries carry none of the new symbols; the headers that name the library are the two built over it."""
 import acc_cases as ac
 import check_library as cl
 from isa_extract import needs_llvm
@@ -19,37 +15,17 @@ from isa_extract import needs_llvm
 TABLE = cl.ROOT / "profiles" / "isa_resources_acc.json"
 code_object = cl.code_object_fixture("ACC_LIB_PATH")
 DECLARED = ["aesw_acc_add_device", "aesw_acc_add_device_chunk", "aesw_acc_add_key_device", "aesw_acc_default_chunk", "aesw_acc_reset_device"]
+METHODS = ("multiplicity_accumulator",)
 
 
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
-    api = pkg.api
-    lib = api.ACC_LIB_PATH
-    assert lib.name == "libaesw_acc.so" and lib.parent == api.LIB_PATH.parent and lib.exists()
-    decl = cl.declared("aesw_acc.h", "aesw_acc_")
-    assert decl == DECLARED
-    exported = {line.split()[-1] for line in cl.nm(lib, "-D", "--defined-only").splitlines() if " T " in line}
-    assert sorted(f for f in exported if f.startswith("aesw_")) == decl, sorted(exported)[:20]
-    loaded = api.load_acc_library()
-    assert api.load_acc_library() is loaded
-    assert sorted(api.ACC_SYMBOLS) == decl and all(getattr(loaded, f) is not None for f in decl)
-    dyn = subprocess.run(["readelf", "-d", str(lib)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    assert "libaesw.so" in dyn and "$ORIGIN" in dyn and "libaesw_mult" not in dyn, dyn
-    assert (cl.ROOT / "halo2-aes_amd" / "csrc" / "acc" / "aesw_acc.hip").exists()  # one level below csrc/, as every satellite's
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("b", cl.ROOT / "halo2-aes_amd" / "_build.py")
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    assert "acc" in b.SATELLITES and b.ACC_LIB == lib
-    assert callable(pkg.Context.multiplicity_accumulator)
+    cl.check_exports(pkg, "acc", DECLARED)
     for method in ("reset", "add", "add_key", "histograms", "report"):
-        assert callable(getattr(api.MultiplicityAccumulator, method)), method
+        assert callable(getattr(pkg.api.MultiplicityAccumulator, method)), method
 
 
 def test_a_missing_path_says_how_to_build_it(pkg, tmp_path):
-    missing = tmp_path / "nowhere" / pkg.api.ACC_LIB_PATH.name
-    with pytest.raises(FileNotFoundError) as e:
-        pkg.api.load_acc_library(missing)
-    assert str(missing) in str(e.value) and "There is no fallback implementation." in str(e.value)
+    cl.check_missing_path(pkg, "acc", tmp_path)
 
 
 def test_the_default_chunk_depends_on_the_shape_alone_and_is_never_zero(pkg):
@@ -67,17 +43,11 @@ def test_the_default_chunk_depends_on_the_shape_alone_and_is_never_zero(pkg):
 
 
 def test_the_other_libraries_are_left_alone(pkg):
-    for other in (pkg.api.LIB_PATH, pkg.api.CIRC_LIB_PATH, pkg.api.COLS_LIB_PATH, pkg.api.VALS_LIB_PATH, pkg.api.MULT_LIB_PATH):
-        text = cl.nm(other, "-C")
-        assert "aesw_acc" not in text and "acc_add_kernel" not in text, other
-    for header in ("aesw.h", "aesw_circ.h", "aesw_cols.h", "aesw_vals.h", "aesw_host.h", "aesw_mult.h"):
-        assert "aesw_acc" not in (cl.ROOT / "include" / header).read_text(), header
+    cl.check_others_left_alone(pkg, "acc", ("acc_add_kernel",), named_by=("aesw_perm.h", "aesw_vacc.h"))
 
 
 def test_a_group_refuses(pkg):
-    with pytest.raises(pkg.AeswError) as e:
-        pkg.Group.multiplicity_accumulator(None, 12, 1)
-    assert e.value.status == pkg.api.ERR_INVALID_ARG
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_every_kernel_of_the_library_is_swept_and_the_list_names_nothing_else(pkg):

@@ -17,12 +17,21 @@ from isa_extract import needs_llvm
 
 TABLE = cl.ROOT / "profiles" / "isa_resources_circ.json"
 code_object = cl.code_object_fixture("CIRC_LIB_PATH")
+METHODS = ("check_circuits",)
 
 
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
     declared = cl.check_exports(pkg, "circ")
     assert "aesw_circ_check_witness_device" in declared and len(declared) >= 2, declared
-    assert callable(pkg.Context.check_circuits)
+
+
+def test_the_other_libraries_are_left_alone(pkg):
+    # libaesw.so assembles many circuits in a namespace aesw_circ of its own: what no other library holds is the C prefix
+    cl.check_others_left_alone(pkg, "circ", ("circ_check_kernel",), named_by=("aesw_cols.h", "aesw_vals.h"), symbol="aesw_circ_")
+
+
+def test_a_group_refuses(pkg):
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_the_product_library_is_left_alone(pkg):

@@ -7,7 +7,7 @@
   * its code object: no scratch, no VGPR spills, at most 256 unified registers, compared with the tracked table
     profiles/isa_resources_cols.json.  Regenerate that table on purpose with
     AESW_UPDATE_ISA_JSON=1 python -m pytest tests/test_cols_check_library.py;
-  * libaesw.so and libaesw_circ.so carry none of the new symbols.
+  * the other libraries and their headers carry none of the new symbols.
 
 The checks every checker library gets are in tests/check_library.py."""
 import check_library as cl
@@ -16,20 +16,20 @@ from isa_extract import needs_llvm
 
 TABLE = cl.ROOT / "profiles" / "isa_resources_cols.json"
 code_object = cl.code_object_fixture("COLS_LIB_PATH")
+METHODS = ("check_columns",)
 
 
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
     declared = cl.check_exports(pkg, "cols")
     assert "aesw_cols_check_device" in declared and "aesw_cols_cell_index" in declared and len(declared) >= 5, declared
-    assert callable(pkg.Context.check_columns)
 
 
 def test_the_other_libraries_are_left_alone(pkg):
-    for other in (pkg.api.LIB_PATH, pkg.api.CIRC_LIB_PATH):
-        text = cl.nm(other, "-C")
-        assert "cols_check_kernel" not in text and "aesw_cols_" not in text, other
-    for header in ("aesw.h", "aesw_circ.h"):
-        assert "aesw_cols" not in (cl.ROOT / "include" / header).read_text()
+    cl.check_others_left_alone(pkg, "cols", ("cols_check_kernel",))
+
+
+def test_a_group_refuses(pkg):
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_the_cell_index_helper(pkg):

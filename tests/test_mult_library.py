@@ -7,9 +7,8 @@
   * its code object: no scratch, no VGPR spills, at most 256 unified registers; the PRIVATE form counts with LDS adds and has no
     global atomic but the report's, the DIRECT form is the one with global atomic adds; compared with the tracked table
     profiles/isa_resources_mult.json (regenerate it on purpose with AESW_UPDATE_ISA_JSON=1 python -m pytest tests/test_mult_library.py);
-  * the four other libraries and their headers carry none of the new symbols."""
+  * the other libraries carry none of the new symbols; the headers that name the library are the five that include aesw_mult.h."""
 import shutil
-import subprocess
 
 import pytest
 
@@ -20,28 +19,12 @@ from isa_extract import needs_llvm
 TABLE = cl.ROOT / "profiles" / "isa_resources_mult.json"
 code_object = cl.code_object_fixture("MULT_LIB_PATH")
 DECLARED = ["aesw_mult_bin", "aesw_mult_count_device", "aesw_mult_count_device_form", "aesw_mult_default_form"]
+METHODS = ("lookup_multiplicities",)
 
 
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
-    api = pkg.api
-    lib = api.MULT_LIB_PATH
-    assert lib.name == "libaesw_mult.so" and lib.parent == api.LIB_PATH.parent and lib.exists()
-    decl = cl.declared("aesw_mult.h", "aesw_mult_")
-    assert decl == DECLARED
-    exported = {line.split()[-1] for line in cl.nm(lib, "-D", "--defined-only").splitlines() if " T " in line}
-    assert sorted(f for f in exported if f.startswith("aesw_mult")) == decl, sorted(exported)[:20]
-    loaded = api.load_mult_library()
-    assert sorted(api.MULT_SYMBOLS) == decl and all(getattr(loaded, f) is not None for f in decl)
-    dyn = subprocess.run(["readelf", "-d", str(lib)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    assert "libaesw.so" in dyn and "$ORIGIN" in dyn, dyn
-    assert (cl.ROOT / "halo2-aes_amd" / "csrc" / "mult" / "aesw_mult.hip").exists()  # one level below csrc/, as every satellite's
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("b", cl.ROOT / "halo2-aes_amd" / "_build.py")
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    assert list(b.SATELLITES)[-1] == "mult" and b.MULT_LIB == lib
-    assert callable(pkg.Context.lookup_multiplicities)
-    assert ctypes_fields(api.MultReport) == ["lookups", "misses", "first_miss"]
+    cl.check_exports(pkg, "mult", DECLARED)
+    assert ctypes_fields(pkg.api.MultReport) == ["lookups", "misses", "first_miss"]
 
 
 def ctypes_fields(struct):
@@ -74,17 +57,13 @@ def test_the_pure_host_functions(pkg):
 
 
 def test_the_other_libraries_are_left_alone(pkg):
-    for other in (pkg.api.LIB_PATH, pkg.api.CIRC_LIB_PATH, pkg.api.COLS_LIB_PATH, pkg.api.VALS_LIB_PATH):
-        text = cl.nm(other, "-C")
-        assert "aesw_mult" not in text and "mult_private_kernel" not in text and "mult_direct_kernel" not in text, other
-    for header in ("aesw.h", "aesw_circ.h", "aesw_cols.h", "aesw_vals.h", "aesw_host.h"):
-        assert "aesw_mult" not in (cl.ROOT / "include" / header).read_text(), header
+    # the multiplicity family and what compresses its table include aesw_mult.h (the row order, the bounds) and say so
+    family = ("aesw_acc.h", "aesw_grand.h", "aesw_perm.h", "aesw_theta.h", "aesw_vacc.h")
+    cl.check_others_left_alone(pkg, "mult", ("mult_private_kernel", "mult_direct_kernel"), named_by=family)
 
 
 def test_a_group_refuses(pkg):
-    with pytest.raises(pkg.AeswError) as e:
-        pkg.Group.lookup_multiplicities(None, 12, 1, None, None, [1])
-    assert e.value.status == pkg.api.ERR_INVALID_ARG
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_every_kernel_of_the_library_is_swept_and_the_list_names_nothing_else(pkg):

@@ -1,19 +1,13 @@
 """libaesw_ntt.so without a GPU: that build() makes it and what it is made of.
 
   * it exists after build(), exports exactly the aesw_ntt_ functions include/aesw_ntt.h declares, api.NTT_SYMBOLS binds exactly
-    those, its NEEDED entry is libaesw.so via $ORIGIN and no other library of the project is one; it is the one entry of
-    _build.DOMAIN_LIBRARIES, a fourth table that library_names() does not list and library_entry() knows;
+    those, its NEEDED entry is libaesw.so via $ORIGIN and no other library of the project is one;
   * a Group refuses; a missing path says how to build it;
   * every __global__ in it is launched by the GPU tests (tests/ntt_cases.py), and that list names nothing else;
   * its code object: no scratch, no VGPR spills, no atomic in any kernel, the field products as 64-bit multiply-adds, at most 256
     unified registers; compared with the tracked table profiles/isa_resources_ntt.json (regenerate it on purpose with
     AESW_UPDATE_ISA_JSON=1 python -m pytest tests/test_ntt_library.py);
   * the other libraries and their headers carry none of the new symbols."""
-import importlib.util
-import subprocess
-
-import pytest
-
 import check_library as cl
 import ntt_cases as nc
 from isa_extract import needs_llvm
@@ -22,76 +16,27 @@ TABLE = cl.ROOT / "profiles" / "isa_resources_ntt.json"
 code_object = cl.code_object_fixture("NTT_LIB_PATH")
 DECLARED = ["aesw_ntt_coeff_to_extended_device", "aesw_ntt_coeff_to_lagrange_device", "aesw_ntt_extended_to_coeff_device", "aesw_ntt_lagrange_to_coeff_device",
             "aesw_ntt_tables_bytes", "aesw_ntt_tables_device", "aesw_ntt_workspace_bytes"]
-OTHERS = ("LIB_PATH", "CIRC_LIB_PATH", "COLS_LIB_PATH", "VALS_LIB_PATH", "ACC_LIB_PATH", "VACC_LIB_PATH", "MULT_LIB_PATH", "PERM_LIB_PATH", "THETA_LIB_PATH",
-          "GRAND_LIB_PATH", "SIGMA_LIB_PATH", "HOST_LIB_PATH")
 METHODS = ("ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended", "extended_to_coeff")
 
 
-def _build_module():
-    spec = importlib.util.spec_from_file_location("b", cl.ROOT / "halo2-aes_amd" / "_build.py")
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    return b
-
-
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
-    api = pkg.api
-    lib = api.NTT_LIB_PATH
-    assert lib.name == "libaesw_ntt.so" and lib.parent == api.LIB_PATH.parent and lib.exists()
-    decl = cl.declared("aesw_ntt.h", "aesw_ntt_")
-    assert decl == DECLARED
-    exported = {line.split()[-1] for line in cl.nm(lib, "-D", "--defined-only").splitlines() if " T " in line}
-    assert sorted(f for f in exported if f.startswith("aesw_")) == decl, sorted(exported)[:20]
-    loaded = api.load_ntt_library()
-    assert api.load_ntt_library() is loaded
-    assert sorted(api.NTT_SYMBOLS) == decl and all(getattr(loaded, f) is not None for f in decl)
-    assert api._LIBRARIES["ntt"][:2] == (lib, api.NTT_SYMBOLS)
-    dyn = subprocess.run(["readelf", "-d", str(lib)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    assert "libaesw.so" in dyn and "$ORIGIN" in dyn, dyn
-    others = ("libaesw_acc", "libaesw_vacc", "libaesw_mult", "libaesw_perm", "libaesw_theta", "libaesw_grand", "libaesw_sigma", "libaesw_vals", "libaesw_circ",
-              "libaesw_cols", "libaesw_host")
-    assert not [s for s in others if s in dyn], dyn
-    assert (cl.ROOT / "halo2-aes_amd" / "csrc" / "ntt" / "aesw_ntt.hip").exists()  # one level below csrc/, as every satellite's
-    for name in METHODS:
-        assert callable(getattr(api.Context, name)), name
-    assert callable(api.load_ntt_library)
+    cl.check_exports(pkg, "ntt", DECLARED)
+    assert callable(pkg.api.load_ntt_library)
     header = (cl.ROOT / "include" / "aesw_ntt.h").read_text()
     assert '#include "aesw.h"' in header and header.count("#include \"aesw") == 1
     assert "NOT PINNED" in header and "NON-CANONICAL" in header
 
 
-def test_the_entry_is_a_fourth_table_and_the_three_stay_what_they_are():
-    b = _build_module()
-    assert list(b.DOMAIN_LIBRARIES) == ["ntt"] == b.domain_library_names() and b.NTT_LIB == b.PKG / "libaesw_ntt.so"
-    assert b.library_names() == list(b.SATELLITES) + list(b.FIELD_LIBRARIES) + list(b.ARGUMENT_LIBRARIES) and "ntt" not in b.library_names()
-    assert b.library_names()[-2:] == ["grand", "sigma"] and list(b.FIELD_LIBRARIES) == ["theta"] and len(b.SATELLITES) == 7
-    sources, headers, public = b.library_entry("ntt")
-    assert sources[0].parent.name == "ntt" and public.name == "aesw_ntt.h" and [h.name for h in headers] == ["aesw_fr.h", "aesw_sigma.h", "aesw_ntt.h"]
-    with pytest.raises(KeyError):
-        b.library_entry("nowhere")
-
-
 def test_a_missing_path_says_how_to_build_it(pkg, tmp_path):
-    missing = tmp_path / "nowhere" / pkg.api.NTT_LIB_PATH.name
-    with pytest.raises(FileNotFoundError) as e:
-        pkg.api.load_ntt_library(missing)
-    assert str(missing) in str(e.value) and "There is no fallback implementation." in str(e.value)
+    cl.check_missing_path(pkg, "ntt", tmp_path)
 
 
 def test_the_other_libraries_are_left_alone(pkg):
-    for other in OTHERS:
-        text = cl.nm(getattr(pkg.api, other), "-C")
-        assert "aesw_ntt" not in text and "ntt_pass_kernel" not in text and "ntt_tables_kernel" not in text, other
-    for header in sorted((cl.ROOT / "include").glob("*.h")):
-        if header.name != "aesw_ntt.h":
-            assert "aesw_ntt" not in header.read_text(), header.name
+    cl.check_others_left_alone(pkg, "ntt", ("ntt_pass_kernel", "ntt_tables_kernel"))
 
 
 def test_a_group_refuses(pkg):
-    for name in METHODS:
-        with pytest.raises(pkg.AeswError) as e:
-            getattr(pkg.Group, name)(None)
-        assert e.value.status == pkg.api.ERR_INVALID_ARG
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_every_kernel_of_the_library_is_launched_and_the_list_names_nothing_else(pkg):

@@ -1,19 +1,14 @@
 """libaesw_perm.so without a GPU: that build() makes it and what it is made of.
 
   * it exists after build(), exports exactly the aesw_perm_ functions include/aesw_perm.h declares, api.PERM_SYMBOLS binds exactly
-    those, its NEEDED entry is libaesw.so via $ORIGIN (and no other satellite is one), "perm" is an entry of _build.SATELLITES in
-    front of "vacc" and "mult", and the Python face is there;
+    those, its NEEDED entry is libaesw.so via $ORIGIN (and no other library of the project is one),
+    and the Python face is there;
   * every __global__ in it is launched by the GPU tests (tests/perm_cases.py), and that list names nothing else;
   * its code object: no scratch, no VGPR spills, no atomic at all, the scan's LDS two small arrays; compared with the tracked table
     profiles/isa_resources_perm.json (regenerate it on purpose with AESW_UPDATE_ISA_JSON=1 python -m pytest
     tests/test_perm_library.py);
   * aesw_perm_workspace_bytes is the rule header's layout;
   * the other libraries and their headers carry none of the new symbols."""
-import importlib.util
-import subprocess
-
-import pytest
-
 import check_library as cl
 import perm_cases as pc
 from isa_extract import needs_llvm
@@ -21,46 +16,18 @@ from isa_extract import needs_llvm
 TABLE = cl.ROOT / "profiles" / "isa_resources_perm.json"
 code_object = cl.code_object_fixture("PERM_LIB_PATH")
 DECLARED = ["aesw_perm_build_device", "aesw_perm_gather_fr_device", "aesw_perm_workspace_bytes"]
-OTHERS = ("LIB_PATH", "CIRC_LIB_PATH", "COLS_LIB_PATH", "VALS_LIB_PATH", "ACC_LIB_PATH", "VACC_LIB_PATH", "MULT_LIB_PATH", "HOST_LIB_PATH")
-
-
-def _build_module():
-    spec = importlib.util.spec_from_file_location("b", cl.ROOT / "halo2-aes_amd" / "_build.py")
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    return b
+METHODS = ("permuted_columns", "gather_fr")
 
 
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
-    api = pkg.api
-    lib = api.PERM_LIB_PATH
-    assert lib.name == "libaesw_perm.so" and lib.parent == api.LIB_PATH.parent and lib.exists()
-    decl = cl.declared("aesw_perm.h", "aesw_perm_")
-    assert decl == DECLARED
-    exported = {line.split()[-1] for line in cl.nm(lib, "-D", "--defined-only").splitlines() if " T " in line}
-    assert sorted(f for f in exported if f.startswith("aesw_")) == decl, sorted(exported)[:20]
-    loaded = api.load_perm_library()
-    assert api.load_perm_library() is loaded
-    assert sorted(api.PERM_SYMBOLS) == decl and all(getattr(loaded, f) is not None for f in decl)
-    assert api._LIBRARIES["perm"][:2] == (lib, api.PERM_SYMBOLS)
-    dyn = subprocess.run(["readelf", "-d", str(lib)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    assert "libaesw.so" in dyn and "$ORIGIN" in dyn, dyn
-    assert not [s for s in ("libaesw_acc", "libaesw_vacc", "libaesw_mult", "libaesw_vals", "libaesw_circ", "libaesw_cols", "libaesw_host") if s in dyn], dyn
-    assert (cl.ROOT / "halo2-aes_amd" / "csrc" / "perm" / "aesw_perm.hip").exists()  # one level below csrc/, as every satellite's
-    b = _build_module()
-    names = list(b.SATELLITES)
-    assert len(names) == 7 and names[-3:] == ["perm", "vacc", "mult"] and b.PERM_LIB == lib
-    assert [getattr(b, n.upper() + "_LIB").name for n in names] == ["libaesw_%s.so" % n for n in names]  # the tuple below SATELLITES
-    assert callable(api.Context.permuted_columns) and callable(api.Context.gather_fr) and callable(api.MultiplicityAccumulator.permuted_columns)
+    cl.check_exports(pkg, "perm", DECLARED)
+    assert callable(pkg.api.MultiplicityAccumulator.permuted_columns)
     header = (cl.ROOT / "include" / "aesw_perm.h").read_text()
     assert '#include "aesw_mult.h"' in header and "aesw_acc.h\"" not in header
 
 
 def test_a_missing_path_says_how_to_build_it(pkg, tmp_path):
-    missing = tmp_path / "nowhere" / pkg.api.PERM_LIB_PATH.name
-    with pytest.raises(FileNotFoundError) as e:
-        pkg.api.load_perm_library(missing)
-    assert str(missing) in str(e.value) and "There is no fallback implementation." in str(e.value)
+    cl.check_missing_path(pkg, "perm", tmp_path)
 
 
 def test_the_workspace_is_the_rule_headers(pkg):
@@ -70,19 +37,11 @@ def test_the_workspace_is_the_rule_headers(pkg):
 
 
 def test_the_other_libraries_are_left_alone(pkg):
-    for other in OTHERS:
-        text = cl.nm(getattr(pkg.api, other), "-C")
-        assert "aesw_perm" not in text and "perm_scan_kernel" not in text and "perm_expand_kernel" not in text, other
-    for header in sorted((cl.ROOT / "include").glob("*.h")):
-        if header.name != "aesw_perm.h":
-            assert "aesw_perm" not in header.read_text(), header.name
+    cl.check_others_left_alone(pkg, "perm", ("perm_scan_kernel", "perm_expand_kernel"))
 
 
 def test_a_group_refuses(pkg):
-    for name in ("permuted_columns", "gather_fr"):
-        with pytest.raises(pkg.AeswError) as e:
-            getattr(pkg.Group, name)(None)
-        assert e.value.status == pkg.api.ERR_INVALID_ARG
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_every_kernel_of_the_library_is_launched_and_the_list_names_nothing_else(pkg):

@@ -1,8 +1,8 @@
 """libaesw_vacc.so without a GPU: that build() makes it and what it is made of.
 
   * it exists after build(), exports exactly the aesw_vacc_ functions include/aesw_vacc.h declares, api.VACC_SYMBOLS binds exactly
-    those, its NEEDED entry is libaesw.so via $ORIGIN (and no other satellite is one), "vacc" is an entry of _build.SATELLITES with
-    "mult" still the last, and the Python face is there;
+    those, its NEEDED entry is libaesw.so via $ORIGIN (and no other library of the project is one),
+    and the Python face is there;
   * every __global__ in it is launched by the GPU sweep (tests/vacc_cases.py), and that list names nothing else;
   * its code object: no scratch, no VGPR spills, at most 256 unified registers, the counters and at most 160 KiB of static LDS, an
     LDS add per row step, the flushes and the report as global atomics; compared with the tracked table
@@ -10,11 +10,6 @@
     tests/test_vacc_library.py);
   * aesw_vacc_default_chunk is aesw_acc_default_chunk on the shapes of tests/test_acc_library.py;
   * the other libraries and their headers carry none of the new symbols, and the accumulator still refuses VALUES by name."""
-import importlib.util
-import subprocess
-
-import pytest
-
 import check_library as cl
 import vacc_cases as vc
 from isa_extract import needs_llvm
@@ -22,46 +17,18 @@ from isa_extract import needs_llvm
 TABLE = cl.ROOT / "profiles" / "isa_resources_vacc.json"
 code_object = cl.code_object_fixture("VACC_LIB_PATH")
 DECLARED = ["aesw_vacc_add_device", "aesw_vacc_add_device_chunk", "aesw_vacc_default_chunk", "aesw_vacc_prepare"]
-OTHERS = ("LIB_PATH", "CIRC_LIB_PATH", "COLS_LIB_PATH", "VALS_LIB_PATH", "ACC_LIB_PATH", "MULT_LIB_PATH", "HOST_LIB_PATH")
-
-
-def _build_module():
-    spec = importlib.util.spec_from_file_location("b", cl.ROOT / "halo2-aes_amd" / "_build.py")
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    return b
+METHODS = ("multiplicity_accumulator",)
 
 
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
-    api = pkg.api
-    lib = api.VACC_LIB_PATH
-    assert lib.name == "libaesw_vacc.so" and lib.parent == api.LIB_PATH.parent and lib.exists()
-    decl = cl.declared("aesw_vacc.h", "aesw_vacc_")
-    assert decl == DECLARED
-    exported = {line.split()[-1] for line in cl.nm(lib, "-D", "--defined-only").splitlines() if " T " in line}
-    assert sorted(f for f in exported if f.startswith("aesw_")) == decl, sorted(exported)[:20]
-    loaded = api.load_vacc_library()
-    assert api.load_vacc_library() is loaded
-    assert sorted(api.VACC_SYMBOLS) == decl and all(getattr(loaded, f) is not None for f in decl)
-    assert api._LIBRARIES["vacc"][:2] == (lib, api.VACC_SYMBOLS)
-    dyn = subprocess.run(["readelf", "-d", str(lib)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    assert "libaesw.so" in dyn and "$ORIGIN" in dyn, dyn
-    assert not [s for s in ("libaesw_acc", "libaesw_mult", "libaesw_vals", "libaesw_circ", "libaesw_cols", "libaesw_host") if s in dyn], dyn
-    assert (cl.ROOT / "halo2-aes_amd" / "csrc" / "vacc" / "aesw_vacc.hip").exists()  # one level below csrc/, as every satellite's
-    b = _build_module()
-    names = list(b.SATELLITES)
-    assert "vacc" in names and names[-1] == "mult" and names.index("vacc") == len(names) - 2 and b.VACC_LIB == lib
-    assert b.MULT_LIB.name == "libaesw_mult.so" and b.ACC_LIB.name == "libaesw_acc.so"  # the tuple below SATELLITES still names each its own
-    assert callable(api.MultiplicityAccumulator.add_values)
+    cl.check_exports(pkg, "vacc", DECLARED)
+    assert callable(pkg.api.MultiplicityAccumulator.add_values)
     header = (cl.ROOT / "include" / "aesw_vacc.h").read_text()
     assert '#include "aesw_mult.h"' in header and "aesw_acc.h\"" not in header and "aesw_vals.h\"" not in header
 
 
 def test_a_missing_path_says_how_to_build_it(pkg, tmp_path):
-    missing = tmp_path / "nowhere" / pkg.api.VACC_LIB_PATH.name
-    with pytest.raises(FileNotFoundError) as e:
-        pkg.api.load_vacc_library(missing)
-    assert str(missing) in str(e.value) and "There is no fallback implementation." in str(e.value)
+    cl.check_missing_path(pkg, "vacc", tmp_path)
 
 
 def test_an_accumulator_that_never_sees_values_does_not_load_the_library():
@@ -87,12 +54,7 @@ def test_the_default_chunk_is_the_accumulators(pkg):
 
 
 def test_the_other_libraries_are_left_alone(pkg):
-    for other in OTHERS:
-        text = cl.nm(getattr(pkg.api, other), "-C")
-        assert "aesw_vacc" not in text and "vacc_count_kernel" not in text, other
-    for header in sorted((cl.ROOT / "include").glob("*.h")):
-        if header.name != "aesw_vacc.h":
-            assert "aesw_vacc" not in header.read_text(), header.name
+    cl.check_others_left_alone(pkg, "vacc", ("vacc_count_kernel",))
     # every refusal of VALUES stays, by name
     acc = (cl.ROOT / "halo2-aes_amd" / "csrc" / "acc" / "aesw_acc.hip").read_text()
     rules = (cl.ROOT / "halo2-aes_amd" / "csrc" / "aesw_entry_rules.h").read_text()
@@ -101,9 +63,7 @@ def test_the_other_libraries_are_left_alone(pkg):
 
 
 def test_a_group_refuses(pkg):
-    with pytest.raises(pkg.AeswError) as e:
-        pkg.Group.multiplicity_accumulator(None, 12, 1)
-    assert e.value.status == pkg.api.ERR_INVALID_ARG
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_every_kernel_of_the_library_is_swept_and_the_list_names_nothing_else(pkg):

@@ -7,38 +7,30 @@
   * its code object: no scratch, no VGPR spills, at most 256 unified registers, compared with the tracked table
     profiles/isa_resources_vals.json.  Regenerate that table on purpose with
     AESW_UPDATE_ISA_JSON=1 python -m pytest tests/test_vals_check_library.py;
-  * the three other libraries and their headers carry none of the new symbols.
+  * the other libraries carry none of the new symbols; the one header that names the library is aesw_vacc.h, built over its rules.
 
 The checks every checker library gets are in tests/check_library.py."""
-import pytest
-
 import check_library as cl
 import vals_check_cases as vcs
 from isa_extract import needs_llvm
 
 TABLE = cl.ROOT / "profiles" / "isa_resources_vals.json"
 code_object = cl.code_object_fixture("VALS_LIB_PATH")
+METHODS = ("check_values",)
 
 
 def test_build_makes_the_library_and_it_exports_the_header(pkg):
     declared = cl.check_exports(pkg, "vals")
     assert {"aesw_vals_check_device", "aesw_vals_check_rows", "aesw_vals_check_table", "aesw_vals_image_bytes"} <= set(declared), declared
-    assert callable(pkg.Context.check_values)
 
 
 def test_the_other_libraries_are_left_alone(pkg):
-    for other in (pkg.api.LIB_PATH, pkg.api.CIRC_LIB_PATH, pkg.api.COLS_LIB_PATH):
-        text = cl.nm(other, "-C")
-        assert "vals_check_kernel" not in text and "aesw_vals" not in text, other
-    for header in ("aesw.h", "aesw_circ.h", "aesw_cols.h"):
-        text = (cl.ROOT / "include" / header).read_text()
-        assert "aesw_vals" not in text and "vals_check_kernel" not in text
+    cl.check_others_left_alone(pkg, "vals", ("vals_check_kernel",), named_by=("aesw_vacc.h",))
+    assert not [h.name for h in (cl.ROOT / "include").glob("*.h") if "vals_check_kernel" in h.read_text()]
 
 
 def test_a_group_refuses_the_values_check(pkg):
-    with pytest.raises(pkg.AeswError) as e:
-        pkg.Group.check_values(None, None, None, None, None)
-    assert e.value.status == pkg.api.ERR_INVALID_ARG
+    cl.check_group_refuses(pkg, METHODS)
 
 
 def test_every_kernel_of_the_library_is_swept_and_the_list_names_nothing_else(pkg):
