@@ -755,6 +755,55 @@ class ArenaWitness(Witness):
     freed by (Context.free_columns), so slicing or replacing a member tensor cannot orphan the arena."""
 
 
+# ---- marshalling of the prover-side tensor arguments: every rule once (DESIGN 4.27) -------------
+
+TABLE_FR_SHAPE = (3, K.TABLE_ROWS, 32)  # table_fr, what compress_table returns
+INV_FR_SHAPE = (2,) + TABLE_FR_SHAPE    # inv_fr, what invert_table returns
+
+
+def argument_shape(k: int, n_sets: int) -> tuple:
+    """(n_sets, 5, 2^k), a column of table-row indices for every lookup argument of a circuit; (0,) outside 0 <= k <= 30 and
+    1 <= n_sets <= 1024, where the library refuses the call and nothing may be sized by k."""
+    return (n_sets, 5, 1 << k) if 0 <= k <= 30 and 0 < n_sets <= 1024 else (0,)
+
+
+def check_tensor(t, name: str, device: int, dtype: str = "uint8", shape=None, min_bytes: int | None = None, nbytes: int | None = None, alt: str = ""):
+    """`t` as a library call takes it: a torch tensor of `dtype` ("uint8" or "int32") on cuda:`device`, else TypeError (`alt`
+    names what else the caller accepts); contiguous, else ValueError; and of `shape` -- a tuple whose first entry may be None, any
+    number of columns, or a list of such tuples --, of at least `min_bytes` or of exactly `nbytes`, where given, else ValueError."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != getattr(torch, dtype) or not t.is_cuda or t.device.index != device:
+        raise TypeError("%s must be a tensor of %s on cuda:%d%s" % (name, dtype, device, alt))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    if shape is not None and tuple(t.shape) != shape:
+        shapes, has = shape if isinstance(shape, list) else [shape], tuple(t.shape)
+        for s in shapes:
+            if has == s or (s[:1] == (None,) and len(has) == len(s) and has[1:] == s[1:]):
+                break
+        else:
+            raise ValueError("%s must have shape %s" % (name, " or ".join("[%s]" % ", ".join("n" if a is None else str(a) for a in s) for s in shapes)))
+    held = t.numel() * t.element_size() if min_bytes is not None or nbytes is not None else 0
+    if (min_bytes is not None and held < min_bytes) or (nbytes is not None and held != nbytes):
+        raise ValueError("%s must hold %s%d bytes" % (name, "at least " if nbytes is None else "", min_bytes if nbytes is None else nbytes))
+    return t
+
+
+def cells_of(value, name: str = "value") -> np.ndarray:
+    """The numpy half of Context._cells: an int (Python's or numpy's) or a sequence of ints becomes uint8 [n, 32], each reduced mod
+    r and put into Montgomery form (fr_cell); a numpy array must already be uint8 cells, [..., 32], and is returned as it is."""
+    if isinstance(value, (int, np.integer)):
+        value = [value]
+    if not isinstance(value, np.ndarray):
+        try:
+            value = np.array([fr_cell(v) for v in value], np.uint8).reshape(-1, 32)
+        except TypeError:  # no sequence, or not of ints: as before, under the argument's name
+            raise TypeError("%s must be ints, or uint8 cells of shape [n, 32]" % name) from None
+    if value.dtype != np.uint8 or value.shape[-1:] != (32,):
+        raise ValueError("%s must be ints, or uint8 cells of shape [n, 32]" % name)
+    return value
+
+
 class Context:
     """One aesw_ctx: a device plus the host's three byte tables."""
 
@@ -832,6 +881,52 @@ class Context:
         if not t.is_contiguous():
             raise ValueError("%s must be contiguous" % what)
         return t
+
+    # the prover-side arguments (lookup_multiplicities ... divide_columns): check_tensor on this context's device
+    def _tensor(self, t, name, dtype="uint8", shape=None, **size):
+        return check_tensor(t, name, self.device, dtype, shape, **size)
+
+    def _output(self, t, name, shape, dtype="uint8", **size):
+        """An output: None allocates `shape`; a tensor handed in must have that shape -- or the byte count of `size` instead."""
+        if t is None:
+            return self._torch().empty(shape, dtype=getattr(self._torch(), dtype), device=self._dev())
+        return check_tensor(t, name, self.device, dtype, None if size else shape, **size)
+
+    def _workspace(self, t, need: int):
+        """A workspace of `need` bytes: the caller's, or one that lives for the call."""
+        if t is None:
+            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
+            return self._torch().empty(max(need, 16), dtype=self._torch().uint8, device=self._dev())
+        return check_tensor(t, "_workspace", self.device, min_bytes=need)
+
+    def _index_words(self, t, name, shape):
+        """uint32 words the kernels index by (source, mapping): a numpy array is uploaded as int32, an int32 device tensor stays."""
+        if isinstance(t, np.ndarray):
+            t = self._torch().from_numpy(np.ascontiguousarray(t, np.uint32).view(np.int32)).to(self._dev())
+        return check_tensor(t, name, self.device, "int32", shape, alt=", or a numpy array")
+
+    def _columns(self, t, name, k):
+        """n_cols of `t`, a uint8 [n_cols, 2^k, 32] tensor of columns of cells (or [2^k, 32], one column)."""
+        check_tensor(t, name, self.device, shape=[(None, 1 << k, 32), (1 << k, 32)])
+        return t.shape[0] if t.dim() == 3 else 1
+
+    def _cells(self, value, name, one=False):
+        """Points (or v) as the calls of libaesw_open.so read them, a uint8 [n, 32] tensor of cells on the device: an int or a
+        sequence of ints (reduced mod r and put into Montgomery form) and a numpy uint8 [n, 32] array of cells (rotated_points) are
+        uploaded, a uint8 [n, 32] or [32] tensor stays and is read when the kernels run.  one: n must be 1."""
+        if not isinstance(value, self._torch().Tensor):
+            value = self._torch().from_numpy(np.ascontiguousarray(cells_of(value, name))).to(self._dev())
+        value = check_tensor(value, name, self.device, shape=[(None, 32), (32,)], alt=", or ints or numpy cells").view(-1, 32)
+        if one and value.shape[0] != 1:
+            raise ValueError("%s must be one int or one cell" % name)
+        return value
+
+    def _challenge(self, value, name):
+        """theta, beta or gamma as the calls that read a challenge take it: an int (Python's or numpy's; reduced mod r and put into
+        Montgomery form, one 32-byte upload per call) becomes its cell on the device, a uint8[32] tensor stays."""
+        if isinstance(value, (int, np.integer)):
+            value = self._torch().from_numpy(fr_cell(value)).to(self._dev())
+        return check_tensor(value, name, self.device, shape=(32,), alt=", or an int")
 
     def alloc_witness(self, n: int, layout: int = K.LAYOUT_PACKED, want_ct: bool = False, key_slab: bool = False,
                       n_keys: int | None = None):
@@ -1205,11 +1300,7 @@ class Context:
                 raise ValueError("witness holds fewer blocks than the counts sum to")
         nc, d_offs = self._circuit_args(k, n_sets, n, counts, None, _offsets)
         ks = self._key_slabs(key_witness, nc) if key_witness is not None else None
-        shape = (nc, n_sets, K.TABLE_ROWS)
-        if _out is None:
-            _out = torch.empty(shape, dtype=torch.int32, device=self._dev())
-        elif tuple(_out.shape) != shape or _out.dtype != torch.int32 or not _out.is_contiguous():
-            raise ValueError("_out must be a contiguous int32 tensor of shape %r" % (shape,))
+        _out = self._output(_out, "_out", (nc, n_sets, K.TABLE_ROWS), "int32")
         rep = torch.empty(3, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_mult_count_device_form(
             self._h, k, n_sets, nc, d_offs.data_ptr(), layout, witness.x.data_ptr(), witness.y.data_ptr(), witness.z.data_ptr(),
@@ -1229,20 +1320,11 @@ class Context:
         lib = load_perm_library()
         torch = self._torch()
         k, n_sets = int(k), int(n_sets)
-        if not isinstance(mult, torch.Tensor) or mult.dtype != torch.int32 or not mult.is_cuda or mult.device.index != self.device:
-            raise TypeError("mult must be an int32 tensor on cuda:%d" % self.device)
-        if tuple(mult.shape) == (1, n_sets, K.TABLE_ROWS):
+        if isinstance(mult, torch.Tensor) and tuple(mult.shape) == (1, n_sets, K.TABLE_ROWS):
             mult = mult[0]
-        if tuple(mult.shape) != (n_sets, K.TABLE_ROWS) or not mult.is_contiguous():
-            raise ValueError("mult must be a contiguous int32 tensor of shape %r" % ((n_sets, K.TABLE_ROWS),))
-        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 else (0,)
-        if _out is None:
-            _out = (torch.empty(shape, dtype=torch.int32, device=self._dev()), torch.empty(shape, dtype=torch.int32, device=self._dev()))
-        for t in _out:
-            if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
-                raise ValueError("_out must be two contiguous int32 tensors of shape %r" % (shape,))
-        # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
-        ws = torch.empty(max(int(lib.aesw_perm_workspace_bytes(n_sets)), 16), dtype=torch.uint8, device=self._dev())
+        mult = self._tensor(mult, "mult", "int32", (n_sets, K.TABLE_ROWS))
+        _out = [self._output(t, "_out", argument_shape(k, n_sets), "int32") for t in ((None, None) if _out is None else _out)]
+        ws = self._workspace(None, int(lib.aesw_perm_workspace_bytes(n_sets)))
         rep = torch.empty(3, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_perm_build_device(self._h, k, n_sets, (1 << k) if n_rows is None else int(n_rows), int(pad_row), mult.data_ptr(),
                                         _out[0].data_ptr(), _out[1].data_ptr(), ws.data_ptr(), rep.data_ptr(), self._stream())
@@ -1254,19 +1336,10 @@ class Context:
         (aesw_perm_gather_fr_device).  table_fr: uint8 [66561, 32], the host's compressed table; an index outside the table gives
         a cell of zeros."""
         lib = load_perm_library()
-        torch = self._torch()
-        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or not index.is_cuda or index.device.index != self.device:
-            raise TypeError("index must be an int32 tensor on cuda:%d" % self.device)
-        if not index.is_contiguous():
-            raise ValueError("index must be contiguous")
-        table_fr = self._u8(table_fr, "table_fr")
-        if tuple(table_fr.shape) != (K.TABLE_ROWS, 32):
-            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((K.TABLE_ROWS, 32),))
+        index = self._tensor(index, "index", "int32")
+        table_fr = self._tensor(table_fr, "table_fr", shape=TABLE_FR_SHAPE[1:])
         n = index.numel()
-        if out is None:
-            out = torch.empty(tuple(index.shape) + (32,), dtype=torch.uint8, device=self._dev())
-        elif self._u8(out, "out").numel() != n * 32:
-            raise ValueError("out must hold 32 bytes per index")
+        out = self._output(out, "out", tuple(index.shape) + (32,), nbytes=n * 32)
         rc = lib.aesw_perm_gather_fr_device(self._h, n, index.data_ptr(), table_fr.data_ptr(), out.data_ptr(), self._stream())
         self._check(rc, "aesw_perm_gather_fr_device")
         return out
@@ -1281,11 +1354,7 @@ class Context:
         lib = load_theta_library()
         torch = self._torch()
         theta = self._challenge(theta, "theta")
-        shape = (3, K.TABLE_ROWS, 32)
-        if _out is None:
-            _out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(_out, "_out").shape) != shape:
-            raise ValueError("_out must be a uint8 tensor of shape %r" % (shape,))
+        _out = self._output(_out, "_out", TABLE_FR_SHAPE)
         rep = torch.empty(2, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_theta_compress_table_device(self._h, theta.data_ptr(), _out.data_ptr(), rep.data_ptr(), self._stream())
         self._check(rc, "aesw_theta_compress_table_device")
@@ -1310,11 +1379,7 @@ class Context:
             if int(self._u8(t, "witness").numel()) < n_blocks * column_stride(layout, i):
                 raise ValueError("witness holds fewer than n_blocks blocks")
         ks = self._key_slabs(key_witness, 1) if key_witness is not None else None
-        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 and 0 < n_sets <= 1024 else (0,)
-        if _out is None:
-            _out = torch.empty(shape, dtype=torch.int32, device=self._dev())
-        elif tuple(_out.shape) != shape or _out.dtype != torch.int32 or not _out.is_contiguous():
-            raise ValueError("_out must be a contiguous int32 tensor of shape %r" % (shape,))
+        _out = self._output(_out, "_out", argument_shape(k, n_sets), "int32")
         if not torch.cuda.is_current_stream_capturing():  # the report's workspace: a capture needs it in place already
             self._check(lib.aesw_theta_prepare(self._h, k, n_sets, self._stream()), "aesw_theta_prepare")
         rep = torch.empty(3, dtype=torch.int64, device=self._dev())
@@ -1336,33 +1401,16 @@ class Context:
         index outside the table gives a cell of zeros -- or None for the table column in row order: row i for i < 66561, pad_row
         behind it.  table_fr: what compress_table returns."""
         lib = load_theta_library()
-        torch = self._torch()
         k, n_sets = int(k), int(n_sets)
-        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 and 0 < n_sets <= 1024 else (0,)
+        shape = argument_shape(k, n_sets)
         if index is not None:
-            if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or not index.is_cuda or index.device.index != self.device:
-                raise TypeError("index must be None or an int32 tensor on cuda:%d" % self.device)
-            if tuple(index.shape) != shape or not index.is_contiguous():
-                raise ValueError("index must be a contiguous int32 tensor of shape %r" % (shape,))
-        if tuple(self._u8(table_fr, "table_fr").shape) != (3, K.TABLE_ROWS, 32):
-            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((3, K.TABLE_ROWS, 32),))
-        if out is None:
-            out = torch.empty(shape + (32,), dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(out, "out").shape) != shape + (32,):
-            raise ValueError("out must be a uint8 tensor of shape %r" % (shape + (32,),))
+            self._tensor(index, "index", "int32", shape, alt=", or None")
+        self._tensor(table_fr, "table_fr", shape=TABLE_FR_SHAPE)
+        out = self._output(out, "out", shape + (32,))
         rc = lib.aesw_theta_columns_device(self._h, k, n_sets, (1 << k) if n_rows is None else int(n_rows), int(pad_row),
                                            None if index is None else index.data_ptr(), table_fr.data_ptr(), out.data_ptr(), self._stream())
         self._check(rc, "aesw_theta_columns_device")
         return out
-
-    def _challenge(self, value, name):
-        """theta, beta or gamma as the calls that read a challenge take it: an int (Python's or numpy's; reduced mod r and put into
-        Montgomery form, one 32-byte upload per call) becomes its cell on the device, a uint8[32] tensor stays."""
-        if isinstance(value, (int, np.integer)):
-            value = self._torch().from_numpy(fr_cell(value)).to(self._dev())
-        if tuple(self._u8(value, name).shape) != (32,):
-            raise ValueError("%s must be an int or a uint8[32] tensor" % name)
-        return value
 
     def invert_table(self, table_fr, beta, gamma, sync: bool = True, _out=None):
         """The inverse table of the lookup grand product (aesw_grand_invert_table_device, libaesw_grand.so): (inv_fr, report) with
@@ -1373,14 +1421,9 @@ class Context:
         canonical every cell is zero and the report says so.  _out is a tensor to write into (tests, tools)."""
         lib = load_grand_library()
         torch = self._torch()
-        if tuple(self._u8(table_fr, "table_fr").shape) != (3, K.TABLE_ROWS, 32):
-            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((3, K.TABLE_ROWS, 32),))
+        self._tensor(table_fr, "table_fr", shape=TABLE_FR_SHAPE)
         beta, gamma = self._challenge(beta, "beta"), self._challenge(gamma, "gamma")
-        shape = (2, 3, K.TABLE_ROWS, 32)
-        if _out is None:
-            _out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(_out, "_out").shape) != shape:
-            raise ValueError("_out must be a uint8 tensor of shape %r" % (shape,))
+        _out = self._output(_out, "_out", INV_FR_SHAPE)
         rep = torch.empty(3, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_grand_invert_table_device(self._h, table_fr.data_ptr(), beta.data_ptr(), gamma.data_ptr(), _out.data_ptr(), rep.data_ptr(),
                                                 self._stream())
@@ -1401,27 +1444,15 @@ class Context:
         lib = load_grand_library()
         torch = self._torch()
         k, n_sets = int(k), int(n_sets)
-        shape = (n_sets, 5, 1 << k) if 0 <= k <= 30 and 0 < n_sets <= 1024 else (0,)
+        shape = argument_shape(k, n_sets)
         for name, t in (("inputs", inputs), ("a", a), ("s", s)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.device.index != self.device:
-                raise TypeError("%s must be an int32 tensor on cuda:%d" % (name, self.device))
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous int32 tensor of shape %r" % (name, shape))
-        if tuple(self._u8(table_fr, "table_fr").shape) != (3, K.TABLE_ROWS, 32):
-            raise ValueError("table_fr must be a uint8 tensor of shape %r" % ((3, K.TABLE_ROWS, 32),))
-        if tuple(self._u8(inv_fr, "inv_fr").shape) != (2, 3, K.TABLE_ROWS, 32):
-            raise ValueError("inv_fr must be a uint8 tensor of shape %r" % ((2, 3, K.TABLE_ROWS, 32),))
+            self._tensor(t, name, "int32", shape)
+        self._tensor(table_fr, "table_fr", shape=TABLE_FR_SHAPE)
+        self._tensor(inv_fr, "inv_fr", shape=INV_FR_SHAPE)
         beta, gamma = self._challenge(beta, "beta"), self._challenge(gamma, "gamma")
-        if _out is None:
-            _out = (torch.empty(shape + (32,), dtype=torch.uint8, device=self._dev()), torch.empty(shape[:2] + (32,), dtype=torch.uint8, device=self._dev()))
-        if tuple(self._u8(_out[0], "_out").shape) != shape + (32,) or tuple(self._u8(_out[1], "_out").shape) != shape[:2] + (32,):
-            raise ValueError("_out must be uint8 tensors of shapes %r and %r" % (shape + (32,), shape[:2] + (32,)))
-        need = int(lib.aesw_grand_workspace_bytes(k, n_sets))
-        if _workspace is None:
-            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
-            _workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=self._dev())
-        elif self._u8(_workspace, "_workspace").numel() < need:
-            raise ValueError("_workspace must hold %d bytes" % need)
+        z, closing = (None, None) if _out is None else _out[:2]
+        _out = (self._output(z, "_out", shape + (32,)), self._output(closing, "_out", shape[:2] + (32,)))
+        _workspace = self._workspace(_workspace, int(lib.aesw_grand_workspace_bytes(k, n_sets)))
         rep = torch.empty(3, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_grand_product_device(self._h, k, n_sets, (1 << k) if n_rows is None else int(n_rows), int(pad_row), inputs.data_ptr(), a.data_ptr(),
                                            s.data_ptr(), table_fr.data_ptr(), inv_fr.data_ptr(), beta.data_ptr(), gamma.data_ptr(), _out[0].data_ptr(),
@@ -1433,13 +1464,9 @@ class Context:
         """The power tables of the permutation argument (aesw_sigma_tables_device, libaesw_sigma.so), challenge free, once per
         (k, n_cols): a uint8 [2^min(k, 14) + 2^max(k - 14, 0) + n_cols, 32] tensor -- omega^j, omega^(j * 2^14), delta^c."""
         lib = load_sigma_library()
-        torch = self._torch()
         k, n_cols = int(k), int(n_cols)
         need = int(lib.aesw_sigma_tables_bytes(k, n_cols)) if 0 <= k < 2 ** 32 and 0 <= n_cols < 2 ** 32 else 0
-        if _out is None:
-            _out = torch.empty((max(need, 32) // 32, 32), dtype=torch.uint8, device=self._dev())
-        elif self._u8(_out, "_out").numel() < need:
-            raise ValueError("_out must hold %d bytes" % need)
+        _out = self._output(_out, "_out", (max(need, 32) // 32, 32), min_bytes=need)
         rc = lib.aesw_sigma_tables_device(self._h, k, n_cols, _out.data_ptr(), self._stream())
         self._check(rc, "aesw_sigma_tables_device")
         return _out
@@ -1459,40 +1486,19 @@ class Context:
         torch = self._torch()
         k, n_cols, chunk_len = int(k), int(n_cols), int(chunk_len)
         rows = 1 << k if 0 <= k <= 28 else 0
-
-        def words(t, name, shape):
-            if isinstance(t, np.ndarray):
-                t = torch.from_numpy(np.ascontiguousarray(t, np.uint32).view(np.int32)).to(self._dev())
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.device.index != self.device:
-                raise TypeError("%s must be a numpy array or an int32 tensor on cuda:%d" % (name, self.device))
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s must be contiguous and of shape %r" % (name, shape))
-            return t
-        source, mapping = words(source, "source", (n_cols,)), words(mapping, "mapping", (n_cols, rows))
+        source, mapping = self._index_words(source, "source", (n_cols,)), self._index_words(mapping, "mapping", (n_cols, rows))
         n_advice = n_fixed = 0
         if advice_bytes is not None:
-            if self._u8(advice_bytes, "advice_bytes").dim() != 2 or advice_bytes.shape[1] != rows:
-                raise ValueError("advice_bytes must be a uint8 tensor of shape [n_advice, %d]" % rows)
-            n_advice = advice_bytes.shape[0]
+            n_advice = self._tensor(advice_bytes, "advice_bytes", shape=(None, rows)).shape[0]
         if fixed_bytes is not None:
-            if self._u8(fixed_bytes, "fixed_bytes").dim() != 2 or fixed_bytes.shape[1] != rows:
-                raise ValueError("fixed_bytes must be a uint8 tensor of shape [n_fixed, %d]" % rows)
-            n_fixed = fixed_bytes.shape[0]
-        need_tables = int(lib.aesw_sigma_tables_bytes(k, n_cols)) if k >= 0 and n_cols >= 0 else 0
-        if self._u8(tables, "tables").numel() < need_tables:
-            raise ValueError("tables must hold %d bytes" % need_tables)
+            n_fixed = self._tensor(fixed_bytes, "fixed_bytes", shape=(None, rows)).shape[0]
+        self._tensor(tables, "tables", min_bytes=int(lib.aesw_sigma_tables_bytes(k, n_cols)) if k >= 0 and n_cols >= 0 else 0)
         beta, gamma = self._challenge(beta, "beta"), self._challenge(gamma, "gamma")
         sets = -(-n_cols // chunk_len) if 1 <= chunk_len <= 8 and n_cols > 0 else 0
-        if _out is None:
-            _out = (torch.empty((sets, rows, 32), dtype=torch.uint8, device=self._dev()), torch.empty((sets, 32), dtype=torch.uint8, device=self._dev()))
-        if tuple(self._u8(_out[0], "_out").shape) != (sets, rows, 32) or tuple(self._u8(_out[1], "_out").shape) != (sets, 32):
-            raise ValueError("_out must be uint8 tensors of shapes %r and %r" % ((sets, rows, 32), (sets, 32)))
+        z, closing = (None, None) if _out is None else _out[:2]
+        _out = (self._output(z, "_out", (sets, rows, 32)), self._output(closing, "_out", (sets, 32)))
         need = int(lib.aesw_sigma_workspace_bytes(k, n_cols, chunk_len)) if k >= 0 and n_cols >= 0 and chunk_len >= 0 else 0
-        if _workspace is None:
-            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
-            _workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=self._dev())
-        elif self._u8(_workspace, "_workspace").numel() < need:
-            raise ValueError("_workspace must hold %d bytes" % need)
+        _workspace = self._workspace(_workspace, need)
         rep = torch.empty(6, dtype=torch.int64, device=self._dev())
         rc = lib.aesw_sigma_product_device(self._h, k, n_cols, chunk_len, rows if n_rows is None else int(n_rows),
                                            None if advice_bytes is None else advice_bytes.data_ptr(), n_advice,
@@ -1506,15 +1512,11 @@ class Context:
         """The twiddle tables of the transforms below (aesw_ntt_tables_device, libaesw_ntt.so), once per max_k (10 ... 28): a uint8
         [cells, 32] tensor that serves every transform of size up to 2^max_k."""
         lib = load_ntt_library()
-        torch = self._torch()
         max_k = int(max_k)
         need = int(lib.aesw_ntt_tables_bytes(max_k)) if 0 <= max_k < 2 ** 32 else 0
         if not need:
             raise AeswError(ERR_INVALID_ARG, "aesw_ntt_tables_device: max_k must be 10 ... 28")
-        if _out is None:
-            _out = torch.empty((need // 32, 32), dtype=torch.uint8, device=self._dev())
-        elif self._u8(_out, "_out").numel() != need:
-            raise ValueError("_out must hold %d bytes" % need)
+        _out = self._output(_out, "_out", (need // 32, 32), nbytes=need)
         rc = lib.aesw_ntt_tables_device(self._h, max_k, _out.data_ptr(), self._stream())
         self._check(rc, "aesw_ntt_tables_device")
         return _out
@@ -1525,27 +1527,18 @@ class Context:
         `tables` was built for (its size says which).  The workspace of a call in place is allocated here and handed back to the
         caching allocator in stream order; _workspace is a uint8 tensor to use instead (a capture)."""
         lib = load_ntt_library()
-        torch = self._torch()
         k_in, k_out = int(k_in), int(k_out)
         if not 10 <= k_in <= k_out <= 28:
             raise AeswError(ERR_INVALID_ARG, call + ": k (and ext_k, no smaller) must be 10 ... 28")
-        if self._u8(cells, "cells").dim() not in (2, 3) or tuple(cells.shape[-2:]) != (1 << k_in, 32):
-            raise ValueError("cells must be a uint8 tensor of shape [n_cols, %d, 32] or [%d, 32]" % (1 << k_in, 1 << k_in))
-        n_cols = cells.shape[0] if cells.dim() == 3 else 1
-        shape = tuple(cells.shape[:-2]) + (1 << k_out, 32)
-        max_k = next((m for m in range(k_out, 29) if int(lib.aesw_ntt_tables_bytes(m)) == self._u8(tables, "tables").numel()), None)
+        n_cols = self._columns(cells, "cells", k_in)
+        tables_bytes = self._tensor(tables, "tables").numel()
+        max_k = next((m for m in range(k_out, 29) if int(lib.aesw_ntt_tables_bytes(m)) == tables_bytes), None)
         if max_k is None:
             raise ValueError("tables must be what ntt_tables(max_k) returns for a max_k of at least %d" % k_out)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(out, "out").shape) != shape:
-            raise ValueError("out must be a uint8 tensor of shape %r" % (shape,))
+        out = self._output(out, "out", tuple(cells.shape[:-2]) + (1 << k_out, 32))
         need = int(lib.aesw_ntt_workspace_bytes(k_out, n_cols)) if out.data_ptr() == cells.data_ptr() else 0
-        if need and _workspace is None:
-            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
-            _workspace = torch.empty(need, dtype=torch.uint8, device=self._dev())
-        elif need and self._u8(_workspace, "_workspace").numel() < need:
-            raise ValueError("_workspace must hold %d bytes" % need)
+        if need:
+            _workspace = self._workspace(_workspace, need)
         rc = getattr(lib, call)(self._h, *[int(v) for v in leading], n_cols, cells.data_ptr(), out.data_ptr(), tables.data_ptr(), max_k,
                                 None if _workspace is None else _workspace.data_ptr(), self._stream())
         self._check(rc, call)
@@ -1577,24 +1570,13 @@ class Context:
         cell itself.  mapping: the [n_cols, 2^k] cell indices (permutation_mapping; a numpy array is uploaded, an int32 device
         tensor stays); sigma_tables: what permutation_tables returns for the same (k, n_cols)."""
         lib = load_quot_library()
-        torch = self._torch()
         k, n_cols = int(k), int(n_cols)
         need = int(load_sigma_library().aesw_sigma_tables_bytes(k, n_cols)) if 0 <= k < 2 ** 32 and 0 <= n_cols < 2 ** 32 else 0
         if not need:
             raise AeswError(ERR_INVALID_ARG, "aesw_quot_sigma_fr_device: k must be 10 ... 28, n_cols 1 ... 3074 and n_cols * 2^k at most 2^32")
-        if isinstance(mapping, np.ndarray):
-            mapping = torch.from_numpy(np.ascontiguousarray(mapping, np.uint32).view(np.int32)).to(self._dev())
-        if not isinstance(mapping, torch.Tensor) or mapping.dtype != torch.int32 or not mapping.is_cuda or mapping.device.index != self.device:
-            raise TypeError("mapping must be a numpy array or an int32 tensor on cuda:%d" % self.device)
-        if tuple(mapping.shape) != (n_cols, 1 << k) or not mapping.is_contiguous():
-            raise ValueError("mapping must be contiguous and of shape %r" % ((n_cols, 1 << k),))
-        if self._u8(sigma_tables, "sigma_tables").numel() < need:
-            raise ValueError("sigma_tables must hold %d bytes" % need)
-        shape = (n_cols, 1 << k, 32)
-        if _out is None:
-            _out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(_out, "_out").shape) != shape:
-            raise ValueError("_out must be a uint8 tensor of shape %r" % (shape,))
+        mapping = self._index_words(mapping, "mapping", (n_cols, 1 << k))
+        self._tensor(sigma_tables, "sigma_tables", min_bytes=need)
+        _out = self._output(_out, "_out", (n_cols, 1 << k, 32))
         rc = lib.aesw_quot_sigma_fr_device(self._h, k, n_cols, mapping.data_ptr(), sigma_tables.data_ptr(), _out.data_ptr(), self._stream())
         self._check(rc, "aesw_quot_sigma_fr_device")
         return _out
@@ -1604,35 +1586,10 @@ class Context:
         k = int(k)
         if not 10 <= k <= 28:
             raise AeswError(ERR_INVALID_ARG, call + ": k must be 10 ... 28")
-        if self._u8(coeff, "coeff").dim() not in (2, 3) or tuple(coeff.shape[-2:]) != (1 << k, 32):
-            raise ValueError("coeff must be a uint8 tensor of shape [n_cols, %d, 32] or [%d, 32]" % (1 << k, 1 << k))
-        return k, (coeff.shape[0] if coeff.dim() == 3 else 1)
-
-    def _open_cells(self, value, name):
-        """Points (or v) as the calls of libaesw_open.so read them, a uint8 [n, 32] tensor of cells on the device: an int or a
-        sequence of ints (reduced mod r and put into Montgomery form) and a numpy uint8 [n, 32] array of cells (rotated_points) are
-        uploaded, a uint8 [n, 32] or [32] tensor stays and is read when the kernels run."""
-        torch = self._torch()
-        if isinstance(value, (int, np.integer)):
-            value = [value]
-        if not isinstance(value, (torch.Tensor, np.ndarray)):
-            value = np.array([fr_cell(v) for v in value], np.uint8).reshape(-1, 32)
-        if isinstance(value, np.ndarray):
-            if value.dtype != np.uint8 or value.shape[-1:] != (32,):
-                raise ValueError("%s must be ints, or uint8 cells of shape [n, 32]" % name)
-            value = torch.from_numpy(np.ascontiguousarray(value)).to(self._dev())
-        if self._u8(value, name).dim() not in (1, 2) or value.shape[-1] != 32:
-            raise ValueError("%s must be ints, or uint8 cells of shape [n, 32]" % name)
-        return value.view(-1, 32)
+        return k, self._columns(coeff, "coeff", k)
 
     def _open_workspace(self, k, n_cols, n_points, _workspace):
-        need = int(load_open_library().aesw_open_workspace_bytes(k, n_cols, n_points)) if n_cols < 2 ** 32 else 0
-        if _workspace is None:
-            # freed on return, while the kernels may still run: the caching allocator hands it out again in stream order only
-            return self._torch().empty(max(need, 16), dtype=self._torch().uint8, device=self._dev())
-        if self._u8(_workspace, "_workspace").numel() < need:
-            raise ValueError("_workspace must hold %d bytes" % need)
-        return _workspace
+        return self._workspace(_workspace, int(load_open_library().aesw_open_workspace_bytes(k, n_cols, n_points)) if n_cols < 2 ** 32 else 0)
 
     def evaluate_columns(self, coeff, k: int, points, out=None, _workspace=None):
         """aesw_open_evaluate_device (libaesw_open.so): every coefficient column at every point, halo2's eval_polynomial -- a uint8
@@ -1642,15 +1599,10 @@ class Context:
         out: the tensor to write into; _workspace: a uint8 tensor to use instead of a fresh one (a capture)."""
         call = "aesw_open_evaluate_device"
         lib = load_open_library()
-        torch = self._torch()
         k, n_cols = self._open_columns(call, coeff, k)
-        points = self._open_cells(points, "points")
+        points = self._cells(points, "points")
         n_points = points.shape[0]
-        shape = tuple(coeff.shape[:-2]) + (n_points, 32)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(out, "out").shape) != shape:
-            raise ValueError("out must be a uint8 tensor of shape %r" % (shape,))
+        out = self._output(out, "out", tuple(coeff.shape[:-2]) + (n_points, 32))
         _workspace = self._open_workspace(k, n_cols, n_points, _workspace)
         rc = lib.aesw_open_evaluate_device(self._h, k, n_cols, n_points, coeff.data_ptr(), points.data_ptr(), out.data_ptr(), _workspace.data_ptr(), self._stream())
         self._check(rc, call)
@@ -1663,18 +1615,11 @@ class Context:
         uint8 [32] tensor on the device, read when the kernel runs.  The order is not pinned against halo2 (include/aesw_open.h)."""
         call = "aesw_open_fold_device"
         lib = load_open_library()
-        torch = self._torch()
         k, n_cols = self._open_columns(call, coeff, k)
-        v = self._open_cells(v, "v")
-        if v.shape[0] != 1:
-            raise ValueError("v must be one int or one cell")
-        shape = (1 << k, 32)
-        if acc is not None and tuple(self._u8(acc, "acc").shape) != shape:
-            raise ValueError("acc must be a uint8 tensor of shape %r" % (shape,))
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(out, "out").shape) != shape:
-            raise ValueError("out must be a uint8 tensor of shape %r" % (shape,))
+        v = self._cells(v, "v", one=True)
+        if acc is not None:
+            self._tensor(acc, "acc", shape=(1 << k, 32))
+        out = self._output(out, "out", (1 << k, 32))
         rc = lib.aesw_open_fold_device(self._h, k, n_cols, coeff.data_ptr(), v.data_ptr(), None if acc is None else acc.data_ptr(), out.data_ptr(), self._stream())
         self._check(rc, call)
         return out
@@ -1685,20 +1630,10 @@ class Context:
         one column), p_c(z).  point: one int or a uint8 [32] tensor on the device.  out=coeff divides in place."""
         call = "aesw_open_divide_device"
         lib = load_open_library()
-        torch = self._torch()
         k, n_cols = self._open_columns(call, coeff, k)
-        point = self._open_cells(point, "point")
-        if point.shape[0] != 1:
-            raise ValueError("point must be one int or one cell")
-        if out is None:
-            out = torch.empty_like(coeff)
-        elif tuple(self._u8(out, "out").shape) != tuple(coeff.shape):
-            raise ValueError("out must be a uint8 tensor of shape %r" % (tuple(coeff.shape),))
-        rem_shape = tuple(coeff.shape[:-2]) + (32,)
-        if _rem is None:
-            _rem = torch.empty(rem_shape, dtype=torch.uint8, device=self._dev())
-        elif tuple(self._u8(_rem, "_rem").shape) != rem_shape:
-            raise ValueError("_rem must be a uint8 tensor of shape %r" % (rem_shape,))
+        point = self._cells(point, "point", one=True)
+        out = self._output(out, "out", tuple(coeff.shape))
+        _rem = self._output(_rem, "_rem", tuple(coeff.shape[:-2]) + (32,))
         _workspace = self._open_workspace(k, n_cols, 1, _workspace)
         rc = lib.aesw_open_divide_device(self._h, k, n_cols, coeff.data_ptr(), point.data_ptr(), out.data_ptr(), _rem.data_ptr(), _workspace.data_ptr(), self._stream())
         self._check(rc, call)
@@ -1911,12 +1846,7 @@ class MultiplicityAccumulator:
         torch = ctx._torch()
         self._lib = load_acc_library()
         self.ctx, self.k, self.n_sets, self.layout = ctx, int(k), int(n_sets), int(layout)
-        shape = (self.n_sets, K.TABLE_ROWS)
-        if _out is None:
-            _out = torch.empty(shape, dtype=torch.int32, device=ctx._dev())
-        elif tuple(_out.shape) != shape or _out.dtype != torch.int32 or not _out.is_contiguous():
-            raise ValueError("_out must be a contiguous int32 tensor of shape %r" % (shape,))
-        self._mult = _out
+        self._mult = ctx._output(_out, "_out", (self.n_sets, K.TABLE_ROWS), "int32")
         self._rep = torch.empty(3, dtype=torch.int64, device=ctx._dev())
 
     def _stream(self, stream):
