@@ -153,10 +153,34 @@ def library_entry(name: str):
     return LIBRARIES[name]
 
 
+def _build_entry(name: str, entry, force: bool, extra_flags, out) -> Path:
+    """libaesw_<name>.so from an entry of LIBRARIES or of CURVE_LIBRARIES: one hipcc line, NEEDED libaesw.so found next to it ($ORIGIN)."""
+    sources, headers, public = entry
+    return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
+                  lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)
+
+
 def build_satellite(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
     """libaesw_<name>.so of an entry of LIBRARIES: its kernels and its entry points (hipcc, gfx950), NEEDED libaesw.so found next to it ($ORIGIN).
     A library of its own: the kernel sets of libaesw.so and of the other satellites stay what they are.  With `extra_flags` and
     another `out` (a file name next to libaesw.so) a measurement variant of it (tools/vacc_bench.py: -DAESW_VACC_WAVES=16)."""
-    sources, headers, public = library_entry(name)
-    return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
-                  lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)
+    return _build_entry(name, library_entry(name), force, extra_flags, out)
+
+
+# The libraries that compute on the curve, built after LIBRARIES and in the same way (an entry has the same shape): a table of
+# its own, because what they bring beyond Fr -- the base field aesw_fq.h, the group -- is theirs alone.
+#   msm    columns of Fr cells or of bytes committed against a basis of points of bn256's G1
+CURVE_LIBRARIES = {
+    "msm": ([CSRC / "msm" / "aesw_msm.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_fq.h", CSRC / "aesw_msm.h"], INCLUDE / "aesw_msm.h"),
+}
+
+
+def curve_library_names() -> list:
+    """Every library build_curve() builds, in the order of CURVE_LIBRARIES."""
+    return list(CURVE_LIBRARIES)
+
+
+def build_curve(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
+    """libaesw_<name>.so of an entry of CURVE_LIBRARIES, as build_satellite builds one of LIBRARIES.  With `extra_flags` and another
+    `out` a measurement variant of it (tools/msm_bench.py: -DAESW_MSM_CHUNK=1024)."""
+    return _build_entry(name, CURVE_LIBRARIES[name], force, extra_flags, out)

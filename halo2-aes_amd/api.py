@@ -32,6 +32,7 @@ SIGMA_LIB_PATH = _PKG / "libaesw_sigma.so"  # the grand products of the permutat
 NTT_LIB_PATH = _PKG / "libaesw_ntt.so"  # columns of Fr cells between Lagrange, coefficient and extended-coset form (include/aesw_ntt.h)
 QUOT_LIB_PATH = _PKG / "libaesw_quot.so"  # sigma of the permutation argument as Fr columns, for the quotient h(X) (include/aesw_quot.h)
 OPEN_LIB_PATH = _PKG / "libaesw_open.so"  # coefficient columns evaluated at points, folded under v and divided by (X - z) (include/aesw_open.h)
+MSM_LIB_PATH = _PKG / "libaesw_msm.so"  # columns of cells or bytes committed against a basis of points of bn256's G1 (include/aesw_msm.h)
 
 STATUS = {
     0: "AESW_OK", 1: "AESW_ERR_INVALID_ARG", 2: "AESW_ERR_NO_DEVICE", 3: "AESW_ERR_HIP", 4: "AESW_ERR_NOMEM",
@@ -287,7 +288,17 @@ OPEN_SYMBOLS = {
     "aesw_open_fold_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P]),
     "aesw_open_divide_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P]),
 }
+# include/aesw_msm.h
+MSM_SYMBOLS = {
+    "aesw_msm_chunk_rows": (_U32, []),
+    "aesw_msm_slices": (_U32, [_U32, _U32, _U32, _U32]),
+    "aesw_msm_workspace_bytes": (C.c_size_t, [_U32, _U32, _U32, _U32]),
+    "aesw_msm_basis_device": (_I, [_P, _U32, _P, _P, _P, _P]),
+    "aesw_msm_commit_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P]),
+}
+MSM_FR, MSM_BYTES = 0, 1  # AESW_MSM_FR, AESW_MSM_BYTES
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
+FQ_MODULUS = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47  # bn256's base field: the coordinates of G1
 
 _BUILD_IT = "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 _NO_FALLBACK = " (hipcc --offload-arch=gfx950). There is no fallback implementation."
@@ -310,6 +321,10 @@ _LIBRARIES = {
     "quot": (QUOT_LIB_PATH, QUOT_SYMBOLS, _NO_FALLBACK),
     "open": (OPEN_LIB_PATH, OPEN_SYMBOLS, _NO_FALLBACK),
 }
+# the libraries of _build.curve_library_names(), in its order: the same entry shape, consulted after _LIBRARIES
+_CURVE_LIBRARIES = {
+    "msm": (MSM_LIB_PATH, MSM_SYMBOLS, _NO_FALLBACK),
+}
 _loaded = {}  # name -> the CDLL of the default path
 
 
@@ -318,7 +333,7 @@ def _load(name: str, path) -> C.CDLL:
     loaded once; an explicit path is loaded anew and never cached.  A missing library is an error: there is no fallback."""
     if path is None and name in _loaded:
         return _loaded[name]
-    default, symbols, hint = _LIBRARIES[name]
+    default, symbols, hint = _LIBRARIES[name] if name in _LIBRARIES else _CURVE_LIBRARIES[name]
     if name == "aesw":
         # torch ships its own libamdhip64.so.7 and dlopen()s it by path.  Import it
         # FIRST so libaesw.so's NEEDED libamdhip64.so.7 binds to that copy: two HIP
@@ -423,6 +438,11 @@ def load_open_library(path: Path | None = None) -> C.CDLL:
     return _load("open", path)
 
 
+def load_msm_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_msm.so (in-tree): the commitments behind Context.msm_basis and Context.commit_columns."""
+    return _load("msm", path)
+
+
 def permutation_columns(n_sets: int) -> int:
     """aesw_sigma_columns: the columns of the permutation argument of a FixedAes128Config<k, n_sets> circuit, 3 * n_sets + 2."""
     return int(load_sigma_library().aesw_sigma_columns(int(n_sets)))
@@ -454,6 +474,24 @@ def permutation_mapping(k: int, n_sets: int, n_blocks: int) -> np.ndarray:
 def fr_cell(value: int) -> np.ndarray:
     """uint8[32]: the Fr cell of `value` (any int, reduced mod r) -- value * 2^256 mod r, little-endian."""
     return np.frombuffer(((int(value) % FR_MODULUS << 256) % FR_MODULUS).to_bytes(32, "little"), np.uint8).copy()
+
+
+def fq_cell(value: int) -> np.ndarray:
+    """uint8[32]: the Fq coordinate of `value` (any int, reduced mod q) -- value * 2^256 mod q, little-endian."""
+    return np.frombuffer(((int(value) % FQ_MODULUS << 256) % FQ_MODULUS).to_bytes(32, "little"), np.uint8).copy()
+
+
+def g1_from_cells(cells) -> list:
+    """The points of uint8 [..., 64] cells (what Context.commit_columns returns, copied to the host) as plain integers: (x, y) a
+    point, None for the identity, 64 zero bytes."""
+    unmont = pow(1 << 256, -1, FQ_MODULUS)
+    rows = np.ascontiguousarray(cells, np.uint8).reshape(-1, 64)
+    return [tuple(int.from_bytes(row[i:i + 32].tobytes(), "little") * unmont % FQ_MODULUS for i in (0, 32)) if row.any() else None for row in rows]
+
+
+def g1_generator() -> np.ndarray:
+    """uint8[64]: the generator (1, 2) of bn256's G1 as a point of a basis, x then y in Montgomery form."""
+    return np.concatenate([fq_cell(1), fq_cell(2)])
 
 
 def rotated_points(x: int, k: int, rotations) -> np.ndarray:
@@ -909,6 +947,17 @@ class Context:
         """n_cols of `t`, a uint8 [n_cols, 2^k, 32] tensor of columns of cells (or [2^k, 32], one column)."""
         check_tensor(t, name, self.device, shape=[(None, 1 << k, 32), (1 << k, 32)])
         return t.shape[0] if t.dim() == 3 else 1
+
+    def _points(self, t, name):
+        """Points as the calls of libaesw_msm.so read them, a uint8 [2^k, 64] tensor on the device, and k: a numpy array is uploaded,
+        a device tensor stays.  A row count that is no power of two in 2^10 ... 2^28 is refused."""
+        if isinstance(t, np.ndarray):
+            t = self._torch().from_numpy(np.ascontiguousarray(t, np.uint8)).to(self._dev())
+        check_tensor(t, name, self.device, shape=(None, 64), alt=", or a numpy array")
+        k = t.shape[0].bit_length() - 1
+        if t.shape[0] != 1 << k or not 10 <= k <= 28:
+            raise AeswError(ERR_INVALID_ARG, "%s must hold 2^k points, k = 10 ... 28" % name)
+        return t, k
 
     def _cells(self, value, name, one=False):
         """Points (or v) as the calls of libaesw_open.so read them, a uint8 [n, 32] tensor of cells on the device: an int or a
@@ -1639,6 +1688,44 @@ class Context:
         self._check(rc, call)
         return out, _rem
 
+    def msm_basis(self, points, out=None, _report=None):
+        """aesw_msm_basis_device (libaesw_msm.so): the basis a commitment is taken against -- a uint8 [2^k, 64] tensor of points in
+        Montgomery form -- from the plain little-endian coordinates a params file holds, uint8 [2^k, 64], x then y: a numpy array
+        or a tensor on the device.  Every point is checked (both coordinates below q, on the curve); a bad one raises AeswError
+        with their count and the index of the first.  out=points converts a device tensor in place.  Waits for the stream."""
+        call = "aesw_msm_basis_device"
+        lib = load_msm_library()
+        points, k = self._points(points, "points")
+        out = self._output(out, "out", (1 << k, 64))
+        _report = self._output(_report, "_report", (16,))
+        rc = lib.aesw_msm_basis_device(self._h, k, points.data_ptr(), out.data_ptr(), _report.data_ptr(), self._stream())
+        self._check(rc, call)
+        bad, first = self._report(_report, True, lambda rep: _words(rep.view(self._torch().int64)))
+        if bad:
+            raise AeswError(ERR_INVALID_ARG, "%s: %d of the 2^%d points are not on the curve or not below q, the first at index %d" % (call, bad, k, first))
+        return out
+
+    def commit_columns(self, scalars, basis, *, out=None, slices: int = 0, _workspace=None):
+        """aesw_msm_commit_device: the commitments of columns against a basis, C_j = sum_i scalars[j][i] * basis[i] over bn256's G1 --
+        a uint8 [n_cols, 64] tensor of affine points in Montgomery form, 64 zero bytes for the identity (g1_from_cells reads
+        them).  scalars: uint8 [n_cols, 2^k, 32], columns of Fr cells, or uint8 [n_cols, 2^k], columns of bytes (an assembled advice
+        column as it lies: one window of the method).  basis: uint8 [2^k, 64], what msm_basis returns.  slices: 0 for the
+        library's own count, else how many runs the rows are cut into -- the time changes, never the result.  out: the tensor to
+        write into; _workspace: a uint8 tensor to use instead of a fresh one (a capture)."""
+        call = "aesw_msm_commit_device"
+        lib = load_msm_library()
+        basis, k = self._points(basis, "basis")
+        self._tensor(scalars, "scalars", shape=[(None, 1 << k, 32), (None, 1 << k)])
+        kind, n_cols, slices = MSM_FR if scalars.dim() == 3 else MSM_BYTES, scalars.shape[0], int(slices)
+        need = int(lib.aesw_msm_workspace_bytes(k, n_cols, kind, slices)) if 0 <= slices < 2 ** 32 and 0 < n_cols < 2 ** 32 else 0
+        if not need:
+            raise AeswError(ERR_INVALID_ARG, call + ": n_cols must be 1 ... 65535 and slices 0 ... 2^k / 16, at most 65535")
+        out = self._output(out, "out", (n_cols, 64))
+        _workspace = self._workspace(_workspace, need)
+        rc = lib.aesw_msm_commit_device(self._h, k, n_cols, kind, slices, scalars.data_ptr(), basis.data_ptr(), out.data_ptr(), _workspace.data_ptr(), self._stream())
+        self._check(rc, call)
+        return out
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1969,7 +2056,8 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "lookup_multiplicities", "multiplicity_accumulator", "permuted_columns", "gather_fr",
               "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
               "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
-              "extended_to_coeff", "permutation_columns_fr", "evaluate_columns", "fold_columns", "divide_columns"):
+              "extended_to_coeff", "permutation_columns_fr", "evaluate_columns", "fold_columns", "divide_columns", "msm_basis",
+              "commit_columns"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
