@@ -82,7 +82,7 @@ def build_host(force: bool = False) -> Path:
 PRODUCT_SOURCES = [CSRC / n for n in ("aesw_kernels.hip", "aesw_api.cpp", "aesw_keyring.cpp", "aesw_hostpath.cpp", "aesw_arena.cpp",
                                       "aesw_comm.cpp", "aesw_group.cpp", "aesw_circuits.cpp")]
 PRODUCT_HEADERS = [CSRC / n for n in ("aesw_lane.h", "aesw_layout.h", "aesw_flush.h", "aesw_slabmap.h", "aesw_check.h", "aesw_check_dev.h", "aesw_internal.h", "aesw_ctx.h",
-                                      "aesw_keyring.h", "aesw_options.h", "aesw_placement.h", "aesw_align.h", "aesw_store.h", "aesw_report_dev.h", "aesw_fr.h")] + \
+                                      "aesw_keyring.h", "aesw_options.h", "aesw_placement.h", "aesw_align.h", "aesw_store.h", "aesw_report_dev.h", "aesw_fr.h", "aesw_mont.h")] + \
     [INCLUDE / "aesw.h"]
 
 
@@ -104,7 +104,7 @@ def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_so
 # every one of them may include: the context, the checker core, what an entry point says before it launches (aesw_entry.h;
 # aesw_entry_rules.h, whose bounds are aesw_mult.h's), the store flavour (aesw_store.h), the report's reset and fold
 # (aesw_report_dev.h), what a kernel of the libraries that compute in Fr does to a cell (aesw_fr_dev.h, over the aesw_fr.h each
-# of them lists).  A new library is one more entry here (DESIGN 4.26 lists what else it brings).
+# of them lists), the Montgomery arithmetic under every field (aesw_mont.h).  A new library is one more entry here (DESIGN 4.26 lists what else it brings).
 #   circ   checks the witnesses of many circuits in one launch
 #   cols   checks the assembled advice columns, as bytes or Fr cells
 #   vals   checks a VALUES witness
@@ -120,7 +120,7 @@ def build_product(force: bool = False, extra_flags=(), out: Path = LIB, extra_so
 #   open   coefficient columns evaluated at points, folded under v and divided by (X - z)
 SATELLITE_HEADERS = [CSRC / n for n in ("aesw_check_dev.h", "aesw_check.h", "aesw_layout.h", "aesw_slabmap.h", "aesw_internal.h", "aesw_ctx.h",
                                         "aesw_keyring.h", "aesw_options.h", "aesw_placement.h", "aesw_align.h", "aesw_entry.h", "aesw_entry_rules.h", "aesw_mult.h",
-                                        "aesw_store.h", "aesw_report_dev.h", "aesw_fr_dev.h")] + [INCLUDE / "aesw.h", INCLUDE / "aesw_mult.h"]
+                                        "aesw_store.h", "aesw_report_dev.h", "aesw_fr_dev.h", "aesw_mont.h")] + [INCLUDE / "aesw.h", INCLUDE / "aesw_mult.h"]
 LIBRARIES = {
     "circ": ([CSRC / "circ" / "aesw_circ_check.hip"], [CSRC / "aesw_circ_search.h"], INCLUDE / "aesw_circ.h"),
     "cols": ([CSRC / "cols" / "aesw_cols_check.hip"], [CSRC / "aesw_circ_search.h", CSRC / "aesw_fr.h"], INCLUDE / "aesw_cols.h"),

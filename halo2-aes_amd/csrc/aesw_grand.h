@@ -31,7 +31,7 @@ AESW_HD constexpr uint32_t grand_row_of_index(uint32_t x) { return x < MULT_BINS
 // product of the sums that are not zero, out(i, inverse) for every i -- the zero cell for a zero sum, which the running product
 // skips.  Returns how many sums were zero.  B products forwards, 2 B backwards, one inversion.
 template <int B, class Sum, class Out>
-AESW_FR_HD uint32_t grand_batch_invert(Sum &&sum, Out &&out) {
+AESW_MONT_HD uint32_t grand_batch_invert(Sum &&sum, Out &&out) {
     Fr before[B];  // before[i]: the product of the non-zero sums below i
     Fr acc = FR_ONE;
     fr_unrolled<B>([&](auto at) {
@@ -58,7 +58,7 @@ AESW_FR_HD uint32_t grand_batch_invert(Sum &&sum, Out &&out) {
 
 // What row i of an argument multiplies Z by: t_in, t_tab the table's cells at the input index and at theta_table_index(i, pad_row),
 // inv_a = inv(T[a[i]] + beta) and inv_s = inv(T[s[i]] + gamma) out of the inverse table.  Three products.
-AESW_FR_HD constexpr Fr grand_row(const Fr &t_in, const Fr &t_tab, const Fr &inv_a, const Fr &inv_s, const Fr &beta, const Fr &gamma) {
+AESW_MONT_HD constexpr Fr grand_row(const Fr &t_in, const Fr &t_tab, const Fr &inv_a, const Fr &inv_s, const Fr &beta, const Fr &gamma) {
     return fr_mul(fr_mul(fr_add(t_in, beta), fr_add(t_tab, gamma)), fr_mul(inv_a, inv_s));
 }
 

@@ -87,23 +87,23 @@ struct G1 {
 };
 static_assert(sizeof(G1Affine) == 64 && sizeof(G1) == 96, "an affine point is 64 bytes, an accumulator 96");
 
-AESW_FQ_HD constexpr G1 msm_identity() { return G1{FQ_ZERO, FQ_ONE, FQ_ZERO}; }
-AESW_FQ_HD constexpr bool msm_affine_is_identity(const G1Affine &p) { return fq_is_zero(p.x) && fq_is_zero(p.y); }
-AESW_FQ_HD constexpr G1 msm_select(bool take, const G1 &a, const G1 &b) {
+AESW_MONT_HD constexpr G1 msm_identity() { return G1{FQ_ZERO, FQ_ONE, FQ_ZERO}; }
+AESW_MONT_HD constexpr bool msm_affine_is_identity(const G1Affine &p) { return fq_is_zero(p.x) && fq_is_zero(p.y); }
+AESW_MONT_HD constexpr G1 msm_select(bool take, const G1 &a, const G1 &b) {
     return G1{fq_select(take, a.x, b.x), fq_select(take, a.y, b.y), fq_select(take, a.z, b.z)};
 }
-AESW_FQ_HD constexpr G1 msm_from_affine(const G1Affine &p) { return msm_select(msm_affine_is_identity(p), msm_identity(), G1{p.x, p.y, FQ_ONE}); }
+AESW_MONT_HD constexpr G1 msm_from_affine(const G1Affine &p) { return msm_select(msm_affine_is_identity(p), msm_identity(), G1{p.x, p.y, FQ_ONE}); }
 // y^2 == x^3 + 3, both in Montgomery form
-AESW_FQ_HD constexpr bool msm_on_curve(const G1Affine &p) { return fq_eq(fq_mul(p.y, p.y), fq_add(fq_mul(fq_mul(p.x, p.x), p.x), FQ_THREE)); }
+AESW_MONT_HD constexpr bool msm_on_curve(const G1Affine &p) { return fq_eq(fq_mul(p.y, p.y), fq_add(fq_mul(fq_mul(p.x, p.x), p.x), FQ_THREE)); }
 
 // 9 t = b3 t
-AESW_FQ_HD constexpr Fq msm_times_b3(const Fq &t) {
+AESW_MONT_HD constexpr Fq msm_times_b3(const Fq &t) {
     const Fq t2 = fq_add(t, t), t4 = fq_add(t2, t2), t8 = fq_add(t4, t4);
     return fq_add(t8, t);
 }
 
 // p + q, every pair (algorithm 7): twelve products
-AESW_FQ_HD constexpr G1 msm_add(const G1 &p, const G1 &q) {
+AESW_MONT_HD constexpr G1 msm_add(const G1 &p, const G1 &q) {
     Fq t0 = fq_mul(p.x, q.x), t1 = fq_mul(p.y, q.y), t2 = fq_mul(p.z, q.z);
     Fq t3 = fq_mul(fq_add(p.x, p.y), fq_add(q.x, q.y));
     t3 = fq_sub(t3, fq_add(t0, t1));
@@ -123,7 +123,7 @@ AESW_FQ_HD constexpr G1 msm_add(const G1 &p, const G1 &q) {
 }
 
 // p + q, q affine (algorithm 8): eleven products; the affine identity leaves p
-AESW_FQ_HD constexpr G1 msm_add_mixed(const G1 &p, const G1Affine &q) {
+AESW_MONT_HD constexpr G1 msm_add_mixed(const G1 &p, const G1Affine &q) {
     Fq t0 = fq_mul(p.x, q.x), t1 = fq_mul(p.y, q.y);
     Fq t3 = fq_mul(fq_add(q.x, q.y), fq_add(p.x, p.y));
     t3 = fq_sub(t3, fq_add(t0, t1));
@@ -141,7 +141,7 @@ AESW_FQ_HD constexpr G1 msm_add_mixed(const G1 &p, const G1Affine &q) {
 }
 
 // 2 p (algorithm 9): eight products (two of them squarings)
-AESW_FQ_HD constexpr G1 msm_double(const G1 &p) {
+AESW_MONT_HD constexpr G1 msm_double(const G1 &p) {
     Fq t0 = fq_mul(p.y, p.y);
     Fq z3 = fq_add(t0, t0);
     z3 = fq_add(z3, z3);
@@ -159,15 +159,14 @@ AESW_FQ_HD constexpr G1 msm_double(const G1 &p) {
 }
 
 // the affine form of p: one inversion; the identity comes out as x = y = 0 because fq_inv(0) is 0
-AESW_FQ_HD constexpr G1Affine msm_to_affine(const G1 &p) {
+AESW_MONT_HD constexpr G1Affine msm_to_affine(const G1 &p) {
     const Fq zi = fq_inv(p.z);
     return G1Affine{fq_mul(p.x, zi), fq_mul(p.y, zi)};
 }
 
 // ---- the scalars -----------------------------------------------------------------------------------------------------------------
-constexpr Fr FR_RAW_ONE = {{1, 0, 0, 0, 0, 0, 0, 0}};
 // the plain value of a Montgomery cell: one product
-AESW_FR_HD constexpr Fr msm_canonical_scalar(const Fr &cell) { return fr_mul(cell, FR_RAW_ONE); }
+AESW_MONT_HD constexpr Fr msm_canonical_scalar(const Fr &cell) { return fr_mul(cell, FR_RAW_ONE); }
 // limb i of a plain value holds the windows 4 i ... 4 i + 3, the lowest byte first
 
 // ---- the workspace: the digit planes (Fr scalars alone), the buckets, the window sums --------------------------------------------

@@ -81,12 +81,12 @@ static_assert(open_workspace_bytes(10, 1, 1) == 30 * 32 && open_workspace_bytes(
 // ---- the recurrence ----------------------------------------------------------------------------------------------------------
 
 // front + weight * behind: the value of a piece and the piece behind it, weight = z^len(front)
-AESW_FR_HD constexpr Fr open_join(const Fr &front, const Fr &weight, const Fr &behind) { return fr_add(front, fr_mul(weight, behind)); }
+AESW_MONT_HD constexpr Fr open_join(const Fr &front, const Fr &weight, const Fr &behind) { return fr_add(front, fr_mul(weight, behind)); }
 
 // The serial recurrence over n cells from the top, S_n = above: s(i, S_i) for i = n - 1 ... 0; returns S_0.  What the passes compute
 // piecewise, and what tests/open_driver.cpp holds them against.
 template <class Load, class Out>
-AESW_FR_HD Fr open_serial(uint64_t n, const Fr &z, const Fr &above, Load &&load, Out &&s) {
+AESW_MONT_HD Fr open_serial(uint64_t n, const Fr &z, const Fr &above, Load &&load, Out &&s) {
     Fr acc = above;
     for (uint64_t i = n; i-- > 0;) {
         acc = open_join(load(i), z, acc);
@@ -97,7 +97,7 @@ AESW_FR_HD Fr open_serial(uint64_t n, const Fr &z, const Fr &above, Load &&load,
 
 // A lane's cells c[0 ... 3] from the top by Horner: h[q] = S at the lane's cell q with nothing above the lane; h[0] is the value
 // of the lane's piece.  Three products.
-AESW_FR_HD void open_lane_horner(const Fr (&c)[OPEN_ROWS_PER_LANE], const Fr &z, Fr (&h)[OPEN_ROWS_PER_LANE]) {
+AESW_MONT_HD void open_lane_horner(const Fr (&c)[OPEN_ROWS_PER_LANE], const Fr &z, Fr (&h)[OPEN_ROWS_PER_LANE]) {
     h[OPEN_ROWS_PER_LANE - 1] = c[OPEN_ROWS_PER_LANE - 1];
     fr_unrolled<OPEN_ROWS_PER_LANE - 1>([&](auto at) {
         constexpr int q = OPEN_ROWS_PER_LANE - 2 - decltype(at)::value;
@@ -106,7 +106,7 @@ AESW_FR_HD void open_lane_horner(const Fr (&c)[OPEN_ROWS_PER_LANE], const Fr &z,
 }
 
 // The quotient's cells of a lane: above = S at the cell behind the lane's last; q[j] = S at the lane's cell j + 1.  Three products.
-AESW_FR_HD void open_lane_quotient(const Fr (&c)[OPEN_ROWS_PER_LANE], const Fr &z, const Fr &above, Fr (&q)[OPEN_ROWS_PER_LANE]) {
+AESW_MONT_HD void open_lane_quotient(const Fr (&c)[OPEN_ROWS_PER_LANE], const Fr &z, const Fr &above, Fr (&q)[OPEN_ROWS_PER_LANE]) {
     q[OPEN_ROWS_PER_LANE - 1] = above;
     fr_unrolled<OPEN_ROWS_PER_LANE - 1>([&](auto at) {
         constexpr int j = OPEN_ROWS_PER_LANE - 2 - decltype(at)::value;
@@ -117,7 +117,7 @@ AESW_FR_HD void open_lane_quotient(const Fr (&c)[OPEN_ROWS_PER_LANE], const Fr &
 // z^(unit * (64 - lane)) from the powers power(s) = z^(2^s), unit = 2^base: what multiplies the value above a wave in lane
 // `lane`, whose piece begins 64 - lane units below the wave's end.  64 - lane is 1 ... 64: seven bits, a product for every one.
 template <class Power>
-AESW_FR_HD Fr open_lane_weight(uint32_t base, uint32_t lane, Power &&power) {
+AESW_MONT_HD Fr open_lane_weight(uint32_t base, uint32_t lane, Power &&power) {
     const uint32_t e = OPEN_LANES - lane;
     Fr w = FR_ONE;
     AESW_OPEN_ROLLED
@@ -132,7 +132,7 @@ AESW_FR_HD Fr open_lane_weight(uint32_t base, uint32_t lane, Power &&power) {
 // `above` what lies above the last wave.  above_of(w, value) is told the value above wave w; returns the value of everything
 // from wave 0 up.  (Callables, not arrays: a kernel keeps the one value of its own wave.)
 template <int WAVES, class Total, class Above>
-AESW_FR_HD Fr open_join_waves(const Fr &weight, const Fr &above, Total &&total, Above &&above_of) {
+AESW_MONT_HD Fr open_join_waves(const Fr &weight, const Fr &above, Total &&total, Above &&above_of) {
     Fr acc = above;
     fr_unrolled<WAVES>([&](auto at) {
         constexpr int w = WAVES - 1 - decltype(at)::value;
@@ -145,6 +145,6 @@ AESW_FR_HD Fr open_join_waves(const Fr &weight, const Fr &above, Total &&total, 
 // ---- the fold of columns under v -----------------------------------------------------------------------------------------------
 // acc = acc * v + col, column after column: (...((acc * v + col_0) * v + col_1)...) * v + col_(n-1) -- the order of halo2 v0.3.0's
 // GWC prover as remembered, not pinned by a test.
-AESW_FR_HD constexpr Fr open_fold_step(const Fr &acc, const Fr &v, const Fr &col) { return fr_add(fr_mul(acc, v), col); }
+AESW_MONT_HD constexpr Fr open_fold_step(const Fr &acc, const Fr &v, const Fr &col) { return fr_add(fr_mul(acc, v), col); }
 
 }  // namespace aesw

@@ -147,7 +147,7 @@ AESW_QUOT_HD Fr quot_times_small(const Fr &a, uint32_t t) {
 }
 AESW_QUOT_HD Fr quot_pick(uint32_t arity, const Fr &two, const Fr &three, const Fr &four) {
     Fr out = FR_ZERO;
-    AESW_FR_UNROLL
+    AESW_MONT_UNROLL
     for (int i = 0; i < FR_LIMBS; ++i) out.l[i] = arity == 2 ? two.l[i] : arity == 3 ? three.l[i] : four.l[i];
     return out;
 }

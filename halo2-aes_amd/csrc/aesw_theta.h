@@ -41,7 +41,7 @@ AESW_HD constexpr ThetaTableRow theta_table_row(uint32_t r, const uint8_t *tab76
 
 // halo2's compression: acc = acc * theta + e over the first `arity` (2, 3 or 4) of the expressions tag, a, b, c, given as the
 // Montgomery forms of the four bytes; theta canonical.
-AESW_FR_HD constexpr Fr theta_compress(const Fr &theta, const Fr &tag, const Fr &a, const Fr &b, const Fr &c, uint32_t arity) {
+AESW_MONT_HD constexpr Fr theta_compress(const Fr &theta, const Fr &tag, const Fr &a, const Fr &b, const Fr &c, uint32_t arity) {
     Fr acc = fr_add(fr_mul(tag, theta), a);
     if (arity >= 3) acc = fr_add(fr_mul(acc, theta), b);
     if (arity >= 4) acc = fr_add(fr_mul(acc, theta), c);

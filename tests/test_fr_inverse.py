@@ -1,8 +1,9 @@
-"""csrc/aesw_fr.h's inverse without a GPU: fr_inv, fr_is_zero and fr_eq compiled alone with g++ behind tests/fr_inv_driver.cpp
-and held against tests/grand_model.py (pow(x, r - 2, r), 0 for 0) over the value set of tests/test_fr_header.py -- 0, 1, r - 1 and
-the Montgomery form of 1 among them, the operands whose limbs are all 0xffffffff below the top, 2 000 seeded random canonical
-values.  A cell holds v * 2^256 mod r, so the inverse CELL of a cell x is x^-1 * 2^512 mod r and fr_mul(fr_inv(x), x) is the cell
-of 1.  The same driver once more as a stand-alone program under AddressSanitizer and UBSan."""
+"""csrc/aesw_fr.h's inverse without a GPU: fr_inv, fr_is_zero and fr_eq (the core's, under Fr's names) compiled alone with g++
+behind tests/fr_inv_driver.cpp and held against tests/grand_model.py (pow(x, r - 2, r), 0 for 0) over Fr's value set of
+tests/test_field_headers.py -- 0, 1, r - 1 and the Montgomery form of 1 among them, the operands whose limbs are all 0xffffffff
+below the top, 2 000 seeded random canonical values.  A cell holds v * 2^256 mod r, so the inverse CELL of a cell x is
+x^-1 * 2^512 mod r and fr_mul(fr_inv(x), x) is the cell of 1.  The same driver once more as a stand-alone program under
+AddressSanitizer and UBSan."""
 import subprocess
 from pathlib import Path
 
@@ -10,7 +11,7 @@ import numpy as np
 import pytest
 
 import grand_model as gm
-import test_fr_header as fh
+import test_field_headers as fh
 
 ROOT = Path(__file__).resolve().parent.parent
 ONE = (1 << 256) % gm.R
@@ -48,12 +49,12 @@ def tmp(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def values():
-    rng = np.random.default_rng(0x6672)  # the values of tests/test_fr_header.py
-    return list(fh.SPECIAL) + [int.from_bytes(rng.bytes(40), "little") % gm.R for _ in range(2000)]
+    assert fh.FR.m == gm.R
+    return list(fh.FR.special) + fh.FR.random()  # the values of tests/test_field_headers.py
 
 
 def test_the_inverse_is_the_models_and_multiplies_back_to_one(tmp, values):
-    assert {0, 1, gm.R - 1, ONE} <= set(values) and len(values) == 2008
+    assert {0, 1, gm.R - 1, ONE} <= set(values) and len(values) == 2009
     check(build(tmp), tmp, values + list(fh.CARRIES))
 
 
@@ -68,4 +69,4 @@ def test_zero_inverts_to_zero_and_the_self_inverse_cells_are_one_and_minus_one(t
 
 def test_the_driver_runs_clean_under_address_and_ub_sanitizers(tmp, values):
     exe = build(tmp, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
-    check(exe, tmp, list(fh.SPECIAL) + list(fh.CARRIES) + values[8:72])
+    check(exe, tmp, list(fh.FR.special) + list(fh.CARRIES) + values[9:73])
