@@ -6,7 +6,9 @@
    device witness -- and MockProver checks lookups, the rcon gate and all copy constraints,
 3. the same circuit again from the values-only witness (1 056 B per block over PCIe instead of 3 024),
 4. the whole advice matrix as 32-byte bn256::Fr cells straight from the device (bulk column assignment),
-5. selectors and the fixed column for keygen, from pure-host geometry.
+5. selectors and the fixed column for keygen, from pure-host geometry,
+6. the advice columns committed on the device and theta derived from the commitments by the Blake2b transcript, with no host in
+   between: the challenge stays a device tensor and goes straight into the table compression.
 
 Run:  python examples/end_to_end.py [blocks]
 """
@@ -81,6 +83,21 @@ def main(n=3000, k=20, n_sets=4):
     # 5. keygen data
     sel, fixed = pkg.assemble_selectors(k, n_sets, n)
     print("5. selectors %s (enabled rows: %d), fixed column rcon rows: %d" % (sel.shape, int(sel.sum()), int((fixed != 0).sum())))
+
+    # 6. advice committed -> theta, on the device: the basis here is the generator at every row (a stand-in for a params file)
+    t0 = time.perf_counter()
+    g = np.zeros((1 << k, 64), np.uint8)
+    g[:, 0], g[:, 32] = 1, 2
+    basis = ctx.msm_basis(g)
+    commitments = ctx.commit_columns(cols, basis)
+    transcript = ctx.transcript(32 * commitments.shape[0])
+    theta = transcript.write_points(commitments).squeeze()  # a uint8 [32] device tensor: nothing was downloaded to make it
+    table_fr, rep = ctx.compress_table(theta)
+    assert not rep["noncanonical"] and tuple(table_fr.shape) == (3, pkg.TABLE_ROWS, 32)
+    # a column set no block fills is a column of zeros and commits to the identity (there are no blinding rows here): the
+    # transcript counts such points instead of refusing them as halo2 does
+    print("6. %d advice commitments -> transcript -> theta -> compressed table, all on the device: %.2f ms; proof so far: %d bytes, "
+          "%d commitments are the identity" % (commitments.shape[0], (time.perf_counter() - t0) * 1e3, len(transcript.proof()), transcript.status()["identities"]))
     print("ok")
 
 

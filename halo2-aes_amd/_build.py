@@ -3,7 +3,7 @@
   halo2-aes_amd/libaesw.so        HIP kernels + the C ABI of include/aesw.h (hipcc --offload-arch=gfx950)
   halo2-aes_amd/libaesw_host.so   the C++ mirror of the reference's host interface (include/aesw_host.h): plain g++,
                                   no device code, linked against libaesw.so -- it only calls the C ABI
-  halo2-aes_amd/libaesw_<name>.so one library per entry of LIBRARIES (the table below says what each is; its public header is
+  halo2-aes_amd/libaesw_<name>.so one library per entry of LIBRARIES, CURVE_LIBRARIES and PROOF_LIBRARIES (the tables below say what each is; its public header is
                                   include/aesw_<name>.h): its own gfx950 kernels and entry points (hipcc), linked against
                                   libaesw.so, whose context it takes.  All are built by build_satellite() alike.
 
@@ -154,7 +154,7 @@ def library_entry(name: str):
 
 
 def _build_entry(name: str, entry, force: bool, extra_flags, out) -> Path:
-    """libaesw_<name>.so from an entry of LIBRARIES or of CURVE_LIBRARIES: one hipcc line, NEEDED libaesw.so found next to it ($ORIGIN)."""
+    """libaesw_<name>.so from an entry of LIBRARIES, of CURVE_LIBRARIES or of PROOF_LIBRARIES: one hipcc line, NEEDED libaesw.so found next to it ($ORIGIN)."""
     sources, headers, public = entry
     return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
                   lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)
@@ -184,3 +184,21 @@ def build_curve(name: str, force: bool = False, extra_flags=(), out: Path | None
     """libaesw_<name>.so of an entry of CURVE_LIBRARIES, as build_satellite builds one of LIBRARIES.  With `extra_flags` and another
     `out` a measurement variant of it (tools/msm_bench.py: -DAESW_MSM_CHUNK=1024)."""
     return _build_entry(name, CURVE_LIBRARIES[name], force, extra_flags, out)
+
+
+# The libraries that turn what the others computed into a proof, built after CURVE_LIBRARIES and in the same way (an entry has the
+# same shape): a table of its own, because the first two are pinned at what they hold.
+#   transcript  the Blake2b transcript: commitments and scalars absorbed, challenges squeezed, proof bytes written
+PROOF_LIBRARIES = {
+    "transcript": ([CSRC / "transcript" / "aesw_transcript.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_fq.h", CSRC / "aesw_transcript.h"], INCLUDE / "aesw_transcript.h"),
+}
+
+
+def proof_library_names() -> list:
+    """Every library build_proof() builds, in the order of PROOF_LIBRARIES."""
+    return list(PROOF_LIBRARIES)
+
+
+def build_proof(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
+    """libaesw_<name>.so of an entry of PROOF_LIBRARIES, as build_satellite builds one of LIBRARIES."""
+    return _build_entry(name, PROOF_LIBRARIES[name], force, extra_flags, out)

@@ -33,6 +33,7 @@ NTT_LIB_PATH = _PKG / "libaesw_ntt.so"  # columns of Fr cells between Lagrange, 
 QUOT_LIB_PATH = _PKG / "libaesw_quot.so"  # sigma of the permutation argument as Fr columns, for the quotient h(X) (include/aesw_quot.h)
 OPEN_LIB_PATH = _PKG / "libaesw_open.so"  # coefficient columns evaluated at points, folded under v and divided by (X - z) (include/aesw_open.h)
 MSM_LIB_PATH = _PKG / "libaesw_msm.so"  # columns of cells or bytes committed against a basis of points of bn256's G1 (include/aesw_msm.h)
+TRANSCRIPT_LIB_PATH = _PKG / "libaesw_transcript.so"  # the Blake2b transcript: challenges from commitments, and the proof bytes (include/aesw_transcript.h)
 
 STATUS = {
     0: "AESW_OK", 1: "AESW_ERR_INVALID_ARG", 2: "AESW_ERR_NO_DEVICE", 3: "AESW_ERR_HIP", 4: "AESW_ERR_NOMEM",
@@ -297,6 +298,16 @@ MSM_SYMBOLS = {
     "aesw_msm_commit_device": (_I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P]),
 }
 MSM_FR, MSM_BYTES = 0, 1  # AESW_MSM_FR, AESW_MSM_BYTES
+# include/aesw_transcript.h
+TRANSCRIPT_SYMBOLS = {
+    "aesw_transcript_chunk_points": (_U32, []),
+    "aesw_transcript_chunk_scalars": (_U32, []),
+    "aesw_transcript_init_device": (_I, [_P, _P, _P]),
+    "aesw_transcript_points_device": (_I, [_P, _P, _U32, _P, _P, C.c_uint64, _P]),
+    "aesw_transcript_scalars_device": (_I, [_P, _P, _U32, _P, _P, C.c_uint64, _P]),
+    "aesw_transcript_squeeze_device": (_I, [_P, _P, _P, _P]),
+}
+TRANSCRIPT_STATE_BYTES = 256  # AESW_TRANSCRIPT_STATE_BYTES
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
 FQ_MODULUS = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47  # bn256's base field: the coordinates of G1
 
@@ -325,6 +336,10 @@ _LIBRARIES = {
 _CURVE_LIBRARIES = {
     "msm": (MSM_LIB_PATH, MSM_SYMBOLS, _NO_FALLBACK),
 }
+# the libraries of _build.proof_library_names(), in its order: the same entry shape, consulted after _CURVE_LIBRARIES
+_PROOF_LIBRARIES = {
+    "transcript": (TRANSCRIPT_LIB_PATH, TRANSCRIPT_SYMBOLS, _NO_FALLBACK),
+}
 _loaded = {}  # name -> the CDLL of the default path
 
 
@@ -333,7 +348,7 @@ def _load(name: str, path) -> C.CDLL:
     loaded once; an explicit path is loaded anew and never cached.  A missing library is an error: there is no fallback."""
     if path is None and name in _loaded:
         return _loaded[name]
-    default, symbols, hint = _LIBRARIES[name] if name in _LIBRARIES else _CURVE_LIBRARIES[name]
+    default, symbols, hint = _LIBRARIES[name] if name in _LIBRARIES else _CURVE_LIBRARIES[name] if name in _CURVE_LIBRARIES else _PROOF_LIBRARIES[name]
     if name == "aesw":
         # torch ships its own libamdhip64.so.7 and dlopen()s it by path.  Import it
         # FIRST so libaesw.so's NEEDED libamdhip64.so.7 binds to that copy: two HIP
@@ -441,6 +456,11 @@ def load_open_library(path: Path | None = None) -> C.CDLL:
 def load_msm_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_msm.so (in-tree): the commitments behind Context.msm_basis and Context.commit_columns."""
     return _load("msm", path)
+
+
+def load_transcript_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_transcript.so (in-tree): the Blake2b transcript behind Context.transcript."""
+    return _load("transcript", path)
 
 
 def permutation_columns(n_sets: int) -> int:
@@ -948,12 +968,17 @@ class Context:
         check_tensor(t, name, self.device, shape=[(None, 1 << k, 32), (1 << k, 32)])
         return t.shape[0] if t.dim() == 3 else 1
 
+    def _point_rows(self, t, name):
+        """Points as they lie in memory, a uint8 [n, 64] tensor on the device (what commit_columns returns): a numpy array is
+        uploaded, a device tensor stays."""
+        if isinstance(t, np.ndarray):
+            t = self._torch().from_numpy(np.ascontiguousarray(t, np.uint8)).to(self._dev())
+        return check_tensor(t, name, self.device, shape=(None, 64), alt=", or a numpy array")
+
     def _points(self, t, name):
         """Points as the calls of libaesw_msm.so read them, a uint8 [2^k, 64] tensor on the device, and k: a numpy array is uploaded,
         a device tensor stays.  A row count that is no power of two in 2^10 ... 2^28 is refused."""
-        if isinstance(t, np.ndarray):
-            t = self._torch().from_numpy(np.ascontiguousarray(t, np.uint8)).to(self._dev())
-        check_tensor(t, name, self.device, shape=(None, 64), alt=", or a numpy array")
+        t = self._point_rows(t, name)
         k = t.shape[0].bit_length() - 1
         if t.shape[0] != 1 << k or not 10 <= k <= 28:
             raise AeswError(ERR_INVALID_ARG, "%s must hold 2^k points, k = 10 ... 28" % name)
@@ -1726,6 +1751,14 @@ class Context:
         self._check(rc, call)
         return out
 
+    def transcript(self, proof_capacity: int = 0, _state=None, _proof=None) -> "Transcript":
+        """A fresh Blake2b transcript on the device (libaesw_transcript.so): commitments and scalars go in where they lie,
+        challenges come out as uint8 [32] device tensors that compress_table, invert_table, grand_product, permutation_product
+        and fold_columns take as they are, and the write_ forms append the proof's bytes to a device buffer of proof_capacity
+        bytes (0: none; the transcript then only derives challenges).  _state is a uint8 [256] tensor and _proof a uint8
+        [proof_capacity] tensor to use instead of fresh ones (tests, a capture)."""
+        return Transcript(self, proof_capacity, _state, _proof)
+
     def multiplicity_accumulator(self, k: int, n_sets: int, layout: int = K.LAYOUT_PACKED, _out=None) -> "MultiplicityAccumulator":
         """The lookup multiplicities of ONE FixedAes128Config<k, n_sets> circuit whose blocks arrive piece by piece
         (libaesw_acc.so): reset() once, then add() any contiguous run of the circuit's blocks, in any number of calls and in any
@@ -1925,6 +1958,79 @@ def group_shard(members: int, n: int, i: int):
     return int(first.value), int(count.value)
 
 
+def transcript_status_dict(rep) -> dict:
+    """The report words of a transcript's state (include/aesw_transcript.h, words 26 ... 29)."""
+    v = _words(rep)
+    return {"proof_bytes": v[26], "proof_missed": v[27], "identities": v[28], "first_identity": None if v[29] == _NONE else v[29]}
+
+
+class Transcript:
+    """What Context.transcript returns: halo2's Blake2bWrite<_, G1Affine, Challenge255<_>> on the device (include/aesw_transcript.h
+    states the rule; parity with halo2 itself is not pinned).  Every method but proof() and status() is asynchronous on the
+    current stream and allocates only the tensors it returns, so reset() ... squeeze(out=...) can be captured into one graph."""
+
+    def __init__(self, ctx: "Context", proof_capacity: int = 0, _state=None, _proof=None):
+        self._lib = load_transcript_library()
+        self.ctx, self.proof_capacity = ctx, int(proof_capacity)
+        self._state = ctx._output(_state, "_state", (TRANSCRIPT_STATE_BYTES,))
+        self._proof = ctx._output(_proof, "_proof", (self.proof_capacity,)) if self.proof_capacity > 0 else None
+        self.reset()
+
+    def reset(self):
+        """aesw_transcript_init_device: nothing absorbed, the proof's cursor at 0."""
+        self.ctx._check(self._lib.aesw_transcript_init_device(self.ctx._h, self._state.data_ptr(), self.ctx._stream()), "aesw_transcript_init_device")
+        return self
+
+    def _absorb(self, call, items, write):
+        if write and self._proof is None:
+            raise AeswError(ERR_INVALID_ARG, call + ": the transcript was made with proof_capacity=0 and has no proof to write to")
+        rc = getattr(self._lib, call)(self.ctx._h, self._state.data_ptr(), items.shape[0], items.data_ptr(), self._proof.data_ptr() if write else None,
+                                      self.proof_capacity if write else 0, self.ctx._stream())
+        self.ctx._check(rc, call)
+        return self
+
+    def common_points(self, points):
+        """common_point for every row of points, in order: a uint8 [n, 64] tensor of affine points in Montgomery form (what
+        commit_columns returns), or a numpy array of that shape, which is uploaded.  1 <= n <= 65535."""
+        return self._absorb("aesw_transcript_points_device", self.ctx._point_rows(points, "points"), False)
+
+    def write_points(self, points):
+        """write_point for every row of points: absorbed as common_points absorbs them, and 32 compressed bytes each appended to
+        the proof."""
+        return self._absorb("aesw_transcript_points_device", self.ctx._point_rows(points, "points"), True)
+
+    def common_scalars(self, cells):
+        """common_scalar for every cell, in order.  cells: ints, numpy cells or a uint8 [n, 32] (or [32]) tensor on the device."""
+        return self._absorb("aesw_transcript_scalars_device", self.ctx._cells(cells, "cells"), False)
+
+    def write_scalars(self, cells):
+        """write_scalar for every cell: absorbed, and its 32 plain little-endian bytes appended to the proof."""
+        return self._absorb("aesw_transcript_scalars_device", self.ctx._cells(cells, "cells"), True)
+
+    def squeeze(self, out=None):
+        """squeeze_challenge: a uint8 [32] device tensor holding the challenge as an Fr cell in Montgomery form, written when the
+        kernel runs.  out: the tensor to write into (a capture)."""
+        out = self.ctx._output(out, "out", (32,))
+        rc = self._lib.aesw_transcript_squeeze_device(self.ctx._h, self._state.data_ptr(), out.data_ptr(), self.ctx._stream())
+        self.ctx._check(rc, "aesw_transcript_squeeze_device")
+        return out
+
+    def status(self) -> dict:
+        """The state's report words after synchronising the stream: proof_bytes (produced so far, the cursor), proof_missed (of
+        those, the bytes that did not fit), identities (identity points seen) and first_identity (the index of the first among
+        the points absorbed, or None)."""
+        return self.ctx._report(self._state.view(self.ctx._torch().int64), True, transcript_status_dict)
+
+    def proof(self) -> bytes:
+        """The proof bytes produced so far, after synchronising the stream.  AeswError if any did not fit: the text names the
+        capacity the proof needs."""
+        st = self.status()
+        if st["proof_missed"]:
+            raise AeswError(ERR_CAPACITY, "Transcript.proof: %d of the %d proof bytes did not fit into proof_capacity=%d; the proof needs %d" % (
+                st["proof_missed"], st["proof_bytes"], self.proof_capacity, st["proof_bytes"]))
+        return self._proof[:st["proof_bytes"]].cpu().numpy().tobytes() if st["proof_bytes"] else b""
+
+
 class MultiplicityAccumulator:
     """What Context.multiplicity_accumulator returns.  Nothing here waits on the host or allocates after the constructor, so a
     reset() and its add()s can be captured into one graph; a replay of captured add()s adds again."""
@@ -2057,7 +2163,7 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
               "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
               "extended_to_coeff", "permutation_columns_fr", "evaluate_columns", "fold_columns", "divide_columns", "msm_basis",
-              "commit_columns"):
+              "commit_columns", "transcript"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
