@@ -3,7 +3,7 @@
   halo2-aes_amd/libaesw.so        HIP kernels + the C ABI of include/aesw.h (hipcc --offload-arch=gfx950)
   halo2-aes_amd/libaesw_host.so   the C++ mirror of the reference's host interface (include/aesw_host.h): plain g++,
                                   no device code, linked against libaesw.so -- it only calls the C ABI
-  halo2-aes_amd/libaesw_<name>.so one library per entry of LIBRARIES, CURVE_LIBRARIES and PROOF_LIBRARIES (the tables below say what each is; its public header is
+  halo2-aes_amd/libaesw_<name>.so one library per entry of LIBRARIES, CURVE_LIBRARIES, PROOF_LIBRARIES and MULTIOPEN_LIBRARIES (the tables below say what each is; its public header is
                                   include/aesw_<name>.h): its own gfx950 kernels and entry points (hipcc), linked against
                                   libaesw.so, whose context it takes.  All are built by build_satellite() alike.
 
@@ -154,7 +154,7 @@ def library_entry(name: str):
 
 
 def _build_entry(name: str, entry, force: bool, extra_flags, out) -> Path:
-    """libaesw_<name>.so from an entry of LIBRARIES, of CURVE_LIBRARIES or of PROOF_LIBRARIES: one hipcc line, NEEDED libaesw.so found next to it ($ORIGIN)."""
+    """libaesw_<name>.so from an entry of LIBRARIES, of CURVE_LIBRARIES, of PROOF_LIBRARIES or of MULTIOPEN_LIBRARIES: one hipcc line, NEEDED libaesw.so found next to it ($ORIGIN)."""
     sources, headers, public = entry
     return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
                   lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)
@@ -202,3 +202,22 @@ def proof_library_names() -> list:
 def build_proof(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
     """libaesw_<name>.so of an entry of PROOF_LIBRARIES, as build_satellite builds one of LIBRARIES."""
     return _build_entry(name, PROOF_LIBRARIES[name], force, extra_flags, out)
+
+
+# The libraries of the multi-opening argument, built after PROOF_LIBRARIES and in the same way (an entry has the same shape): a
+# table of its own, because the first three are pinned at what they hold.  (Not OPENING_LIBRARIES: tests/test_build_table.py holds
+# that name gone, with the six tables that became LIBRARIES.)
+#   shplonk  SHPLONK's two quotients h and W over every queried column: the sets' scalars, the combine, the quotient of a set
+MULTIOPEN_LIBRARIES = {
+    "shplonk": ([CSRC / "shplonk" / "aesw_shplonk.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_open.h", CSRC / "aesw_shplonk.h"], INCLUDE / "aesw_shplonk.h"),
+}
+
+
+def multiopen_library_names() -> list:
+    """Every library build_multiopen() builds, in the order of MULTIOPEN_LIBRARIES."""
+    return list(MULTIOPEN_LIBRARIES)
+
+
+def build_multiopen(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
+    """libaesw_<name>.so of an entry of MULTIOPEN_LIBRARIES, as build_satellite builds one of LIBRARIES."""
+    return _build_entry(name, MULTIOPEN_LIBRARIES[name], force, extra_flags, out)

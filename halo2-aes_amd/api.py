@@ -34,6 +34,7 @@ QUOT_LIB_PATH = _PKG / "libaesw_quot.so"  # sigma of the permutation argument as
 OPEN_LIB_PATH = _PKG / "libaesw_open.so"  # coefficient columns evaluated at points, folded under v and divided by (X - z) (include/aesw_open.h)
 MSM_LIB_PATH = _PKG / "libaesw_msm.so"  # columns of cells or bytes committed against a basis of points of bn256's G1 (include/aesw_msm.h)
 TRANSCRIPT_LIB_PATH = _PKG / "libaesw_transcript.so"  # the Blake2b transcript: challenges from commitments, and the proof bytes (include/aesw_transcript.h)
+SHPLONK_LIB_PATH = _PKG / "libaesw_shplonk.so"  # SHPLONK's two quotients over every queried column (include/aesw_shplonk.h)
 
 STATUS = {
     0: "AESW_OK", 1: "AESW_ERR_INVALID_ARG", 2: "AESW_ERR_NO_DEVICE", 3: "AESW_ERR_HIP", 4: "AESW_ERR_NOMEM",
@@ -308,6 +309,20 @@ TRANSCRIPT_SYMBOLS = {
     "aesw_transcript_squeeze_device": (_I, [_P, _P, _P, _P]),
 }
 TRANSCRIPT_STATE_BYTES = 256  # AESW_TRANSCRIPT_STATE_BYTES
+# include/aesw_shplonk.h
+SHPLONK_SYMBOLS = {
+    "aesw_shplonk_scalars_bytes": (C.c_size_t, [_U32, _U32]),
+    "aesw_shplonk_scalars_offset": (C.c_size_t, [_U32, _U32]),
+    "aesw_shplonk_workspace_bytes": (C.c_size_t, [_U32]),
+    "aesw_shplonk_report_bytes": (C.c_size_t, []),
+    "aesw_shplonk_prepare_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aesw_shplonk_finish_device": (_I, [_P, _P, _P, _P, _P, _P]),
+    "aesw_shplonk_combine_device": (_I, [_P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _P]),
+    "aesw_shplonk_quotient_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+# the tables of the scalars block (AESW_SHPLONK_PLAN ... AESW_SHPLONK_Y_POW), for shplonk_table
+SHPLONK_TABLES = ("plan", "v_pow", "ebar", "w", "vw", "neg_r", "z", "z_t", "z0_inv", "l_coef", "l_const", "l_low", "y_pow")
+SHPLONK_REPORT_LAST_REM = 32  # AESW_SHPLONK_REPORT_LAST_REM
 FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001  # the order of bn256's scalar field
 FQ_MODULUS = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47  # bn256's base field: the coordinates of G1
 
@@ -340,6 +355,10 @@ _CURVE_LIBRARIES = {
 _PROOF_LIBRARIES = {
     "transcript": (TRANSCRIPT_LIB_PATH, TRANSCRIPT_SYMBOLS, _NO_FALLBACK),
 }
+# the libraries of _build.multiopen_library_names(), in its order: the same entry shape, consulted after _PROOF_LIBRARIES
+_MULTIOPEN_LIBRARIES = {
+    "shplonk": (SHPLONK_LIB_PATH, SHPLONK_SYMBOLS, _NO_FALLBACK),
+}
 _loaded = {}  # name -> the CDLL of the default path
 
 
@@ -348,7 +367,7 @@ def _load(name: str, path) -> C.CDLL:
     loaded once; an explicit path is loaded anew and never cached.  A missing library is an error: there is no fallback."""
     if path is None and name in _loaded:
         return _loaded[name]
-    default, symbols, hint = _LIBRARIES[name] if name in _LIBRARIES else _CURVE_LIBRARIES[name] if name in _CURVE_LIBRARIES else _PROOF_LIBRARIES[name]
+    default, symbols, hint = next(table[name] for table in (_LIBRARIES, _CURVE_LIBRARIES, _PROOF_LIBRARIES, _MULTIOPEN_LIBRARIES) if name in table)
     if name == "aesw":
         # torch ships its own libamdhip64.so.7 and dlopen()s it by path.  Import it
         # FIRST so libaesw.so's NEEDED libamdhip64.so.7 binds to that copy: two HIP
@@ -461,6 +480,50 @@ def load_msm_library(path: Path | None = None) -> C.CDLL:
 def load_transcript_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_transcript.so (in-tree): the Blake2b transcript behind Context.transcript."""
     return _load("transcript", path)
+
+
+def load_shplonk_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_shplonk.so (in-tree): SHPLONK's multi-opening argument behind Context.shplonk_prepare, shplonk_finish,
+    combine_columns, set_quotient and open_shplonk."""
+    return _load("shplonk", path)
+
+
+class MultiopenPlan:
+    """What multiopen_plan returns: the static part of a multi-opening.  rotations: the super set, in order of first appearance.
+    sets: a list of (point indices, column ids) -- the indices strictly increasing into rotations, the columns in order of first
+    appearance.  set_points, set_cols and point_index are the three host arrays of aesw_shplonk_prepare_device; eval_order() is the
+    (column id, rotation) of every cell of d_evals: set by set, column by column, point by point."""
+
+    def __init__(self, rotations, sets):
+        self.rotations, self.sets = list(rotations), [(tuple(idx), list(cols)) for idx, cols in sets]
+        self.set_points = [len(idx) for idx, _cols in self.sets]
+        self.set_cols = [len(cols) for _idx, cols in self.sets]
+        self.point_index = [p for idx, _cols in self.sets for p in idx]
+
+    def eval_order(self) -> list:
+        return [(c, self.rotations[p]) for idx, cols in self.sets for c in cols for p in idx]
+
+
+def multiopen_plan(queries) -> MultiopenPlan:
+    """The plan of SHPLONK's multi-opening from (column id, rotation) queries, pure Python: the super set is the rotations in
+    order of first appearance; a column's point set is the indices of its rotations, ascending; columns with the same point set
+    form a set, the sets and the columns within one in order of first appearance.  halo2 orders the point sets by the value of
+    their points, which needs x; this order does not, and differs from halo2's."""
+    rotations, of_column = [], {}
+    for column, rotation in queries:
+        if rotation not in rotations:
+            rotations.append(rotation)
+        of_column.setdefault(column, set()).add(rotations.index(rotation))
+    sets = {}
+    for column, indices in of_column.items():  # a dict keeps the order of first appearance
+        sets.setdefault(tuple(sorted(indices)), []).append(column)
+    return MultiopenPlan(rotations, list(sets.items()))
+
+
+def shplonk_report_dict(rep) -> dict:
+    """The report words of include/aesw_shplonk.h; last_remainder: the four words of the last division's remainder, all 0 for 0."""
+    v = _words(rep)
+    return {"bad_sets": v[0], "first_bad_set": None if v[1] == _NONE else v[1], "zero_differences": v[2], "z0_zero": v[3], "last_remainder": v[4:8]}
 
 
 def permutation_columns(n_sets: int) -> int:
@@ -1751,6 +1814,120 @@ class Context:
         self._check(rc, call)
         return out
 
+    def shplonk_table(self, scalars, table: str, set: int = 0, cells: int = 1):
+        """The `cells` cells of `table` (a name of SHPLONK_TABLES) that belong to set `set` in the scalars block shplonk_prepare
+        returns, as a uint8 [cells, 32] view: aesw_shplonk_scalars_offset says where they lie."""
+        at = int(load_shplonk_library().aesw_shplonk_scalars_offset(SHPLONK_TABLES.index(table), int(set)))
+        if at == C.c_size_t(-1).value:
+            raise AeswError(ERR_INVALID_ARG, "shplonk_table: no set %d in table %s" % (set, table))
+        return self._tensor(scalars, "scalars", min_bytes=at + 32 * cells).view(-1)[at:at + 32 * cells].view(cells, 32)
+
+    def shplonk_prepare(self, plan, points, evals, y, v, _scalars=None, _report=None):
+        """aesw_shplonk_prepare_device (libaesw_shplonk.so): the small phase of SHPLONK's multi-opening after y and v -- (scalars,
+        report), a uint8 block that holds the plan and the tables y^j, v^i, e_is, w_is, v^i w_is and -R_i (shplonk_table reads
+        them) and an int64 [8] report, reset (shplonk_report_dict reads it).  plan: what multiopen_plan returns.  points: the
+        super set, len(plan.rotations) cells -- ints, the cells rotated_points returns, or a uint8 [n, 32] tensor on the device;
+        evals: the evaluations in plan.eval_order(), likewise; y, v: ints or uint8 [32] tensors on the device (what
+        Transcript.squeeze returns).  All are read when the kernel runs.  Parity with halo2 is not pinned (include/aesw_shplonk.h)."""
+        call = "aesw_shplonk_prepare_device"
+        lib = load_shplonk_library()
+        points = self._tensor(self._cells(points, "points"), "points", shape=(len(plan.rotations), 32))
+        evals = self._tensor(self._cells(evals, "evals"), "evals", shape=(len(plan.eval_order()), 32))
+        y, v = self._challenge(y, "y"), self._challenge(v, "v")
+        n_sets, max_cols = len(plan.sets), max(plan.set_cols, default=0)
+        need = int(lib.aesw_shplonk_scalars_bytes(n_sets, max_cols)) if n_sets < 2 ** 32 and max_cols < 2 ** 32 else 0
+        if not need:
+            raise AeswError(ERR_INVALID_ARG, call + ": a plan has 1 ... 16 sets of 1 ... 65535 columns")
+        _scalars = self._output(_scalars, "_scalars", (need,), min_bytes=need)
+        _report = self._output(_report, "_report", (8,), "int64")
+        words = [(C.c_uint32 * max(len(a), 1))(*a) for a in (plan.set_points, plan.set_cols, plan.point_index)]
+        rc = lib.aesw_shplonk_prepare_device(self._h, len(plan.rotations), n_sets, *words, points.data_ptr(), evals.data_ptr(), y.data_ptr(), v.data_ptr(),
+                                             _scalars.data_ptr(), _report.data_ptr(), self._stream())
+        self._check(rc, call)
+        return _scalars, _report
+
+    def shplonk_finish(self, points, u, scalars, report):
+        """aesw_shplonk_finish_device: the small phase after u -- z_i, z_T, z_0^-1, the coefficients of L' = z_0^-1 L, its constant
+        and its low cells written into the `scalars` shplonk_prepare returned; word 3 of `report` set.  Returns scalars."""
+        call = "aesw_shplonk_finish_device"
+        lib = load_shplonk_library()
+        points, u = self._cells(points, "points"), self._challenge(u, "u")
+        self._tensor(scalars, "scalars", min_bytes=int(lib.aesw_shplonk_scalars_bytes(1, 1)))
+        self._tensor(report, "report", "int64", (8,))
+        self._check(lib.aesw_shplonk_finish_device(self._h, points.data_ptr(), u.data_ptr(), scalars.data_ptr(), report.data_ptr(), self._stream()), call)
+        return scalars
+
+    def combine_columns(self, coeff, k: int, coefs, low=None, acc=None, out=None):
+        """aesw_shplonk_combine_device: a uint8 [2^k, 32] tensor, cell r = acc[r] + sum_j coefs[j] * coeff[j][r], plus low[r] for
+        r < len(low) <= 8.  coefs: one cell per column, low: the low cells or None -- ints, numpy cells or uint8 [n, 32] tensors on
+        the device (shplonk_table's views), read when the kernel runs; acc: a uint8 [2^k, 32] tensor, or None for zero; out=acc
+        adds into acc itself, so columns of separate tensors take successive calls."""
+        call = "aesw_shplonk_combine_device"
+        lib = load_shplonk_library()
+        k, n_cols = self._open_columns(call, coeff, k)
+        coefs = self._tensor(self._cells(coefs, "coefs"), "coefs", shape=(n_cols, 32))
+        low = None if low is None else self._cells(low, "low")
+        if acc is not None:
+            self._tensor(acc, "acc", shape=(1 << k, 32))
+        out = self._output(out, "out", (1 << k, 32))
+        rc = lib.aesw_shplonk_combine_device(self._h, k, n_cols, coeff.data_ptr(), coefs.data_ptr(), None if low is None else low.data_ptr(),
+                                             0 if low is None else low.shape[0], None if acc is None else acc.data_ptr(), out.data_ptr(), self._stream())
+        self._check(rc, call)
+        return out
+
+    def set_quotient(self, numer, k: int, set: int, points, scalars, report, acc=None, out=None, _rem=None, _workspace=None):
+        """aesw_shplonk_quotient_device: (out, rem) -- out a uint8 [2^k, 32] tensor, acc + v^i Q_i for set i = `set` of the plan in
+        `scalars`, Q_i the partial-fraction sum over the set's points of the quotients of numer = N_i (a uint8 [2^k, 32] tensor);
+        rem a uint8 [8, 32] tensor whose first t_i cells are N_i at the set's points.  out=acc accumulates h over the sets,
+        out=numer divides in place.  A remainder that is not 0 adds the set to `report`."""
+        call = "aesw_shplonk_quotient_device"
+        lib = load_shplonk_library()
+        k, _one = self._open_columns(call, numer, k)
+        self._tensor(numer, "numer", shape=(1 << k, 32))
+        points = self._cells(points, "points")
+        self._tensor(scalars, "scalars", min_bytes=int(lib.aesw_shplonk_scalars_bytes(1, 1)))
+        self._tensor(report, "report", "int64", (8,))
+        if acc is not None:
+            self._tensor(acc, "acc", shape=(1 << k, 32))
+        out = self._output(out, "out", (1 << k, 32))
+        _rem = self._output(_rem, "_rem", (8, 32))
+        _workspace = self._workspace(_workspace, int(lib.aesw_shplonk_workspace_bytes(k)))
+        rc = lib.aesw_shplonk_quotient_device(self._h, k, int(set), numer.data_ptr(), points.data_ptr(), scalars.data_ptr(), None if acc is None else acc.data_ptr(),
+                                              out.data_ptr(), _rem.data_ptr(), _workspace.data_ptr(), report.data_ptr(), self._stream())
+        self._check(rc, call)
+        return out, _rem
+
+    def open_shplonk(self, plan, columns, evals, points, transcript, basis, out=None, _report=None):
+        """SHPLONK's multi-opening, the whole stage on the current stream with no host wait: (points, report) -- a uint8 [2, 64]
+        tensor, the commitments [h] and [W] (what commit_columns returns), and the int64 [8] report (shplonk_report_dict reads it
+        after a synchronise).  Squeezes y and v from `transcript`, prepares, makes N_i (combine_columns) and adds v^i Q_i to h
+        (set_quotient) set by set, commits h, writes [h], squeezes u, finishes, combines L', divides it by (X - u) in place
+        (divide_columns, the remainder into the report), commits W and writes [W]: 64 more proof bytes.  plan: multiopen_plan's;
+        columns: one uint8 [m_i, 2^k, 32] tensor of coefficient columns per set, in the plan's order; evals and points as
+        shplonk_prepare takes them; basis: uint8 [2^k, 64], what msm_basis returns.  It allocates (S + 2) columns of its own."""
+        basis, k = self._points(basis, "basis")
+        n_sets = len(plan.sets)
+        if len(columns) != n_sets:
+            raise ValueError("columns must hold one tensor per set of the plan")
+        out = self._output(out, "out", (2, 64))
+        points = self._cells(points, "points")
+        y, v = transcript.squeeze(), transcript.squeeze()
+        scalars, report = self.shplonk_prepare(plan, points, evals, y, v, _report=_report)
+        work = self._output(None, "work", (n_sets + 1, 1 << k, 32))  # N_0 ... N_(S-1), then h
+        for i, cols in enumerate(columns):
+            self.combine_columns(cols, k, self.shplonk_table(scalars, "y_pow", cells=plan.set_cols[i]), low=self.shplonk_table(scalars, "neg_r", i, plan.set_points[i]),
+                                 out=work[i])
+            self.set_quotient(work[i], k, i, points, scalars, report, acc=work[n_sets] if i else None, out=work[n_sets])
+        self.commit_columns(work[n_sets:], basis, out=out[:1])
+        transcript.write_points(out[:1])
+        u = transcript.squeeze()
+        self.shplonk_finish(points, u, scalars, report)
+        line = self.combine_columns(work, k, self.shplonk_table(scalars, "l_coef", cells=n_sets + 1), low=self.shplonk_table(scalars, "l_low", cells=8))
+        self.divide_columns(line, k, u, out=line, _rem=report.view(self._torch().uint8)[SHPLONK_REPORT_LAST_REM:SHPLONK_REPORT_LAST_REM + 32])
+        self.commit_columns(line.view(1, 1 << k, 32), basis, out=out[1:])
+        transcript.write_points(out[1:])
+        return out, report
+
     def transcript(self, proof_capacity: int = 0, _state=None, _proof=None) -> "Transcript":
         """A fresh Blake2b transcript on the device (libaesw_transcript.so): commitments and scalars go in where they lie,
         challenges come out as uint8 [32] device tensors that compress_table, invert_table, grand_product, permutation_product
@@ -2163,7 +2340,7 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
               "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
               "extended_to_coeff", "permutation_columns_fr", "evaluate_columns", "fold_columns", "divide_columns", "msm_basis",
-              "commit_columns", "transcript"):
+              "commit_columns", "transcript", "shplonk_table", "shplonk_prepare", "shplonk_finish", "combine_columns", "set_quotient", "open_shplonk"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
