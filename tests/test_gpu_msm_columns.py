@@ -1,6 +1,7 @@
 """libaesw_msm.so on the GPU against tests/msm_model.py, every byte of every commitment, on poisoned, guard-banded buffers.
 
-k = 10 and 11, 1 and 3 columns, cells and bytes, slices 0 (the rule's), 1, 2 and 3 (an uneven last slice).  The columns of
+k = 10 and 11, 1 and 3 columns, cells and bytes, slices 0 (the rule's), 1, 2 and 3 (an uneven last slice); at k = 10 also 65 columns:
+the second workgroup of the combine kernel, its guard on the column, and a bucket grid 65 deep.  The columns of
 tests/msm_cases.py: seeded scalars, all 0 (the identity: 64 zero bytes), all 1, all r - 1 (bytes: all 255), all the same value
 (every row in one bucket per window), one non-zero row first and one last.  The basis has known logarithms, so an expectation is
 one scalar multiplication of the model.  A basis of one repeated point (a bucket adds P to P) and one alternating P, -P under
@@ -50,6 +51,28 @@ def test_every_column_is_the_model(pkg, ctx, bases, k, kind, n_cols, slices):
         for name, row in zip(names, got):
             G.assert_bytes("k=%d %s slices=%d column %s" % (k, mc.kind_name(kind), slices, name), row, mc.expected(kind, k, name))
     assert not mc.expected(kind, k, "zero").any()  # the identity is 64 zero bytes
+
+
+MANY_COLS = 65  # the combine kernel takes 64 columns a workgroup: a second one, of which one lane works
+WORKSPACE_LIMIT = 256 << 20
+
+
+@pytest.mark.parametrize("kind,slices", ((mc.BYTES, 3), (mc.FR, 0)), ids=("bytes-3", "fr-0"))
+def test_many_columns_reach_the_second_workgroup_of_the_combine(pkg, ctx, bases, kind, slices):
+    k = mc.KS[0]
+    need = int(pkg.api.load_msm_library().aesw_msm_workspace_bytes(k, MANY_COLS, kind, slices))
+    if need > WORKSPACE_LIMIT:
+        pytest.skip("the workspace of %d columns at k = %d is %d bytes, above %d" % (MANY_COLS, k, need, WORKSPACE_LIMIT))
+    named, n = mc.columns(kind, k), 1 << k
+    # the named columns first; from there on seeded ones, no two of them equal
+    later = lambda j: mm.seeded_scalars(n, 0x6d616e79 + j) if kind == mc.FR else [int(v) for v in np.random.default_rng(0x6d616e79 + j).integers(0, 256, n)]  # noqa: E731
+    cols = [named[sorted(named)[j % 7]] if j < 7 else later(j) for j in range(MANY_COLS)]
+    assert len({tuple(c) for c in cols[7:]}) == MANY_COLS - 7 and len(named) == 7
+    arena = G.DeviceArena(G.CANARIES[kind])
+    got = commit(pkg, ctx, arena, kind, k, np.stack([mc.scalar_bytes(kind, c) for c in cols]), bases[k], slices)  # commit checks the guards: the one behind out is whole
+    assert got.shape == (MANY_COLS, 64) and not (got[64] == arena.canary).all()  # out[64] is written
+    for j, c in enumerate(cols):
+        G.assert_bytes("k=%d %s slices=%d column %d of %d" % (k, mc.kind_name(kind), slices, j, MANY_COLS), got[j], mm.to_points([mm.known_commit(c)])[0])
 
 
 @pytest.mark.parametrize("kind", (mc.FR, mc.BYTES), ids=mc.kind_name)

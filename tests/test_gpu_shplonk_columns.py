@@ -55,11 +55,13 @@ def check_finished(ctx, p, o, scalars):
     assert table("l_coef", 1, S) == [fin["l_coef"][S]]
 
 
-def run_stage(pkg, ctx, k, canary, wrong=None, moved=None, in_place_numer=False):
-    """the stage call by call on guarded buffers; returns what the calls wrote.  moved: (points, evals) to take instead of the stage's"""
+def run_stage(pkg, ctx, k, canary, wrong=None, moved=None, in_place_numer=False, stage=None, u=None):
+    """the stage call by call on guarded buffers; returns what the calls wrote.  moved: (points, evals) to take instead of the stage's;
+    stage: a tuple of sc.stage's shape to take instead of sc.stage(k, wrong=wrong); u: the last challenge instead of the stage's"""
     api = pkg.api
     lib = api.load_shplonk_library()
-    p, pts, columns, evals, y, v, u = sc.stage(k, wrong=wrong)
+    p, pts, columns, evals, y, v, own_u = sc.stage(k, wrong=wrong) if stage is None else stage
+    u = own_u if u is None else u
     pts, evals = moved if moved is not None else (pts, evals)
     plan = api.MultiopenPlan(p.rotations, p.sets)
     S, n = len(p.sets), 1 << k
@@ -92,7 +94,7 @@ def run_stage(pkg, ctx, k, canary, wrong=None, moved=None, in_place_numer=False)
     work = put(arena, "work", np.concatenate([t.cpu().numpy() for t in numer] + [h.cpu().numpy()]).reshape(S + 1, n, 32))
     line = ctx.combine_columns(work, k, ctx.shplonk_table(scalars, "l_coef", cells=S + 1), low=ctx.shplonk_table(scalars, "l_low", cells=8), out=arena.out("line", 32 * n, (n, 32)))
     arena.check()
-    return dict(plan=p, arena=arena, after_prepare=after_prepare, scalars=scalars, report=report, numer=numer, rems=rems, h=h, line=line, points=d_points, ws=ws)
+    return dict(plan=p, arena=arena, after_prepare=after_prepare, scalars=scalars, report=report, numer=numer, rems=rems, h=h, line=line, points=d_points, ws=ws, work=work)
 
 
 def check_stage(pkg, ctx, o, got, k):

@@ -1,8 +1,10 @@
 """The op sequences of tests/transcript_cases.py on the GPU, through Context.transcript, against tests/transcript_model.py: every
 block fill over 128 one-scalar calls, calls of more than two chunks (aesw_transcript_chunk_points / _scalars say how many that is),
 squeezes at which the absorbed length is exactly one and two blocks -- the lazy last block -- each followed by a squeeze and by an
-absorb, a squeeze as the very first op, the kinds and the write / common forms mixed, a proof buffer that ends inside an item, the
-identity first, last and twice, and init on a dirty state.  The state, the proof and every challenge are views of a guarded,
+absorb, a squeeze as the very first op, the kinds and the write / common forms mixed, a proof buffer that ends inside an item
+(between two sixteen-byte pieces and inside one), the identity first, last and twice, and init on a dirty state; calls of a chunk
+and one item entered at every fill, a full block in front of the longest stream, calls of whole chunks, identities on both sides of a
+chunk boundary, and points of which one coordinate alone is zero.  The state, the proof and every challenge are views of a guarded,
 poisoned arena (tests/guarded.py); after every squeeze the challenge and the proof so far are the model's, byte for byte."""
 import numpy as np
 import pytest
@@ -69,17 +71,23 @@ def test_a_sequence_of_ops_gives_the_models_challenges_proof_and_report(pkg, ctx
 
 def test_the_overflow_counts_what_did_not_fit_and_changes_no_challenge(pkg, ctx):
     cases = _cases(pkg)
-    cut, room = cases["overflow"], cases["overflow_with_room"]
-    model, t, proof, capacity = run_case(pkg, ctx, cut, G.CANARIES[0])  # the guard band behind the short buffer is whole: run_case checks it
-    assert capacity == cut.capacity and t.status()["proof_missed"] == len(model.proof) - capacity > tm.PROOF_ITEM
-    assert proof.cpu().numpy().tobytes() == model.proof[:capacity]
-    _model, t_room, _proof, _capacity = run_case(pkg, ctx, room, G.CANARIES[1])  # the same challenges: both runs are held to one model
+    room = cases["overflow_with_room"]
+    # the buffer ends between two sixteen-byte pieces, then inside one: 1 and 15 bytes of room in either piece of the third item
+    for i, name in enumerate(["overflow"] + ["overflow_at_%d" % c for c in tc.CUT_INSIDE_A_PIECE]):
+        cut = cases[name]
+        assert cut.ops == room.ops
+        model, t, proof, capacity = run_case(pkg, ctx, cut, G.CANARIES[i % 2])  # the guard band behind the short buffer is whole: run_case checks it
+        assert capacity == cut.capacity and t.status()["proof_missed"] == len(model.proof) - capacity > tm.PROOF_ITEM, name
+        assert proof.cpu().numpy().tobytes() == model.proof[:capacity], name
+    _model, t_room, _proof, _capacity = run_case(pkg, ctx, room, G.CANARIES[1])  # the same challenges: every run is held to one model
     assert t_room.proof() == model.proof and t_room.status()["proof_missed"] == 0
 
 
 def test_the_identity_is_counted_named_and_written_as_zeros(pkg, ctx):
     cases = _cases(pkg)
-    for name, first, count in (("identity_first", 0, 1), ("identity_last", 6, 1), ("identity_twice", 2, 3)):
+    chunk = int(pkg.api.load_transcript_library().aesw_transcript_chunk_points())
+    for name, first, count in (("identity_first", 0, 1), ("identity_last", 6, 1), ("identity_twice", 2, 3), ("identity_across_chunks", 2 + chunk - 1, 3),
+                               ("identity_in_the_second_chunk", 2 + 2 * chunk - 1, 2), ("half_identities", 5, 1)):
         model, t, _proof, _capacity = run_case(pkg, ctx, cases[name], G.CANARIES[0])
         st = t.status()
         assert (st["first_identity"], st["identities"]) == (first, count) == (model.first_identity, model.identities), name

@@ -91,6 +91,7 @@ def test_every_kernel_of_the_library_is_launched_and_the_list_names_nothing_else
     cl.check_swept(pkg.api.SHPLONK_LIB_PATH, sc.launched())
     assert len(sc.launched()) == 12
     for name, words in (("test_gpu_shplonk_columns.py", ("sc.KS", "sc.STORE_MODES", "sc.stage", "shplonk_prepare", "shplonk_finish", "combine_columns", "set_quotient")),
+                        ("test_gpu_shplonk_extents.py", ("sc.full_stage", "sc.u_on_a_point", "sc.degenerate_stages", "sc.WIDE_COLS", "run_stage", "check_stage")),
                         ("test_gpu_shplonk_reach.py", ("sc.REACH_K",)), ("test_gpu_shplonk_chain.py", ("sc.CHAIN_ROTATIONS", "open_shplonk"))):
         src = (cl.ROOT / "tests" / name).read_text()
         assert all(w in src for w in words), name

@@ -8,7 +8,8 @@ csrc/aesw_shplonk.h -- the plan, the scalars block, the report, what a thread of
 compute -- is compiled alone with g++ into tests/shplonk_driver.cpp, which runs the kernels of shplonk/aesw_shplonk.hip on the CPU
 through those functions and is held against the model cell for cell at k = 10 (one chunk) and k = 11 (the carry is crossed), with
 t = 1, 2, 3 and 8, m = 1 and 5, at the points 0, 1, omega_k, r - 1 and seeded ones, once plain and once under
--fsanitize=address,undefined; at k = 19 (the carry's second turn) the driver holds the passes against the header's serial recurrence.
+-fsanitize=address,undefined, and at k = 10 over sc.FULL_SETS, the 16 sets over 16 points the kernels are written for, with u
+on a super-set point and with y, v and u at 0 and 1; at k = 19 (the carry's second turn) the driver holds the passes against the header's serial recurrence.
 multiopen_plan is pure Python and is held here too."""
 import struct
 import subprocess
@@ -203,11 +204,11 @@ def held(raw, k, p, o, cells_at):
 
 
 @pytest.mark.parametrize("build", sorted(FLAGS))
-@pytest.mark.parametrize("k", sc.KS)
+@pytest.mark.parametrize("k", sc.KS + ("full",))
 def test_the_cpu_run_of_the_kernels_is_the_model(drivers, build, k):
     d = drivers.dir
     cells_at = [int(v) for v in drivers("constants")[0].split()][:13]
-    stage = sc.stage(k)
+    stage, k = (sc.full_stage(), sc.FULL_K) if k == "full" else (sc.stage(k), k)  # full: sc.FULL_SETS, 16 sets over 16 points, up to 257 columns
     p, pts, columns, evals, y, v, u = stage
     write_stage(d, stage)
     drivers("stage", k, d / "plan.txt", d / "cells.bin", d / "out.bin", build=build)
@@ -235,6 +236,65 @@ def test_a_wrong_evaluation_and_two_equal_points_on_the_cpu(drivers):
     o = sm.opening(p, columns, evals, pts, y, v, lambda _h: u)
     assert o["report"]["zero_differences"] == 2
     held(np.fromfile(d / "out.bin", np.uint8), k, p, o, cells_at)
+
+
+def test_the_full_plan_is_what_it_says():
+    p, pts, _columns, _evals, _y, _v, _u = sc.full_stage()
+    assert len(set(pts)) == len(pts) == 16 == len(p.sets) == len(p.rotations) and pts[:4] == [0, 1, nm.omega(sc.FULL_K), R - 1]
+    assert sorted(set(p.set_points)) == list(range(1, 9)) and {q for idx, _cols in p.sets for q in idx} == set(range(16))
+    assert p.sets[15][0] == tuple(range(8, 16)) and p.set_points[0] == 2 and all(list(idx) == sorted(set(idx)) for idx, _cols in p.sets)
+    assert sorted((t, m) for t, m in zip(p.set_points, p.set_cols) if m != 1) == [(1, sc.WIDE_COLS), (8, 3)] and p.set_cols[sc.WIDE_SET] == sc.WIDE_COLS == 257
+
+
+def opened(stage):
+    p, pts, columns, evals, y, v, u = stage
+    return sm.opening(p, columns, evals, pts, y, v, lambda _h: u)
+
+
+def test_what_u_on_a_point_and_challenges_of_0_and_1_do_to_the_model():
+    on_a_point = sc.u_on_a_point()
+    p, pts, _columns, _evals, _y, _v, u = on_a_point["u_outside_set_0"]
+    o = opened(on_a_point["u_outside_set_0"])
+    fin = o["fin"]
+    assert pts.index(u) not in p.sets[0][0] and fin["z"][0] == 0 and fin["z_t"] == 0 and o["report"]["z0_zero"] == 1
+    # fr_inv(0) = 0: every coefficient of L' is zero, and L' with them
+    assert fin["z0_inv"] == 0 and fin["l_coef"] == [0] * 17 and fin["l_const"] == 0 and fin["l_low"] == [0] * 8 and not any(o["line"]) and any(fin["z"])
+    p, pts, _columns, _evals, _y, _v, u = on_a_point["u_inside_set_0"]
+    o = opened(on_a_point["u_inside_set_0"])
+    fin = o["fin"]
+    assert pts.index(u) in p.sets[0][0] and fin["z_t"] == 0 and fin["z"][0] != 0 and o["report"]["z0_zero"] == 0 and fin["l_coef"][16] == 0 and any(fin["l_coef"][:16])
+    assert any(o["line"]) and om.evaluate(o["line"], u) == 0 and o["report"]["last_remainder"] == 0
+    stages = sc.degenerate_stages()
+    for name in ("y=0", "y=0,u=0"):
+        _p, _pts, columns, _evals, y, _v, _u = stages[name]
+        o = opened(stages[name])
+        assert y == 0 and o["prep"]["y_pow"] == [1, 0, 0, 0, 0]  # 0^0 is 1
+        for i, s in enumerate(o["prep"]["sets"]):  # N_i is the set's first column plus the low cells
+            assert o["numer"][i] == [(c + s["neg_r"][d]) % R if d < len(s["neg_r"]) else c for d, c in enumerate(columns[i][0])], i
+        assert o["report"]["bad_sets"] == 0 and o["report"]["last_remainder"] == 0
+    for name in ("v=0", "v=0,u=0"):
+        o = opened(stages[name])
+        q0, _rems = sm.partial_quotient(o["numer"][0], o["prep"]["sets"][0]["pts"])
+        assert stages[name][5] == 0 and o["prep"]["v_pow"] == [1, 0, 0, 0] and o["h"] == q0 and any(q0)  # h is Q_0 alone, scaled by v^0 = 1
+        assert all(not any(s["vw"]) for s in o["prep"]["sets"][1:]) and o["report"]["last_remainder"] == 0
+    for name in ("y=v=1", "y=v=1,u=0"):
+        o = opened(stages[name])
+        assert o["prep"]["y_pow"] == [1] * 5 and o["prep"]["v_pow"] == [1] * 4 and o["report"]["last_remainder"] == 0
+    for name, stage in stages.items():  # u = 0 is super-set point 0, which set 0 of sc.SETS does not hold: z_0 = 0 and L' is zero
+        o = opened(stage)
+        at_zero = name.endswith("u=0")
+        assert (stage[6] == 0) == at_zero and o["report"]["z0_zero"] == int(at_zero) and any(o["line"]) != at_zero and (o["fin"]["l_coef"] == [0] * 5) == at_zero, name
+
+
+@pytest.mark.parametrize("name", sorted(sc.u_on_a_point()) + sorted(sc.degenerate_stages()))
+def test_the_cpu_run_with_u_on_a_point_and_with_challenges_of_0_and_1_is_the_model(drivers, name):
+    d = drivers.dir
+    cells_at = [int(v) for v in drivers("constants")[0].split()][:13]
+    stage = {**sc.u_on_a_point(), **sc.degenerate_stages()}[name]
+    k = sc.FULL_K
+    write_stage(d, stage)
+    drivers("stage", k, d / "plan.txt", d / "cells.bin", d / "out.bin")
+    held(np.fromfile(d / "out.bin", np.uint8), k, stage[0], opened(stage), cells_at)
 
 
 @pytest.mark.parametrize("build,t", (("plain", 2), ("plain", 3), ("sanitized", 2)))

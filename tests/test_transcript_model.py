@@ -160,3 +160,56 @@ def test_the_overflow_changes_no_challenge_and_the_cases_are_what_they_say():
     for name, first, count in (("identity_first", 0, 1), ("identity_last", 6, 1), ("identity_twice", 2, 3)):
         st = tm.run(cases[name].ops)[0].status()
         assert (st["first_identity"], st["identities"]) == (first, count), name
+
+
+def test_the_cases_beyond_the_first_chunk_are_what_they_say(drivers):
+    chunk_points, chunk_scalars = [int(v) for v in drivers("constants")[0].split()][:2]
+    cases = tc.cases(chunk_points, chunk_scalars)
+    every = {0} | set(range(1, tc.BLOCK + 1))
+    # the two sweeps: every call is a chunk and one item, the model enters them at the fills the arithmetic gives, and between
+    # the two every fill is entered, the full block included
+    entered = {}
+    for name, kind, chunk, message in (("every_fill_into_long_scalars", "write_scalars", chunk_scalars, tm.SCALAR_MESSAGE),
+                                       ("every_fill_into_long_points", "write_points", chunk_points, tm.POINT_MESSAGE)):
+        ops = cases[name].ops
+        calls = [items for op, items in ops if op != "squeeze"]
+        assert len(calls) == tc.BLOCK and all(len(items) == chunk + 1 for items in calls) and {op for op, _ in ops} == {kind, "squeeze"}
+        assert (chunk + 1) * message % 2 == 1 and ops[-1] == tc.SQUEEZE and sum(op == tc.SQUEEZE for op in ops[1:]) == tc.BLOCK // 16
+        entered[name] = {fill for _at, fill in tc.entry_fills(ops)}
+        assert entered[name] == tc.sweep_fills(ops, (chunk + 1) * message), name
+    assert entered["every_fill_into_long_scalars"] | entered["every_fill_into_long_points"] == every
+    assert len({p for _op, items in cases["every_fill_into_long_points"].ops[1:] if items for p in items}) == 256  # the basis, cyclically
+    # the longest stream: the long call finds a full block, and its first chunk lays a whole chunk behind it
+    for name, chunk, message in (("full_block_then_longest_stream_scalars", chunk_scalars, tm.SCALAR_MESSAGE), ("full_block_then_longest_stream_points", chunk_points, tm.POINT_MESSAGE)):
+        ops = cases[name].ops
+        (at, fill), = [(at, fill) for at, fill in tc.entry_fills(ops) if len(ops[at][1]) == 2 * chunk + 1]
+        assert fill == tc.BLOCK and tc.SQUEEZE not in ops[:at] and ops[at + 1:] == (tc.SQUEEZE,), name
+        stream = fill + chunk * message
+        assert stream == (128 + 32 * 65 if name.endswith("points") else 128 + 64 * 33), name  # 2240 bytes: the longest the kernel lays out
+    # calls that are whole chunks, one and two, of either kind
+    sizes = [(op, len(items)) for op, items in cases["exact_chunks"].ops if items]
+    assert sizes == [("write_points", chunk_points), ("write_points", 2 * chunk_points), ("write_scalars", chunk_scalars), ("write_scalars", 2 * chunk_scalars)]
+    assert [op for op, _items in cases["exact_chunks"].ops[1::2]] == ["squeeze"] * 4
+    # the identities
+    ops = cases["identity_across_chunks"].ops
+    assert ops[0][0] == "common_points" and len(ops[0][1]) == 2 and len(ops[1][1]) == 2 * chunk_points + 3
+    assert [i for i, p in enumerate(ops[1][1]) if p is None] == [chunk_points - 1, chunk_points, 2 * chunk_points + 2]
+    t = tm.run(ops)[0]
+    assert (t.first_identity, t.identities) == (2 + chunk_points - 1, 3)
+    assert [i for i in range(len(t.proof) // 32) if t.proof[32 * i:32 * i + 32] == bytes(32)] == [chunk_points - 1, chunk_points, 2 * chunk_points + 2]
+    t = tm.run(cases["identity_in_the_second_chunk"].ops)[0]
+    assert (t.first_identity, t.identities) == (2 + 2 * chunk_points - 1, 2) and t.first_identity - 2 >= chunk_points
+    pts = cases["half_identities"].ops[0][1]
+    halves = [(bool(p[0]), bool(p[1])) for p in pts if p is not None]
+    assert (False, True) in halves and (True, False) in halves and pts[-1] is None and pts.count(None) == 1
+    assert any(a is not None and b is not None and a[1] == 0 and b[0] == 0 and a[0] and b[1] for a, b in zip(pts, pts[1:]))  # y = 0 next to x = 0
+    t = tm.run(cases["half_identities"].ops)[0]
+    assert (t.first_identity, t.identities) == (len(pts) - 1, 1) and t.proof.count(bytes(32)) == 1 and t.proof.endswith(bytes(32))
+    # a proof buffer that ends inside a sixteen-byte piece: 1 and 15 bytes of room in either piece of the third item
+    room, model = cases["overflow_with_room"], tm.run(cases["overflow"].ops)[0]
+    assert sorted((c - 2 * tm.PROOF_ITEM) // tc.PIECE for c in tc.CUT_INSIDE_A_PIECE) == [0, 0, 1, 1]
+    assert sorted(c % tc.PIECE for c in tc.CUT_INSIDE_A_PIECE) == [1, 1, tc.PIECE - 1, tc.PIECE - 1]  # the room in the piece that is cut
+    for capacity in tc.CUT_INSIDE_A_PIECE:
+        cut = cases["overflow_at_%d" % capacity]
+        assert cut.ops == room.ops and cut.capacity == capacity and 2 * tm.PROOF_ITEM < capacity < 3 * tm.PROOF_ITEM
+        assert model.status(capacity)["proof_missed"] == len(model.proof) - capacity
