@@ -1,6 +1,9 @@
 // aesw_shplonk.h -- the rules of libaesw_shplonk.so, once: SHPLONK's multi-opening argument over coefficient
 // columns.  It is halo2_proofs v0.3.0 poly/kzg/multiopen/shplonk/prover.rs restated from memory: parity with halo2 is NOT PINNED
 // (no Rust toolchain here, as in aesw_open.h and aesw_transcript.h); what is pinned, exactly, is tests/shplonk_model.py.
+// The argument itself -- that [h] and [W] open the columns' commitments to the claimed evaluations -- is held by
+// tests/kzg_verifier.py, a verifier written from the other side of the paper that shares no rule with this header or that model;
+// it holds neither halo2's transcript order nor its order of the point sets.
 //
 // A PLAN is static and made on the host: P distinct super-set points (cells in device memory), S sets; set i holds t_i strictly
 // increasing indices into the super set and m_i columns.  With y, v, u cells in device memory and e_ijs the evaluation of column
