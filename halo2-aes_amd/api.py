@@ -35,6 +35,7 @@ OPEN_LIB_PATH = _PKG / "libaesw_open.so"  # coefficient columns evaluated at poi
 MSM_LIB_PATH = _PKG / "libaesw_msm.so"  # columns of cells or bytes committed against a basis of points of bn256's G1 (include/aesw_msm.h)
 TRANSCRIPT_LIB_PATH = _PKG / "libaesw_transcript.so"  # the Blake2b transcript: challenges from commitments, and the proof bytes (include/aesw_transcript.h)
 SHPLONK_LIB_PATH = _PKG / "libaesw_shplonk.so"  # SHPLONK's two quotients over every queried column (include/aesw_shplonk.h)
+VANISH_LIB_PATH = _PKG / "libaesw_vanish.so"  # the quotient h(X) folded one constraint segment per call (include/aesw_vanish.h)
 
 STATUS = {
     0: "AESW_OK", 1: "AESW_ERR_INVALID_ARG", 2: "AESW_ERR_NO_DEVICE", 3: "AESW_ERR_HIP", 4: "AESW_ERR_NOMEM",
@@ -320,6 +321,23 @@ SHPLONK_SYMBOLS = {
     "aesw_shplonk_combine_device": (_I, [_P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _P]),
     "aesw_shplonk_quotient_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
+# include/aesw_vanish.h
+VANISH_SYMBOLS = {
+    "aesw_vanish_shape_ok": (_I, [_U32, _U32, _U32, _U32, _U32, _U32]),
+    "aesw_vanish_tables_bytes": (C.c_size_t, [_U32, _U32]),
+    "aesw_vanish_tables_device": (_I, [_P, _U32, _U32, _U32, _P, _P]),
+    "aesw_vanish_scalars_bytes": (C.c_size_t, [_U32, _U32]),
+    "aesw_vanish_scalars_offset": (C.c_size_t, [_U32, _U32]),
+    "aesw_vanish_scalars_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P]),
+    "aesw_vanish_head_device": (_I, [_P, _U32, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "aesw_vanish_perm_device": (_I, [_P, _U32, _U32, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aesw_vanish_lookup_device": (_I, [_P, _U32, _U32, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aesw_vanish_divide_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P]),
+}
+# the entries of the scalars block (AESW_VANISH_THETA ... AESW_VANISH_BETA_DELTA), for vanishing_scalar
+VANISH_TABLES = ("theta", "beta", "gamma", "y", "y_pow", "theta_pow", "tag", "delta", "beta_delta")
+# the column groups of the quotient, in the order Context.quotient_extended takes them
+QUOTIENT_GROUPS = ("advice", "rcon", "selectors", "table", "sigma", "zperm", "a", "s", "zlookup", "l")
 # the tables of the scalars block (AESW_SHPLONK_PLAN ... AESW_SHPLONK_Y_POW), for shplonk_table
 SHPLONK_TABLES = ("plan", "v_pow", "ebar", "w", "vw", "neg_r", "z", "z_t", "z0_inv", "l_coef", "l_const", "l_low", "y_pow")
 SHPLONK_REPORT_LAST_REM = 32  # AESW_SHPLONK_REPORT_LAST_REM
@@ -359,6 +377,10 @@ _PROOF_LIBRARIES = {
 _MULTIOPEN_LIBRARIES = {
     "shplonk": (SHPLONK_LIB_PATH, SHPLONK_SYMBOLS, _NO_FALLBACK),
 }
+# the libraries of _build.vanishing_library_names(), in its order: the same entry shape, consulted after _MULTIOPEN_LIBRARIES
+_VANISHING_LIBRARIES = {
+    "vanish": (VANISH_LIB_PATH, VANISH_SYMBOLS, _NO_FALLBACK),
+}
 _loaded = {}  # name -> the CDLL of the default path
 
 
@@ -367,7 +389,7 @@ def _load(name: str, path) -> C.CDLL:
     loaded once; an explicit path is loaded anew and never cached.  A missing library is an error: there is no fallback."""
     if path is None and name in _loaded:
         return _loaded[name]
-    default, symbols, hint = next(table[name] for table in (_LIBRARIES, _CURVE_LIBRARIES, _PROOF_LIBRARIES, _MULTIOPEN_LIBRARIES) if name in table)
+    default, symbols, hint = next(table[name] for table in (_LIBRARIES, _CURVE_LIBRARIES, _PROOF_LIBRARIES, _MULTIOPEN_LIBRARIES, _VANISHING_LIBRARIES) if name in table)
     if name == "aesw":
         # torch ships its own libamdhip64.so.7 and dlopen()s it by path.  Import it
         # FIRST so libaesw.so's NEEDED libamdhip64.so.7 binds to that copy: two HIP
@@ -486,6 +508,31 @@ def load_shplonk_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_shplonk.so (in-tree): SHPLONK's multi-opening argument behind Context.shplonk_prepare, shplonk_finish,
     combine_columns, set_quotient and open_shplonk."""
     return _load("shplonk", path)
+
+
+def load_vanish_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_vanish.so (in-tree): the quotient h(X) behind Context.vanishing_tables, vanishing_scalars,
+    quotient_accumulator and quotient_extended."""
+    return _load("vanish", path)
+
+
+def permutation_sets(n_sets: int, chunk_len: int) -> int:
+    """The sets the permutation's 3 n_sets + 2 columns are cut into."""
+    return -(-(3 * n_sets + 2) // chunk_len)
+
+
+def permutation_source(n_sets: int, c: int):
+    """Where column c of the permutation (x0 y0 z0 words rcon x1 y1 z1 ...) lies: ("advice", its column) or ("rcon", 0)."""
+    return ("advice", c) if c < 3 else ("advice", 3 * n_sets) if c == 3 else ("rcon", 0) if c == 4 else ("advice", c - 2)
+
+
+def quotient_pieces(h_coeff, k: int, ext_k: int):
+    """The m = 2^(ext_k - k) pieces h_0 ... h_(m-1) of the quotient, h(X) = sum_i X^(n i) h_i(X): views of 2^k coefficients each of
+    what extended_to_coeff returns for the quotient, a [2^ext_k, 32] tensor (or numpy array) of cells.  No copy and no kernel."""
+    k, ext_k = int(k), int(ext_k)
+    if not 0 <= k <= ext_k <= 28 or tuple(h_coeff.shape) != (1 << ext_k, 32):
+        raise ValueError("h_coeff must have shape [2^ext_k, 32] and k must be at most ext_k")
+    return [h_coeff[i << k:(i + 1) << k] for i in range(1 << (ext_k - k))]
 
 
 class MultiopenPlan:
@@ -1928,6 +1975,84 @@ class Context:
         transcript.write_points(out[1:])
         return out, report
 
+    def vanishing_tables(self, k: int, ext_k: int, zeta_sel: int = 1, _out=None):
+        """aesw_vanish_tables_device (libaesw_vanish.so): the tables of the quotient on the coset of (k, ext_k, zeta_sel), free of the
+        challenges -- inv(x^n - 1) for the m values of x^n and the powers x_j is one product of -- as a uint8 tensor."""
+        call = "aesw_vanish_tables_device"
+        lib = load_vanish_library()
+        k, ext_k, zeta_sel = int(k), int(ext_k), int(zeta_sel)
+        need = int(lib.aesw_vanish_tables_bytes(k, ext_k)) if 0 <= k < 2 ** 32 and 0 <= ext_k < 2 ** 32 else 0
+        if not need or not 0 <= zeta_sel <= 1:
+            raise AeswError(ERR_INVALID_ARG, call + ": k must be 10 ... 28, ext_k k + 2 ... 28 and zeta_sel 0 or 1")
+        _out = self._output(_out, "_out", (need,), min_bytes=need)
+        self._check(lib.aesw_vanish_tables_device(self._h, k, ext_k, zeta_sel, _out.data_ptr(), self._stream()), call)
+        return _out
+
+    def vanishing_scalars(self, n_sets: int, chunk_len: int, theta, beta, gamma, y, _out=None):
+        """aesw_vanish_scalars_device: the scalars block of the quotient's segments -- the challenges, y^len per segment kind, theta^2,
+        theta^3, t * theta^(arity - 1) per tag, delta^first(s) and beta * delta^first(s) per permutation set -- as a uint8 tensor
+        (vanishing_scalar reads it).  theta, beta, gamma, y: ints or uint8 [32] tensors on the device (what Transcript.squeeze
+        returns), read when the kernel runs: a captured call follows new challenges."""
+        call = "aesw_vanish_scalars_device"
+        lib = load_vanish_library()
+        n_sets, chunk_len = int(n_sets), int(chunk_len)
+        need = int(lib.aesw_vanish_scalars_bytes(n_sets, chunk_len)) if 0 <= n_sets < 2 ** 32 and 0 <= chunk_len < 2 ** 32 else 0
+        if not need:
+            raise AeswError(ERR_INVALID_ARG, call + ": n_sets must be 1 ... 1024 and chunk_len 1 ... 8")
+        theta, beta, gamma, y = (self._challenge(v, name) for v, name in ((theta, "theta"), (beta, "beta"), (gamma, "gamma"), (y, "y")))
+        _out = self._output(_out, "_out", (need,), min_bytes=need)
+        rc = lib.aesw_vanish_scalars_device(self._h, n_sets, chunk_len, theta.data_ptr(), beta.data_ptr(), gamma.data_ptr(), y.data_ptr(), _out.data_ptr(), self._stream())
+        self._check(rc, call)
+        return _out
+
+    def vanishing_scalar(self, scalars, table: str, index: int = 0, cells: int = 1):
+        """The `cells` cells from entry `index` of `table` (a name of VANISH_TABLES) in the block vanishing_scalars returns, as a
+        uint8 [cells, 32] view: aesw_vanish_scalars_offset says where they lie (the entries of delta and beta_delta lie 64 bytes apart)."""
+        at = int(load_vanish_library().aesw_vanish_scalars_offset(VANISH_TABLES.index(table), int(index)))
+        if at == C.c_size_t(-1).value:
+            raise AeswError(ERR_INVALID_ARG, "vanishing_scalar: no entry %d in table %s" % (index, table))
+        return self._tensor(scalars, "scalars", min_bytes=at + 32 * cells).view(-1)[at:at + 32 * cells].view(cells, 32)
+
+    def quotient_accumulator(self, k: int, ext_k: int, zeta_sel: int, n_sets: int, chunk_len: int, n_rows: int, tables, scalars, _acc=None) -> "QuotientAccumulator":
+        """The quotient h(X) on the extended coset, one constraint segment per call (libaesw_vanish.so): an accumulator that owns the
+        acc column and takes head(...), permutation_set(s, ...) for every permutation set, lookup_set(s, ...) for every column set
+        and divide(), in that order -- each reads only its own extended columns, so a caller extends a group, folds it and uses
+        the buffer again.  tables: what vanishing_tables returns for (k, ext_k, zeta_sel); scalars: what vanishing_scalars returns
+        for (n_sets, chunk_len).  Neither the order of the constraints nor zeta is pinned against halo2 (include/aesw_vanish.h)."""
+        return QuotientAccumulator(self, k, ext_k, zeta_sel, n_sets, chunk_len, n_rows, tables, scalars, _acc)
+
+    def quotient_extended(self, groups, k: int, ext_k: int, zeta_sel: int, n_sets: int, chunk_len: int, n_rows: int, theta, beta, gamma, y, tables=None, out=None):
+        """The quotient over the ten column groups at once, for a caller that has every extended column resident: a uint8
+        [2^ext_k, 32] tensor, halo2's evaluate_h.  groups: a dict by the names of QUOTIENT_GROUPS, or a sequence in their order, of
+        uint8 [columns, 2^ext_k, 32] tensors (what coeff_to_extended returns).  Written on top of quotient_accumulator; the
+        columns of a permutation set are gathered into a buffer of chunk_len columns, since they do not lie next to each other.
+        It allocates that buffer, the scalars block and, without `tables`, the tables inside the call: capture the accumulator's own
+        calls instead (quotient_accumulator with tensors made beforehand), as tests/test_gpu_vanish_calls.py does."""
+        if not isinstance(groups, dict):
+            groups = dict(zip(QUOTIENT_GROUPS, groups))
+        if sorted(groups) != sorted(QUOTIENT_GROUPS):
+            raise ValueError("groups must hold %s" % ", ".join(QUOTIENT_GROUPS))
+        tables = self.vanishing_tables(k, ext_k, zeta_sel) if tables is None else tables
+        acc = self.quotient_accumulator(k, ext_k, zeta_sel, n_sets, chunk_len, n_rows, tables, self.vanishing_scalars(n_sets, chunk_len, theta, beta, gamma, y), _acc=out)
+        n_sets, chunk_len, rows = acc.n_sets, acc.chunk_len, 1 << acc.ext_k
+        count = {"advice": 3 * n_sets + 1, "rcon": 2, "selectors": 5 * n_sets, "table": 4, "sigma": 3 * n_sets + 2, "zperm": acc.perm_sets, "a": 5 * n_sets, "s": 5 * n_sets,
+                 "zlookup": 5 * n_sets, "l": 3}
+        for name in QUOTIENT_GROUPS:
+            self._tensor(groups[name], name, shape=(count[name], rows, 32))
+        acc.head(groups["advice"][3 * n_sets], groups["rcon"], groups["zperm"], groups["l"])
+        values = self._output(None, "values", (chunk_len, rows, 32))
+        for s in range(acc.perm_sets):
+            first, end = s * chunk_len, min((s + 1) * chunk_len, 3 * n_sets + 2)
+            for c in range(first, end):
+                group, column = permutation_source(n_sets, c)
+                values[c - first].copy_(groups[group][column])
+            acc.permutation_set(s, values[:end - first], groups["sigma"][first:end], groups["zperm"][s], groups["l"])
+        for s in range(n_sets):
+            five = slice(5 * s, 5 * s + 5)
+            acc.lookup_set(s, groups["advice"][3 * s:3 * s + 3], groups["selectors"][five], groups["table"], groups["a"][five], groups["s"][five], groups["zlookup"][five],
+                           groups["l"])
+        return acc.divide()
+
     def transcript(self, proof_capacity: int = 0, _state=None, _proof=None) -> "Transcript":
         """A fresh Blake2b transcript on the device (libaesw_transcript.so): commitments and scalars go in where they lie,
         challenges come out as uint8 [32] device tensors that compress_table, invert_table, grand_product, permutation_product
@@ -2141,6 +2266,96 @@ def transcript_status_dict(rep) -> dict:
     return {"proof_bytes": v[26], "proof_missed": v[27], "identities": v[28], "first_identity": None if v[29] == _NONE else v[29]}
 
 
+class QuotientAccumulator:
+    """What Context.quotient_accumulator returns: the fold of the quotient's constraints, cut into segments (include/aesw_vanish.h).
+    It owns acc, a uint8 [2^ext_k, 32] tensor every segment folds into in place.  The segments come in the fold's order -- head,
+    permutation_set(0) ... (S - 1), lookup_set(0) ... (n_sets - 1), divide -- and each once: another order is another
+    polynomial, so it is refused (AeswError, nothing enqueued).  Every method is asynchronous on the current stream and
+    allocates nothing, so the whole fold can be captured into one graph; restart() opens the next fold over the same acc."""
+
+    def __init__(self, ctx: "Context", k, ext_k, zeta_sel, n_sets, chunk_len, n_rows, tables, scalars, _acc=None):
+        self._lib = load_vanish_library()
+        self.ctx = ctx
+        self.k, self.ext_k, self.zeta_sel, self.n_sets, self.chunk_len, self.n_rows = (int(v) for v in (k, ext_k, zeta_sel, n_sets, chunk_len, n_rows))
+        shape = (self.k, self.ext_k, self.zeta_sel, self.n_sets, self.chunk_len, self.n_rows)  # the bounds are the library's: csrc/aesw_quot.h's quot_shape_ok
+        if not all(0 <= v < 2 ** 32 for v in shape) or not self._lib.aesw_vanish_shape_ok(*shape):
+            raise AeswError(ERR_INVALID_ARG, "quotient_accumulator: k must be 10 ... 28 and ext_k k + 2 ... 28, zeta_sel 0 or 1, n_sets 1 ... 1024, chunk_len 1 ... 8 with "
+                            "chunk_len + 2 <= 2^(ext_k - k) + 1, n_rows 1 ... 2^k - 1")
+        self.perm_sets = permutation_sets(self.n_sets, self.chunk_len)
+        self.tables = ctx._tensor(tables, "tables", min_bytes=int(self._lib.aesw_vanish_tables_bytes(self.k, self.ext_k)))
+        self.scalars = ctx._tensor(scalars, "scalars", min_bytes=int(self._lib.aesw_vanish_scalars_bytes(self.n_sets, self.chunk_len)))
+        self.acc = ctx._output(_acc, "_acc", (1 << self.ext_k, 32))
+        self._order = [("head", 0)] + [("permutation_set", s) for s in range(self.perm_sets)] + [("lookup_set", s) for s in range(self.n_sets)] + [("divide", 0)]
+        self._done = 0
+
+    def restart(self):
+        """The next fold over the same acc: head comes next again."""
+        self._done = 0
+        return self
+
+    def _turn(self, segment, s=0):
+        s = int(s)
+        want = self._order[self._done] if self._done < len(self._order) else None
+        if want != (segment, s):
+            raise AeswError(ERR_INVALID_ARG, "quotient_accumulator: %s(%d) is out of order or given twice: %s" %
+                            (segment, s, "the fold is complete" if want is None else "%s(%d) comes next" % want))
+        return s
+
+    def _group(self, t, name, columns):
+        rows = 1 << self.ext_k
+        return self.ctx._tensor(t, name, shape=[(columns, rows, 32), (rows, 32)] if columns == 1 else (columns, rows, 32))
+
+    def _shape(self):
+        return (self.k, self.ext_k, self.n_sets, self.chunk_len, self.n_rows)
+
+    def head(self, words, rcon, zperm, l):
+        """HEAD: the gate and the constraints that tie the permutation's grand products together.  words: the round-constant advice
+        column, advice[3 n_sets]; rcon [2], zperm [S], l [3]: those groups extended.  It opens the fold: acc is written, not read."""
+        call = "aesw_vanish_head_device"
+        self._turn("head")
+        words, rcon, zperm, l = self._group(words, "words", 1), self._group(rcon, "rcon", 2), self._group(zperm, "zperm", self.perm_sets), self._group(l, "l", 3)
+        rc = self._lib.aesw_vanish_head_device(self.ctx._h, *self._shape(), words.data_ptr(), rcon.data_ptr(), zperm.data_ptr(), l.data_ptr(), self.scalars.data_ptr(),
+                                               self.acc.data_ptr(), self.ctx._stream())
+        self.ctx._check(rc, call)
+        self._done += 1
+        return self
+
+    def permutation_set(self, s: int, values, sigma, z, l):
+        """PERM(s): the product constraint of permutation set s.  values, sigma: only the columns of that set, in the permutation's
+        order (permutation_source says where column c lies), extended; z: Zp_s; l [3]."""
+        call = "aesw_vanish_perm_device"
+        s = self._turn("permutation_set", s)
+        columns = min((s + 1) * self.chunk_len, 3 * self.n_sets + 2) - s * self.chunk_len
+        values, sigma, z, l = self._group(values, "values", columns), self._group(sigma, "sigma", columns), self._group(z, "z", 1), self._group(l, "l", 3)
+        rc = self._lib.aesw_vanish_perm_device(self.ctx._h, *self._shape(), s, values.data_ptr(), sigma.data_ptr(), z.data_ptr(), l.data_ptr(), self.tables.data_ptr(),
+                                               self.scalars.data_ptr(), self.acc.data_ptr(), self.acc.data_ptr(), self.ctx._stream())
+        self.ctx._check(rc, call)
+        self._done += 1
+        return self
+
+    def lookup_set(self, s: int, advice3, selectors5, table4, a5, s5, z5, l):
+        """LOOKUP(s): the 25 constraints of column set s.  advice3: the set's columns x, y, z; selectors5, a5, s5, z5: the selector,
+        A', S' and Z of its five arguments; table4: the table; l [3]; all extended."""
+        call = "aesw_vanish_lookup_device"
+        s = self._turn("lookup_set", s)
+        advice3, table4, l = self._group(advice3, "advice3", 3), self._group(table4, "table4", 4), self._group(l, "l", 3)
+        selectors5, a5, s5, z5 = (self._group(t, name, 5) for t, name in ((selectors5, "selectors5"), (a5, "a5"), (s5, "s5"), (z5, "z5")))
+        rc = self._lib.aesw_vanish_lookup_device(self.ctx._h, *self._shape(), s, advice3.data_ptr(), selectors5.data_ptr(), table4.data_ptr(), a5.data_ptr(), s5.data_ptr(),
+                                                 z5.data_ptr(), l.data_ptr(), self.scalars.data_ptr(), self.acc.data_ptr(), self.acc.data_ptr(), self.ctx._stream())
+        self.ctx._check(rc, call)
+        self._done += 1
+        return self
+
+    def divide(self):
+        """DIVIDE: acc * inv(x_j^n - 1) in place; returns acc, the quotient on the extended coset (extended_to_coeff takes it)."""
+        call = "aesw_vanish_divide_device"
+        self._turn("divide")
+        rc = self._lib.aesw_vanish_divide_device(self.ctx._h, self.k, self.ext_k, self.tables.data_ptr(), self.acc.data_ptr(), self.acc.data_ptr(), self.ctx._stream())
+        self.ctx._check(rc, call)
+        self._done += 1
+        return self.acc
+
+
 class Transcript:
     """What Context.transcript returns: halo2's Blake2bWrite<_, G1Affine, Challenge255<_>> on the device (include/aesw_transcript.h
     states the rule; parity with halo2 itself is not pinned).  Every method but proof() and status() is asynchronous on the
@@ -2340,7 +2555,8 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "compress_table", "lookup_inputs", "prepare_lookup_inputs", "argument_columns", "invert_table", "grand_product",
               "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
               "extended_to_coeff", "permutation_columns_fr", "evaluate_columns", "fold_columns", "divide_columns", "msm_basis",
-              "commit_columns", "transcript", "shplonk_table", "shplonk_prepare", "shplonk_finish", "combine_columns", "set_quotient", "open_shplonk"):
+              "commit_columns", "transcript", "shplonk_table", "shplonk_prepare", "shplonk_finish", "combine_columns", "set_quotient", "open_shplonk",
+              "vanishing_tables", "vanishing_scalars", "vanishing_scalar", "quotient_accumulator", "quotient_extended"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 

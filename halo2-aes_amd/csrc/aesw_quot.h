@@ -2,8 +2,8 @@
 // the extended coset, halo2's evaluate_h.  Here: the bounds, which row a rotation reads, which cell of the vanishing table a row
 // takes, the tables, the label a cell index of sigma names, the order of the column groups, and the fold itself -- every
 // constraint in its order, written over a `load(group, column, row)` of the caller's, so that a kernel and the CPU driver of
-// tests/quot_driver.cpp run the same lines -- with the number of field products it takes per row.  Of these only the label of
-// sigma has a kernel today (quot/aesw_quot.hip); the fold is run by the CPU driver alone (DESIGN.md 4.23 says why).
+// tests/quot_driver.cpp run the same lines -- with the number of field products it takes per row.  Of these the label of sigma
+// has a kernel in quot/aesw_quot.hip; the fold runs on the device cut into segments, aesw_vanish.h's.
 // The field is aesw_fr.h's, omega, delta and the column order of the permutation aesw_sigma.h's, zeta aesw_ntt.h's, the arity of
 // a tag aesw_theta.h's; nothing of them is restated.
 // No HIP call and no ROCm include: the tests compile this header alone with g++.
