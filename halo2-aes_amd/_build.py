@@ -3,7 +3,7 @@
   halo2-aes_amd/libaesw.so        HIP kernels + the C ABI of include/aesw.h (hipcc --offload-arch=gfx950)
   halo2-aes_amd/libaesw_host.so   the C++ mirror of the reference's host interface (include/aesw_host.h): plain g++,
                                   no device code, linked against libaesw.so -- it only calls the C ABI
-  halo2-aes_amd/libaesw_<name>.so one library per entry of LIBRARIES, CURVE_LIBRARIES, PROOF_LIBRARIES, MULTIOPEN_LIBRARIES and VANISHING_LIBRARIES (the tables below say what each is; its public header is
+  halo2-aes_amd/libaesw_<name>.so one library per entry of LIBRARIES, CURVE_LIBRARIES, PROOF_LIBRARIES, MULTIOPEN_LIBRARIES, VANISHING_LIBRARIES and BLINDING_LIBRARIES (the tables below say what each is; its public header is
                                   include/aesw_<name>.h): its own gfx950 kernels and entry points (hipcc), linked against
                                   libaesw.so, whose context it takes.  All are built by build_satellite() alike.
 
@@ -154,7 +154,7 @@ def library_entry(name: str):
 
 
 def _build_entry(name: str, entry, force: bool, extra_flags, out) -> Path:
-    """libaesw_<name>.so from an entry of LIBRARIES, of CURVE_LIBRARIES, of PROOF_LIBRARIES, of MULTIOPEN_LIBRARIES or of VANISHING_LIBRARIES: one hipcc line, NEEDED libaesw.so found next to it ($ORIGIN)."""
+    """libaesw_<name>.so from an entry of LIBRARIES, of CURVE_LIBRARIES, of PROOF_LIBRARIES, of MULTIOPEN_LIBRARIES, of VANISHING_LIBRARIES or of BLINDING_LIBRARIES: one hipcc line, NEEDED libaesw.so found next to it ($ORIGIN)."""
     sources, headers, public = entry
     return _build(PKG / (out or "libaesw_%s.so" % name), sources + SATELLITE_HEADERS + headers + [public, LIB],
                   lambda tmp: _hipcc_shared(sources, tmp, extra_flags, link=["-L" + str(PKG), "-laesw", "-Wl,-rpath,$ORIGIN"]), force)
@@ -241,3 +241,22 @@ def vanishing_library_names() -> list:
 def build_vanishing(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
     """libaesw_<name>.so of an entry of VANISHING_LIBRARIES, as build_satellite builds one of LIBRARIES."""
     return _build_entry(name, VANISHING_LIBRARIES[name], force, extra_flags, out)
+
+
+# The libraries that blind, built after VANISHING_LIBRARIES and in the same way (an entry has the same shape): a table of its own,
+# because the first five are pinned at what they hold.
+#   blind  the blinding rows of a column from a seed in device memory, and the commitment of a column of bytes with a blinded tail
+BLINDING_LIBRARIES = {
+    "blind": ([CSRC / "blind" / "aesw_blind.hip"], [CSRC / "aesw_fr.h", CSRC / "aesw_fq.h", CSRC / "aesw_msm.h", CSRC / "aesw_transcript.h", CSRC / "aesw_blind.h"],
+              INCLUDE / "aesw_blind.h"),
+}
+
+
+def blinding_library_names() -> list:
+    """Every library build_blinding() builds, in the order of BLINDING_LIBRARIES."""
+    return list(BLINDING_LIBRARIES)
+
+
+def build_blinding(name: str, force: bool = False, extra_flags=(), out: Path | None = None) -> Path:
+    """libaesw_<name>.so of an entry of BLINDING_LIBRARIES, as build_satellite builds one of LIBRARIES."""
+    return _build_entry(name, BLINDING_LIBRARIES[name], force, extra_flags, out)

@@ -36,6 +36,7 @@ MSM_LIB_PATH = _PKG / "libaesw_msm.so"  # columns of cells or bytes committed ag
 TRANSCRIPT_LIB_PATH = _PKG / "libaesw_transcript.so"  # the Blake2b transcript: challenges from commitments, and the proof bytes (include/aesw_transcript.h)
 SHPLONK_LIB_PATH = _PKG / "libaesw_shplonk.so"  # SHPLONK's two quotients over every queried column (include/aesw_shplonk.h)
 VANISH_LIB_PATH = _PKG / "libaesw_vanish.so"  # the quotient h(X) folded one constraint segment per call (include/aesw_vanish.h)
+BLIND_LIB_PATH = _PKG / "libaesw_blind.so"  # the blinding rows of a column from a seed, and the commitment of a blinded tail (include/aesw_blind.h)
 
 STATUS = {
     0: "AESW_OK", 1: "AESW_ERR_INVALID_ARG", 2: "AESW_ERR_NO_DEVICE", 3: "AESW_ERR_HIP", 4: "AESW_ERR_NOMEM",
@@ -334,6 +335,15 @@ VANISH_SYMBOLS = {
     "aesw_vanish_lookup_device": (_I, [_P, _U32, _U32, _U32, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aesw_vanish_divide_device": (_I, [_P, _U32, _U32, _P, _P, _P, _P]),
 }
+# include/aesw_blind.h
+BLIND_SYMBOLS = {
+    "aesw_blind_tail_rows": (_U64, [_U32, _U64]),
+    "aesw_blind_max_tail": (_U32, []),
+    "aesw_blind_rows_device": (_I, [_P, _U32, _U32, _U64, _U64, _U64, _P, _P, _P]),
+    "aesw_blind_tail_device": (_I, [_P, _U32, _U32, _U64, _U64, _U64, _P, _P, _P]),
+    "aesw_blind_commit_tail_device": (_I, [_P, _U32, _U32, _U64, _P, _P, _P, _P]),
+}
+BLIND_SEED_BYTES = 32  # AESW_BLIND_SEED_BYTES
 # the entries of the scalars block (AESW_VANISH_THETA ... AESW_VANISH_BETA_DELTA), for vanishing_scalar
 VANISH_TABLES = ("theta", "beta", "gamma", "y", "y_pow", "theta_pow", "tag", "delta", "beta_delta")
 # the column groups of the quotient, in the order Context.quotient_extended takes them
@@ -381,6 +391,10 @@ _MULTIOPEN_LIBRARIES = {
 _VANISHING_LIBRARIES = {
     "vanish": (VANISH_LIB_PATH, VANISH_SYMBOLS, _NO_FALLBACK),
 }
+# the libraries of _build.blinding_library_names(), in its order: the same entry shape, consulted after _VANISHING_LIBRARIES
+_BLINDING_LIBRARIES = {
+    "blind": (BLIND_LIB_PATH, BLIND_SYMBOLS, _NO_FALLBACK),
+}
 _loaded = {}  # name -> the CDLL of the default path
 
 
@@ -389,7 +403,8 @@ def _load(name: str, path) -> C.CDLL:
     loaded once; an explicit path is loaded anew and never cached.  A missing library is an error: there is no fallback."""
     if path is None and name in _loaded:
         return _loaded[name]
-    default, symbols, hint = next(table[name] for table in (_LIBRARIES, _CURVE_LIBRARIES, _PROOF_LIBRARIES, _MULTIOPEN_LIBRARIES, _VANISHING_LIBRARIES) if name in table)
+    default, symbols, hint = next(table[name] for table in (_LIBRARIES, _CURVE_LIBRARIES, _PROOF_LIBRARIES, _MULTIOPEN_LIBRARIES, _VANISHING_LIBRARIES, _BLINDING_LIBRARIES)
+                                 if name in table)
     if name == "aesw":
         # torch ships its own libamdhip64.so.7 and dlopen()s it by path.  Import it
         # FIRST so libaesw.so's NEEDED libamdhip64.so.7 binds to that copy: two HIP
@@ -514,6 +529,12 @@ def load_vanish_library(path: Path | None = None) -> C.CDLL:
     """Load libaesw_vanish.so (in-tree): the quotient h(X) behind Context.vanishing_tables, vanishing_scalars,
     quotient_accumulator and quotient_extended."""
     return _load("vanish", path)
+
+
+def load_blind_library(path: Path | None = None) -> C.CDLL:
+    """Load libaesw_blind.so (in-tree): the blinding cells behind Context.blind_rows and blinding_tail, and the tail commitment
+    behind Context.commit_tail and commit_blinded_bytes."""
+    return _load("blind", path)
 
 
 def permutation_sets(n_sets: int, chunk_len: int) -> int:
@@ -2053,6 +2074,76 @@ class Context:
                            groups["l"])
         return acc.divide()
 
+    def blinding_seed(self, seed: bytes | None = None):
+        """The 32-byte seed of the blinding cells as the calls of libaesw_blind.so read it: a uint8 [32] tensor on the device, read
+        when a kernel runs, so a captured graph follows a seed copied into it.  seed None: secrets.token_bytes(32), the operating
+        system's randomness -- what a prover that wants zero knowledge passes.  A proof is reproducible from its seed."""
+        if seed is None:
+            import secrets
+            seed = secrets.token_bytes(BLIND_SEED_BYTES)
+        seed = bytes(seed)
+        if len(seed) != BLIND_SEED_BYTES:
+            raise ValueError("seed must be %d bytes" % BLIND_SEED_BYTES)
+        return self._torch().from_numpy(np.frombuffer(seed, np.uint8).copy()).to(self._dev())
+
+    def _blind_tail(self, call, k, n_cols, first_row, domain=0, first_column=0):
+        """The arguments of a call of libaesw_blind.so as ints, and the rows of the tail; what the library would refuse of a size is
+        an AeswError before anything is sized by it."""
+        lib = load_blind_library()
+        k, n_cols, first_row, domain, first_column = int(k), int(n_cols), int(first_row), int(domain), int(first_column)
+        tail = int(lib.aesw_blind_tail_rows(k, first_row)) if 0 <= k < 2 ** 32 and 0 <= first_row < 2 ** 64 else 0
+        if not tail or not 1 <= n_cols <= 65535 or not 0 <= domain < 2 ** 64 or not 0 <= first_column < 2 ** 64:
+            raise AeswError(ERR_INVALID_ARG, call + ": k must be 10 ... 28, n_cols 1 ... 65535, first_row below 2^k, domain and first_column below 2^64")
+        return lib, k, n_cols, first_row, domain, first_column, tail
+
+    def blind_rows(self, cells, k: int, first_row: int, seed, domain: int, first_column: int = 0):
+        """aesw_blind_rows_device (libaesw_blind.so): rows first_row ... 2^k - 1 of every column of `cells`, a uint8 [n_cols, 2^k, 32]
+        (or [2^k, 32]) tensor of Fr cells, filled in place with blinding cells, and no other byte touched; returns `cells`.  A cell is
+        BLAKE2b-512 keyed by `seed` (what blinding_seed returns) over (domain, first_column + j, row), reduced mod r
+        (include/aesw_blind.h): `domain` is the caller's tag of this group of columns, so that groups under one seed share no cell."""
+        call = "aesw_blind_rows_device"
+        lib, k, _one, first_row, domain, first_column, _tail = self._blind_tail(call, k, 1, first_row, domain, first_column)
+        n_cols = self._columns(cells, "cells", k)
+        seed = self._tensor(seed, "seed", shape=(BLIND_SEED_BYTES,))
+        self._check(lib.aesw_blind_rows_device(self._h, k, n_cols, first_row, domain, first_column, seed.data_ptr(), cells.data_ptr(), self._stream()), call)
+        return cells
+
+    def blinding_tail(self, k: int, n_cols: int, first_row: int, seed, domain: int, first_column: int = 0, out=None):
+        """aesw_blind_tail_device: the same cells compactly, a uint8 [n_cols, 2^k - first_row, 32] tensor -- the tail of columns whose
+        body is bytes (commit_blinded_bytes takes it)."""
+        call = "aesw_blind_tail_device"
+        lib, k, n_cols, first_row, domain, first_column, tail = self._blind_tail(call, k, n_cols, first_row, domain, first_column)
+        seed = self._tensor(seed, "seed", shape=(BLIND_SEED_BYTES,))
+        out = self._output(out, "out", (n_cols, tail, 32))
+        self._check(lib.aesw_blind_tail_device(self._h, k, n_cols, first_row, domain, first_column, seed.data_ptr(), out.data_ptr(), self._stream()), call)
+        return out
+
+    def commit_tail(self, tail, k: int, first_row: int, basis, commitments):
+        """aesw_blind_commit_tail_device: commitments[j] += sum_i tail[j][i] * basis[first_row + i], in place; returns `commitments`.
+        tail: uint8 [n_cols, 2^k - first_row, 32], any canonical cells, at most 64 rows; basis: uint8 [2^k, 64], what msm_basis
+        returns; commitments: uint8 [n_cols, 64], what commit_columns returns.  The scalars are secret: the kernel's double-and-add
+        runs the same steps whatever they are."""
+        call = "aesw_blind_commit_tail_device"
+        n_cols = tail.shape[0] if hasattr(tail, "shape") and len(tail.shape) == 3 else 0
+        lib, k, n_cols, first_row, _domain, _column, rows = self._blind_tail(call, k, n_cols, first_row)
+        if rows > int(lib.aesw_blind_max_tail()):
+            raise AeswError(ERR_INVALID_ARG, call + ": the tail, 2^k - first_row rows, must be at most %d" % int(lib.aesw_blind_max_tail()))
+        basis = self._tensor(basis, "basis", shape=(1 << k, 64))
+        tail = self._tensor(tail, "tail", shape=(n_cols, rows, 32))
+        commitments = self._tensor(commitments, "commitments", shape=(n_cols, 64))
+        self._check(lib.aesw_blind_commit_tail_device(self._h, k, n_cols, first_row, tail.data_ptr(), basis.data_ptr(), commitments.data_ptr(), self._stream()), call)
+        return commitments
+
+    def commit_blinded_bytes(self, byte_columns, tail, k: int, first_row: int, basis, out=None, _workspace=None):
+        """The commitments of columns of bytes whose rows from first_row on are the cells of `tail`: commit_columns over the bytes --
+        one 8-bit window, a thirty-second of the work of a column of cells -- then commit_tail in place: two enqueues and no wait.
+        byte_columns: uint8 [n_cols, 2^k], the rows from first_row on zero (a byte left there is added to its tail cell); tail: uint8
+        [n_cols, 2^k - first_row, 32] (blinding_tail).  Returns a uint8 [n_cols, 64] tensor: byte for byte what commit_columns gives
+        for the same columns expanded to cells with blind_rows applied."""
+        self._tensor(byte_columns, "byte_columns", shape=(None, 1 << int(k)) if 0 <= int(k) <= 28 else None)
+        out = self.commit_columns(byte_columns, basis, out=out, _workspace=_workspace)
+        return self.commit_tail(tail, k, first_row, basis, out)
+
     def transcript(self, proof_capacity: int = 0, _state=None, _proof=None) -> "Transcript":
         """A fresh Blake2b transcript on the device (libaesw_transcript.so): commitments and scalars go in where they lie,
         challenges come out as uint8 [32] device tensors that compress_table, invert_table, grand_product, permutation_product
@@ -2556,7 +2647,8 @@ for _name in ("alloc_witness", "alloc_columns", "free_columns", "schedule_key", 
               "permutation_tables", "permutation_product", "ntt_tables", "lagrange_to_coeff", "coeff_to_lagrange", "coeff_to_extended",
               "extended_to_coeff", "permutation_columns_fr", "evaluate_columns", "fold_columns", "divide_columns", "msm_basis",
               "commit_columns", "transcript", "shplonk_table", "shplonk_prepare", "shplonk_finish", "combine_columns", "set_quotient", "open_shplonk",
-              "vanishing_tables", "vanishing_scalars", "vanishing_scalar", "quotient_accumulator", "quotient_extended"):
+              "vanishing_tables", "vanishing_scalars", "vanishing_scalar", "quotient_accumulator", "quotient_extended",
+              "blinding_seed", "blind_rows", "blinding_tail", "commit_tail", "commit_blinded_bytes"):
     setattr(Group, _name, _group_refuses(_name))
 del _name
 
